@@ -8,11 +8,22 @@ only collective is the barrier / max-reduction of the timing, `value` = N*K toke
 
 A "step" = one decode token of Llama-2-7B (fp16, random-init weights at the exact shapes, synthetic
 prompt, thresholds calibrated to the configured sparsity on the synthetic activations) through the
-hipGraph-captured decode step.  One JSON line on rank 0, with:
-  roofline      HBM roofline of the dominant kernel (the MLP gate/up sparse GEMV), achieved =
-                algorithmic bytes / average launch duration measured live with HIP events;
-  cpu_baseline  the CPU oracle port (oracle/, OpenMP) timed on this box's host cores on a bounded
-                sample of the same workload (one layer's projections + lm_head, scaled to a token).
+hipGraph-captured decode step.  One JSON line on rank 0.
+
+A plain run sets up, warms up, times exactly --steps steps and prints the headline (`value`, `ms_per_step`).
+--full adds everything else the line can carry, each measured after the timed steps:
+  kept_fraction     achieved kept fraction of every projection on the timed decode positions;
+  roofline          HBM roofline of the dominant kernel (the MLP gate/up sparse GEMV), achieved =
+                    algorithmic bytes / average launch duration measured live with HIP events;
+  dense comparators the same engine with every row kept (+ floor_model) and the un-patched model;
+  value_at_context  the same step at ~1000 / ~3800 cached positions;
+  cpu_baseline      the CPU oracle port (oracle/, OpenMP) timed on the host cores on a bounded
+                    sample of the same workload (one layer's projections + lm_head, scaled to a token).
+The --no-* switches drop single legs of a --full run.
+
+--dump-outputs DIR writes what the last timed step handed its caller (logits and sampled token of the engine
+path; the sampled token of the drop-in path) as float32 / float64 .npy files; the inputs depend only on the
+arguments (seeded weights, prompt, calibration and sampler), so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -88,6 +99,11 @@ def parse():
     ap.add_argument("--profile-markers", action="store_true",
                     help="bracket the timed region with one marker dispatch each (compact_kernel on 64 elements) so that "
                          "scripts/summarize_prof.py can restrict a rocprofv3 trace / counter pass to the timed hipGraph replays")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure kept fractions, the roofline, the dense comparators, the context "
+                         "sweep and the CPU baseline (off: the run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (logits, sampled token) as .npy files into DIR")
     return ap.parse_args()
 
 
@@ -215,7 +231,24 @@ def make_stepper(model, a, dense=False):
         dec.tok.copy_(dec.out_tok.view(1, 1))  # feed the sampled token back, advance the position
         dec.pos.add_(one)
 
+    info["decoder"] = dec
     return step, info
+
+
+def dump_outputs(path, mode, info):
+    """What the last timed step handed its caller, one .npy per array under `path` (float32; token ids as float64):
+    engine   logits.npy [vocab] (the step's logits), token.npy [1] (the token the fused sampler drew from them and feeds
+             to the next step);
+    dropin   token.npy [1] (what GraphedDecoder returns; its logits live in the graph's private pool)."""
+    if mode == "engine":
+        eng = info["engine"]
+        arrays = {"logits": eng.logits.detach().float().reshape(-1).cpu().numpy(),
+                  "token": eng.tok_buf.detach().reshape(-1).cpu().numpy().astype(np.float64)}
+    else:
+        arrays = {"token": info["decoder"].out_tok.detach().reshape(-1).cpu().numpy().astype(np.float64)}
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(v))
 
 
 def roofline_dominant_kernel(model, a):
@@ -642,6 +675,8 @@ def main():
     else:
         step, info = make_stepper(model, a)
     t = timed_decode(step, a.steps, a.warmup, world, markers=a.profile_markers)
+    if a.dump_outputs and rank == 0:  # before anything below runs the engine again
+        dump_outputs(a.dump_outputs, mode, info)
     tps = aggregate_tokens_per_sec(world, a.steps, t)
     mname = {"7B": "Llama-2-7B", "13B": "Llama-2-13B", "70B": "Llama-2-70B", "llama-3-8b": "Llama-3-8B"}.get(a.model, a.model)
     out = {"metric": f"decode tokens/sec (bs=1), {mname} {a.precision} @{a.sparsity:.0%} activation sparsity", "value": tps, "unit": "tokens/s",
@@ -668,10 +703,11 @@ def main():
         out["config"]["graph_tokens"] = info["graph_tokens"]  # decode steps per hipGraph replay (device-resident loop state)
     if rank == 0 and mode == "engine":
         eng = info["engine"]
-        # achieved kept fraction of all seven projections on the DECODE activations of one more step
-        out["kept_fraction"] = {k: round(v, 4) for k, v in
-                                eng.mean_kept_fractions(info["first_token"], info["pos0"], info["span"], 3).items()}
-        out["kept_fraction_note"] = "mean over layers and over 3 decode positions (first, middle, last) of the timed range"
+        if a.full:
+            # achieved kept fraction of all seven projections on the DECODE activations of one more step
+            out["kept_fraction"] = {k: round(v, 4) for k, v in
+                                    eng.mean_kept_fractions(info["first_token"], info["pos0"], info["span"], 3).items()}
+            out["kept_fraction_note"] = "mean over layers and over 3 decode positions (first, middle, last) of the timed range"
         # the reference's tokens/sec definition (gpt-fast/generate.py:487-497): generated tokens / (prefill + decode) for
         # one sample of max_new_tokens = 200 after a prompt of `prompt_tokens`
         t_pf = info.get("prefill_s")
@@ -682,7 +718,7 @@ def main():
             out["prefill_path"] = {"hip": "hand-fused HIP prompt pass (teal_amd/gpt_fast/prefill.py), hipGraph replay",
                                    "fallback": "module path"}.get(info.get("prefill_path"), info.get("prefill_path"))
     st_sparse = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and a.full:
         out["roofline"] = roofline_engine_gateup(info["engine"], a) if mode == "engine" else roofline_dominant_kernel(model, a)
         if mode == "engine" and not a.no_dense and info["engine"].att_fused_merge and not info["engine"].int4:
             st_sparse = info["engine"].stage_times()  # (int4: kept PAIRS + dense group parameters — another byte model)
@@ -739,13 +775,13 @@ def main():
         if not a.no_cpu_baseline and a.weights == "16bit":
             out["cpu_baseline"] = cpu_baseline(model, a)
     elif world > 1:
-        # N > 1: the timing's collectives are done — the ranks leave the group TOGETHER (barrier first), then rank 0 alone measures
-        # the dominant launch on its own GPU (a per-GPU property: replicas do not change it).  No dense leg, no CPU baseline (N = 1
+        # N > 1: the timing's collectives are done — the ranks leave the group TOGETHER (barrier first), then (--full) rank 0 alone
+        # measures the dominant launch on its own GPU (a per-GPU property: replicas do not change it).  No dense leg, no CPU baseline (N = 1
         # only, by the bench contract).
         import torch.distributed as dist
         barrier(world)
         dist.destroy_process_group()
-        if rank == 0:
+        if rank == 0 and a.full:
             out["roofline"] = roofline_engine_gateup(info["engine"], a) if mode == "engine" else roofline_dominant_kernel(model, a)
             out["roofline"]["note_n_gpus"] = f"measured on rank 0's GPU after the timed region (each of the {world} replicas runs the same launch)"
             out["cpu_baseline"] = None

@@ -7,7 +7,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=gpurun_out/ratio; mkdir -p $OUT
-COMMON="--no-cpu-baseline --no-context-sweep --no-live-traffic --no-reference-dense --steps ${STEPS:-100} --warmup 10"
+COMMON="--full --no-cpu-baseline --no-context-sweep --no-live-traffic --no-reference-dense --steps ${STEPS:-100} --warmup 10"
 run() {  # tag, args...
   local tag=$1; shift
   timeout ${RUN_TIMEOUT:-900} python bench.py $COMMON "$@" > $OUT/$tag.log 2>&1

@@ -37,9 +37,13 @@ def test_bench_cli_contract():
         sys.argv = ["bench.py"]
         a = bench.parse()
         assert a.gpus == 1 and a.steps > 0 and a.warmup >= 0 and a.model == "7B" and a.sparsity == 0.5
+        assert a.full is False and a.dump_outputs is None  # a plain run times the headline only and writes nothing
         sys.argv = ["bench.py", "--gpus", "8", "--steps", "50", "--warmup", "5"]
         a = bench.parse()
         assert (a.gpus, a.steps, a.warmup) == (8, 50, 5)
+        sys.argv += ["--full", "--dump-outputs", "out_dir"]
+        a = bench.parse()
+        assert a.full is True and a.dump_outputs == "out_dir"
     finally:
         sys.argv = old
 
@@ -117,3 +121,24 @@ def test_floor_model_without_a_slope_stays_valid_json():
     assert back["x"] is None and back["y"] == [1.0, None]
     same = bench.floor_model(s, dict(s, layer=50.0), 32)  # --sparsity 0: both engines keep every row
     json.dumps(bench._finite(same), allow_nan=False)
+
+
+def test_dump_outputs_writes_the_last_steps_arrays(tmp_path):
+    """bench.dump_outputs: the engine's logits as float32 and its sampled token as float64, bit for bit; the drop-in path's
+    token alone"""
+    import types
+
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    logits = torch.randn(1, 1, 320).to(torch.float16)
+    eng = types.SimpleNamespace(logits=logits, tok_buf=torch.tensor([[317]], dtype=torch.int32))
+    bench.dump_outputs(str(tmp_path / "engine"), "engine", {"engine": eng})
+    lg, tok = np.load(tmp_path / "engine" / "logits.npy"), np.load(tmp_path / "engine" / "token.npy")
+    assert lg.dtype == np.float32 and lg.shape == (320,) and np.array_equal(lg, logits.float().reshape(-1).numpy())
+    assert tok.dtype == np.float64 and tok.tolist() == [317.0]
+    dec = types.SimpleNamespace(out_tok=torch.tensor([42], dtype=torch.int32))
+    bench.dump_outputs(str(tmp_path / "dropin"), "dropin", {"decoder": dec})
+    assert sorted(os.listdir(tmp_path / "dropin")) == ["token.npy"]
+    assert np.load(tmp_path / "dropin" / "token.npy").tolist() == [42.0]

@@ -368,7 +368,7 @@ def test_bench_replicas_under_torch_distributed_run():
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3", "--n_layer", "2",
-           "--no-cpu-baseline", "--no-context-sweep"]
+           "--full", "--no-cpu-baseline", "--no-context-sweep"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -380,3 +380,33 @@ def test_bench_replicas_under_torch_distributed_run():
     # baseline is an N = 1 item
     assert d["cpu_baseline"] is None and "replicas x2" in d["config"]["parallelism"]
     assert d["roofline"]["bound"] == "hbm" and 0.05 < d["roofline"]["frac"] < 1.0 and d["roofline"]["peak"] == 8000.0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_headline_and_dumps_reproducible_outputs(tmp_path):
+    """a plain `bench.py` run prints the headline keys and none of --full's legs; --dump-outputs writes the last timed step's
+    logits and token, and a second run with the same arguments writes the same bits"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--n_layer", "2",
+               "--dump-outputs", str(d)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        r = json.loads(lines[0])
+        assert r["unit"] == "tokens/s" and r["higher_is_better"] is True and r["dtype"] == "f16" and r["steps"] == 7
+        assert abs(r["value"] - 1e3 / r["ms_per_step"]) < 1e-6 * r["value"]
+        assert not {"roofline", "cpu_baseline", "kept_fraction", "dense_tokens_per_sec", "value_at_context"} & set(r), sorted(r)
+        dumps.append({n: np.load(d / n) for n in sorted(os.listdir(d))})
+    a, b = dumps
+    assert sorted(a) == ["logits.npy", "token.npy"]
+    assert a["logits.npy"].dtype == np.float32 and a["logits.npy"].shape == (32000,) and np.isfinite(a["logits.npy"]).all()
+    assert a["token.npy"].dtype == np.float64 and a["token.npy"].shape == (1,) and 0 <= a["token.npy"][0] < 32000
+    for n in a:
+        assert np.array_equal(a[n], b[n]), n

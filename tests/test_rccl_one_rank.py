@@ -46,7 +46,7 @@ def test_engine_graph_holds_the_rccl_allreduce_and_stays_bit_identical(arch, pre
 def test_bench_distributed_branch_with_one_rccl_rank():
     """bench.py's world > 1 branch — init_process_group("nccl", device_id=...), barrier, the float64 MAX all-reduce on the device —
     taken by one rank (TEAL_BENCH_FORCE_DIST=nccl): same keys as the plain line, n_gpus 1, value within 2 %."""
-    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "100", "--warmup", "10", "--n_layer", "8", "--no-dense",
+    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "100", "--warmup", "10", "--n_layer", "8", "--full", "--no-dense",
             "--no-cpu-baseline", "--no-context-sweep", "--no-live-traffic"]
     lines = {}
     for tag, env in (("plain", _env()), ("nccl", _env(TEAL_BENCH_FORCE_DIST="nccl"))):
