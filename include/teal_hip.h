@@ -377,6 +377,46 @@ int teal_prefill_resid_norm(const void* emb, const int32_t* tokens, int T, const
 int teal_prefill_attention(const float* qkv_slabs, int split, const void* rope, void* k_cache, void* v_cache, void* yt, int T, int n_head,
                            int n_kv_head, int head_dim, int max_seq, int dtype, void* stream);
 
+/* ---- speculative decoding: the dense verify pass and the accept step, teal_amd/csrc/teal_speculative.hip ---------- */
+
+/* A round (gpt-fast/generate.py:98-217): k draft tokens d1 .. dk from the sparse decode step, then ONE dense prompt-pass-shaped
+ * pass over the T = k + 1 tokens [x0, d1 .. dk] at positions p0 .. p0+k (teal_prefill_gemm / teal_prefill_resid_norm with this
+ * attention), the lm_head of every row (teal_prefill_gemm over the column-major lm_head image), then teal_spec_accept. */
+
+/* Bytes of `partials` teal_verify_attention may need (any cache length). */
+size_t teal_verify_attention_ws_bytes(int T, int n_head, int head_dim);
+/* q | k | v of T <= 16 tokens from the slabs [split][(n_head + 2 n_kv_head) * head_dim][R] of a teal_prefill_gemm launch: RoPE(q, k) at
+ * positions p0 + t, cache rows p0 .. p0+T-1 written, query t attends causally to rows 0 .. p0+t -> yt [n_head * head_dim][R] (slots
+ * >= T zero), the input of the wo GEMM.  p0 = *pos is read on the DEVICE (a captured round replays at any position), clamped to
+ * [0, max_seq - T].  Split-KV over the context (every K / V row a workgroup loads serves all T x (n_head / n_kv_head) query rows
+ * of its KV head) and a merge launch; the T new rows are rebuilt from the slabs by every workgroup that needs them — no row written
+ * by the launch is read back by it.  head_dim 64 or 128, max_seq >= T.  Two launches. */
+int teal_verify_attention(const float* qkv_slabs, int split, const void* rope, const int32_t* pos, void* k_cache, void* v_cache, void* yt,
+                          float* partials, size_t partials_bytes, int T, int n_head, int n_kv_head, int head_dim, int max_seq, int dtype,
+                          void* stream);
+
+/* Bytes of `scratch` teal_spec_accept needs (the rounded target rows and per-row statistics). */
+size_t teal_spec_accept_scratch_bytes(int vocab, int k);
+/* The accept / reject step of one round, on the device (gpt-fast/generate.py:123-146).
+ *   logit_slabs   [split][vocab][R] lm_head slabs of the T = k + 1 verified rows (teal_prefill_gemm, R = 8 for T <= 8 else 16): row t
+ *                 is summed in slice order and rounded ONCE to 16 bits (the module path's logits) -> q_t
+ *   draft_logits  [k][vocab] 16-bit: the draft's logits row that drew d_{i+1} -> p_i
+ *   tokens        int32 [T]: tokens[0] = the round's input token x0, tokens[1 .. k] = d1 .. dk; tokens[0] <- the next round's input
+ * Distributions: prob(v) = exp((x_v - max x) / temperature) / Z over the top_k largest logits (ties at the pivot kept; top_k <= 0 or
+ * >= vocab: all) — the fused sampler's weights (teal_sample_topk), normalised.  With (seed, c) = rng_state[0], rng_state[1] at entry and
+ * U(h) = ((h >> 8) + 0.5) / 2^24, hash3 as in the sampler:
+ *   u_i      = U(hash3(seed, c, i)),  i < k
+ *   accept d_{i+1} while p_i(d_{i+1}) > 0 and u_i <= min(1, q_i(d_{i+1}) / p_i(d_{i+1}))   (fp32); n = accepted count
+ *   key_v    = U(hash3(seed, c + 1, v)),  v < vocab
+ *   token    = argmax_v w_v / -log(key_v) (ties: lowest v), w = max(q_n - p_n, 0) if n < k (q_n if that is zero everywhere), else q_k
+ *   rng_state[1] = c + 2.
+ * Outputs: out_seq[*out_len ..] <- d1 .. dn, token (entries past out_cap dropped), *out_len += n + 1; *spec_pos += n + 1 and, if
+ * given, *pos_out = the same (the draft engine's position); *n_acc = n and hist[n] += 1 if given.  vocab 8 .. 131072, a multiple of
+ * 8; 1 <= k <= 15.  Three launches: round the target rows, per-row statistics (2k + 1 workgroups), the decision (one workgroup). */
+int teal_spec_accept(const float* logit_slabs, int split, const void* draft_logits, int vocab, int k, int dtype, int top_k, float temperature,
+                     void* rng_state, int32_t* tokens, int32_t* spec_pos, int32_t* pos_out, int32_t* out_seq, int out_cap, int32_t* out_len,
+                     int32_t* n_acc, int32_t* hist, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- benchmark comparator (scripts/benchmark_gemv.py only; not on the decode path) ----------- */
 
 /* The Deja Vu gather GEMV the reference's kernel benchmark plots next to TEAL's (scripts/benchmark_gemv.py:32-107,170-172),

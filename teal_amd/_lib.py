@@ -21,7 +21,8 @@ CSRC = os.path.join(_PKG, "csrc")
 # (weight width, activation dtype) so that they compile in parallel
 SOURCES = ("teal_kernels.hip", "teal_attention.hip", "teal_gemv_w16_f16.hip", "teal_gemv_w16_bf16.hip",
            "teal_gemv_w8_f16.hip", "teal_gemv_w8_bf16.hip", "teal_gemv_fast_f16.hip", "teal_gemv_fast_bf16.hip", "teal_gemv_int4.hip",
-           "teal_gemv_fast_w8_f16.hip", "teal_gemv_fast_w8_bf16.hip", "teal_comparators.hip", "teal_prefill.hip")
+           "teal_gemv_fast_w8_f16.hip", "teal_gemv_fast_w8_bf16.hip", "teal_comparators.hip", "teal_prefill.hip",
+           "teal_speculative.hip")
 # translation units whose kernels take their hot arguments as scalar parameters: the command processor preloads the
 # first 11 dwords into SGPRs at wave launch (no scalar-cache miss before the first activation load)
 PRELOAD = {"teal_gemv_fast_f16.hip": 12, "teal_gemv_fast_bf16.hip": 12, "teal_gemv_fast_w8_f16.hip": 12,
@@ -55,7 +56,8 @@ DIAG_LIB_PATH = os.path.join(_PKG, "libteal_hip_diag.so")
 # writes there (an override pointing at an older build must not be overwritten by the current tree), and symbols that build
 # lacks are tolerated (OPTIONAL_WITH_OVERRIDE).
 LIB_OVERRIDE = os.environ.get("TEAL_LIB_PATH") or None
-OPTIONAL_WITH_OVERRIDE = ("teal_decode_attention_split_roped", "teal_prefill_gemm", "teal_prefill_resid_norm", "teal_prefill_attention")
+OPTIONAL_WITH_OVERRIDE = ("teal_decode_attention_split_roped", "teal_prefill_gemm", "teal_prefill_resid_norm", "teal_prefill_attention",
+                          "teal_verify_attention_ws_bytes", "teal_verify_attention", "teal_spec_accept_scratch_bytes", "teal_spec_accept")
 
 # every symbol include/teal_hip.h declares
 EXPORTS = (
@@ -65,6 +67,7 @@ EXPORTS = (
     "teal_workspace_init", "teal_workspace_release", "teal_sample_topk_ws", "teal_decode_attention_split_ws", "teal_cmp_flag_gemv",
     "teal_decode_attention_split_roped",
     "teal_prefill_gemm", "teal_prefill_resid_norm", "teal_prefill_attention",
+    "teal_verify_attention_ws_bytes", "teal_verify_attention", "teal_spec_accept_scratch_bytes", "teal_spec_accept",
 )
 
 # what libteal_hip_diag.so exports on top (include/teal_hip.h, #ifdef TEAL_DIAGNOSTICS); libteal_hip.so must export NONE of them
@@ -191,6 +194,13 @@ def _open(path: str, diag: bool) -> ctypes.CDLL:
         L.teal_prefill_gemm.argtypes = [vp, vp, ci, ci, vp, ci, ci, vp, sz, ci, ci, ci, ctypes.POINTER(ci), vp]  # (teal_prefill_in_t*, ...)
         L.teal_prefill_resid_norm.argtypes = [vp, vp, ci, vp, vp, ci, vp, cf, ci, vp, vp, vp, vp, ci, vp]
         L.teal_prefill_attention.argtypes = [vp, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
+    if hasattr(L, "teal_spec_accept"):
+        L.teal_verify_attention_ws_bytes.argtypes = [ci, ci, ci]
+        L.teal_verify_attention_ws_bytes.restype = sz
+        L.teal_verify_attention.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, ci, ci, ci, vp]
+        L.teal_spec_accept_scratch_bytes.argtypes = [ci, ci]
+        L.teal_spec_accept_scratch_bytes.restype = sz
+        L.teal_spec_accept.argtypes = [vp, ci, vp, ci, ci, ci, ci, cf, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, sz, vp]
     for name in EXPORTS + (DIAG_EXPORTS if diag else ()):
         if LIB_OVERRIDE and name in OPTIONAL_WITH_OVERRIDE and not hasattr(L, name):
             continue  # an older build loaded for A/B: callers of this entry point fail with AttributeError when they reach it

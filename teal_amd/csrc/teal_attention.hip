@@ -862,43 +862,7 @@ __global__ __launch_bounds__(128) void decode_attention_merge_kernel(const float
 // index); the draw counter lives on the device and is bumped by the kernel, so hipGraph replays
 // draw fresh numbers.  Token streams are not pinned by the reference (they depend on torch's RNG).
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t order_key16(uint32_t b, bool bf16) {
-    (void)bf16;  // fp16 and bf16 share sign-magnitude ordering
-    return (b & 0x8000u) ? (~b & 0xFFFFu) : (b | 0x8000u);
-}
-
-__device__ __forceinline__ uint32_t hash3(uint32_t a, uint32_t b, uint32_t c) {
-    uint32_t h = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u) * 0x85EBCA77u ^ (c + 0x165667B1u) * 0xC2B2AE3Du;
-    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-    return h;
-}
-
-// sel[0] = the bin b in which the `need`-th largest key falls, sel[1] = its rank inside that bin.  One wave does
-// it without workgroup barriers (lane l owns bins 4l..4l+3, suffix sums over lanes by shuffles): the Hillis-Steele
-// scan over 1024 threads it replaces cost 18 barriers per call, and barriers were most of this kernel's time.
-// All threads must call this; hist[] must be complete (barrier before), sel[] is valid after the trailing barrier.
-__device__ __forceinline__ void select_bin(const unsigned int* hist, unsigned int* suf, unsigned int* sel,
-                                           const unsigned int need, const int tid) {
-    (void)suf;
-    if (tid < 64) {
-        const unsigned int h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
-        const unsigned int own = h0 + h1 + h2 + h3;
-        unsigned int incl = own;  // keys in this lane's bins and all higher lanes'
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned int t = (unsigned int)__shfl_down((int)incl, d);
-            if (tid + d < 64) incl += t;
-        }
-        // keys in strictly higher bins, for each of the four bins (highest first)
-        const unsigned int a3 = incl - own, a2 = a3 + h3, a1 = a2 + h2, a0 = a1 + h1;
-        if (a3 + h3 >= need && a3 < need) { sel[0] = 4u * tid + 3u; sel[1] = need - a3; }
-        if (a2 + h2 >= need && a2 < need) { sel[0] = 4u * tid + 2u; sel[1] = need - a2; }
-        if (a1 + h1 >= need && a1 < need) { sel[0] = 4u * tid + 1u; sel[1] = need - a1; }
-        if (a0 + h0 >= need && a0 < need) { sel[0] = 4u * tid; sel[1] = need - a0; }
-        if (tid == 0 && incl < need) { sel[0] = 0u; sel[1] = need; }  // fewer keys than requested: keep all
-    }
-    __syncthreads();
-}
+// (order_key16, hash3 and select_bin live in teal_common.h: the speculative accept kernel draws from the same stream)
 
 template <bool BF16>
 __device__ __forceinline__ void sample_full(const uint16_t* __restrict__ logits, const int V, const int top_k,

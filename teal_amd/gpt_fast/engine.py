@@ -371,11 +371,13 @@ class DecodeEngine:
         if rc != 0:
             _lib.check(rc, "teal_fused_gemv")
 
-    def __call__(self, idx: torch.Tensor, input_pos: torch.Tensor, hook=None) -> torch.Tensor:
+    def __call__(self, idx: torch.Tensor, input_pos: torch.Tensor, hook=None, logits_out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """idx: int32 [1, 1] token id, input_pos: int32 [1] position -> logits [1, 1, vocab].
 
         `hook(when, stage, layer)` (tests / measurements only; never under graph capture) is called around every launch:
-        when in {"before", "after"}, stage in {"qkv", "attn", "wo", "gate_up", "down", "head"}."""
+        when in {"before", "after"}, stage in {"qkv", "attn", "wo", "gate_up", "down", "head"}.
+        `logits_out`: a contiguous [vocab] destination of this step's logits instead of `self.logits` (speculative decoding
+        records every draft step's row)."""
         assert idx.dtype == torch.int32 and input_pos.dtype == torch.int32 and idx.numel() == 1
         self._stream = runtime.stream_ptr()
         tok_ptr, pos_ptr = idx.data_ptr(), input_pos.data_ptr()
@@ -384,10 +386,16 @@ class DecodeEngine:
         self.head_in.nslabs = self.n_down.value
         if hook:
             hook("before", "head", -1)
-        self._gemv(self.head_in, self.head_out, self.dim)
+        if logits_out is not None:
+            assert logits_out.is_contiguous() and logits_out.numel() == self.cfg.vocab_size and logits_out.dtype == self.logits.dtype
+            self.head_out.y[0] = logits_out.data_ptr()
+        try:
+            self._gemv(self.head_in, self.head_out, self.dim)
+        finally:
+            self.head_out.y[0] = self.logits.data_ptr()
         if hook:
             hook("after", "head", -1)
-        return self.logits
+        return self.logits if logits_out is None else logits_out
 
     @staticmethod
     def _gqa_lds_bytes(rep: int, hd: int, max_seq: int, nsplit: int) -> int:

@@ -472,12 +472,161 @@ def generate(model: Transformer, prompt: torch.Tensor, max_new_tokens: int, deco
 
 
 # ------------------------------------------------------------------------------------------------
+# speculative decoding (gpt-fast/generate.py:98-217, 392-398, 500-524): a TEAL-sparse draft, the dense model verifies
+# ------------------------------------------------------------------------------------------------
+def check_speculative_args(args) -> Optional[str]:
+    """None (no speculation), "self" (the target's own weights draft, with TEAL thresholds) or "draft" (a separate checkpoint).
+    Every refusal is raised here, before anything is loaded."""
+    draft = getattr(args, "draft_checkpoint_path", None)
+    self_spec = bool(getattr(args, "self_speculate", False))
+    if draft is None and not self_spec:
+        return None
+    from teal_amd.gpt_fast.speculative import MAX_K
+    k = int(getattr(args, "speculate_k", 5))
+    if not 1 <= k <= MAX_K:
+        raise SystemExit(f"speculative decoding: --speculate_k must be in 1..{MAX_K} (k + 1 tokens per verify pass), got {k}")
+    if int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1"))) > 1:
+        raise SystemExit("speculative decoding does not run under tensor parallelism")
+    if args.precision not in ("fp16", "bf16"):
+        raise SystemExit(f"speculative decoding needs a 16-bit target, got --precision {args.precision}")
+    if self_spec and draft is not None:
+        raise SystemExit("speculative decoding: give --self_speculate or --draft_checkpoint_path, not both")
+    if self_spec:
+        if not args.synthetic:
+            raise SystemExit("speculative decoding: --self_speculate is for --synthetic runs; with a checkpoint, pass it as "
+                             "--draft_checkpoint_path too")
+        return "self"
+    if args.synthetic:
+        raise SystemExit("speculative decoding: --synthetic runs self-speculate (--self_speculate); a draft checkpoint needs a target checkpoint")
+    target = Path(args.checkpoint_path)
+    if "int8" in str(target) or "int4" in str(target):  # (the loader's own test: load_checkpoint_model)
+        raise SystemExit(f"speculative decoding verifies with a dense 16-bit target; {target} is quantised")
+    draft = Path(draft)
+    if not draft.is_file():
+        raise SystemExit(f"speculative decoding: draft checkpoint {draft} not found")
+    if draft.resolve() == target.resolve():
+        return "self"
+    try:
+        vt, vd = ModelArgs.from_name(target.parent.name).vocab_size, ModelArgs.from_name(draft.parent.name).vocab_size
+    except KeyError as e:
+        raise SystemExit(f"speculative decoding: cannot tell the vocabulary of a checkpoint ({e})")
+    if vt != vd:
+        raise SystemExit(f"speculative decoding: the draft's vocabulary ({vd}) differs from the target's ({vt})")
+    return "draft"
+
+
+@torch.no_grad()
+def speculative_generate(spec, prompt: torch.Tensor, max_new_tokens: int, prefill, draft_prefill=None,
+                         temperature: float = 0.8, top_k: Optional[int] = 200):
+    """prompt pass (target; the draft's too for a separate draft), the first token from the target's prompt logits, then rounds
+    until max_new_tokens tokens are out (the last round's overshoot is trimmed).  Returns (sequence, accepted-count histogram)."""
+    T = prompt.size(0)
+    seq = torch.empty(T + max_new_tokens, dtype=prompt.dtype, device=prompt.device)
+    seq[:T] = prompt
+    logits = prefill(prompt)
+    if draft_prefill is not None:
+        draft_prefill(prompt)
+    eng = spec.draft
+    first = eng.sample_first(logits[0, -1].contiguous(), temperature, top_k)
+    seq[T] = first.view(())
+    if max_new_tokens > 1:
+        seq[T + 1:] = spec.decode(first, T, max_new_tokens - 1).to(seq.dtype)
+    return seq, spec.histogram()
+
+
+def load_draft_model(path: Path, device: str, dtype: torch.dtype, sparsity: float, hist_path: Optional[str],
+                     greedy_lookup: Optional[str]):
+    """(draft model, its TEAL thresholds) from a checkpoint (16-bit, int8 or int4, as load_checkpoint_model reads it).  Sparsity 0
+    without histograms: thresholds of -1 (every activation kept, a dense draft — calibrate_thresholds' convention)."""
+    draft = load_checkpoint_model(Path(path), device, dtype)
+    if hist_path is None and sparsity <= 0:
+        return draft, [{p: -1.0 for p in PROJS} for _ in draft.layers]
+    return draft, apply_sparsity(draft, sparsity=sparsity, hist_path=hist_path, greedy_lookup=greedy_lookup, synthetic=hist_path is None)
+
+
+def build_speculator(model: Transformer, thresholds, k: int, temperature: float, top_k: Optional[int], capacity: int, max_seq: int,
+                     use_graph: bool, draft=None):
+    """(SpeculativeDecoder, draft prompt pass or None) for a target whose caches are set up (max_seq rows).  draft: None
+    (self-speculation: the target's own weights with `thresholds` draft) or (draft model, its thresholds): a separate draft with
+    its own caches, prompt pass and fill-in step."""
+    from teal_amd.gpt_fast.engine import pick_engine
+    from teal_amd.gpt_fast.prefill import FusedPrefill
+    from teal_amd.gpt_fast.speculative import SpeculativeDecoder, VerifyPass
+    why = VerifyPass.supports(model)
+    if why is not None:
+        raise SystemExit(f"speculative decoding cannot verify with this target: {why}")
+    verify = VerifyPass(model)
+    if draft is None:
+        draft_model, draft_prefill = model, None
+    else:
+        draft_model, thresholds = draft
+        if draft_model.config.vocab_size != model.config.vocab_size:
+            raise SystemExit("speculative decoding: the draft's vocabulary differs from the target's")
+        draft_model.setup_caches(max_batch_size=1, max_seq_length=max_seq)
+        relayout_for_engine(draft_model)
+        draft_prefill = FusedPrefill(draft_model, graph=use_graph)
+    cls, why = pick_engine(draft_model)
+    if cls is None:
+        raise SystemExit(f"speculative decoding: no fused engine for the draft: {why}")
+    eng = cls(draft_model, thresholds)
+    spec = SpeculativeDecoder(eng, verify, k, temperature, top_k, fill_in=draft is not None, capacity=capacity, graph=use_graph)
+    return spec, draft_prefill
+
+
+def run_speculative(args, model: Transformer, thresholds, prompt: torch.Tensor, tokenizer, mode: str, device: str,
+                    dtype: torch.dtype) -> Dict:
+    """main()'s loop for speculative decoding: caches sized T_new + k + 1 (gpt-fast/generate.py:174), tokens/sec as the reference
+    counts it (new tokens over the whole generate() call), and its acceptance printout (:500-524)."""
+    from teal_amd.gpt_fast.prefill import FusedPrefill
+    from teal_amd.gpt_fast.speculative import SpeculativeDecoder
+    if mode == "self" and thresholds is None:
+        raise SystemExit("speculative decoding needs TEAL thresholds for the draft (--hist_path, or --synthetic)")
+    use_graph = bool(args.compile)
+    T = prompt.numel()
+    max_seq = min(T + args.max_new_tokens + args.speculate_k + 1, model.config.block_size)
+    model.setup_caches(max_batch_size=1, max_seq_length=max_seq)
+    relayout_for_engine(model)
+    prefill = FusedPrefill(model, graph=use_graph)
+    draft = None
+    if mode == "draft":
+        draft = load_draft_model(Path(args.draft_checkpoint_path), device, dtype, args.sparsity, args.hist_path, args.greedy_lookup)
+    spec, draft_prefill = build_speculator(model, thresholds, args.speculate_k, args.temperature, args.top_k,
+                                           args.max_new_tokens + args.speculate_k + 1, max_seq, use_graph, draft)
+    model_size = _get_model_size(model)
+    tps, seqs, hist = [], [], [0] * (args.speculate_k + 1)
+    for i in range(-1 if args.compile else 0, args.num_samples):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        y, h = speculative_generate(spec, prompt, args.max_new_tokens, prefill, draft_prefill, args.temperature, args.top_k)
+        torch.cuda.synchronize()
+        t = time.perf_counter() - t0
+        if i == -1:
+            print(f"Graph capture + warm-up time: {t:.2f} seconds")
+            continue
+        hist = [a + b for a, b in zip(hist, h)]
+        tps.append((y.size(0) - T) / t)
+        seqs.append(y.tolist())
+        if tokenizer is not None:
+            print(tokenizer.decode(y.tolist()))
+        print(f"Time for inference {i + 1}: {t:.02f} sec total, {tps[-1]:.02f} tokens/sec")
+        print(f"Bandwidth achieved: {model_size * tps[-1] / 1e9:.02f} GB/s (dense parameter bytes x tok/s, as the reference reports)")
+    print("==========")
+    st = SpeculativeDecoder.acceptance_stats(hist)
+    print(f"Acceptance probs: {st['acceptance_probs']}")
+    print(f"Mean Accepted: {st['mean_accepted']}")
+    mean = sum(tps) / max(1, len(tps))
+    print(f"Average tokens/sec: {mean:.2f}")
+    print(f"Memory used: {torch.cuda.max_memory_reserved() / 1e9:.02f} GB")
+    return {"tokens_per_sec": tps, "mean_tokens_per_sec": mean, "thresholds": thresholds, "decoder": "SpeculativeDecoder",
+            "sequences": seqs, "prefill": "FusedPrefill", "speculative": mode, "acceptance_histogram": hist,
+            "acceptance_probs": st["acceptance_probs"], "mean_accepted": st["mean_accepted"]}
+
+
+# ------------------------------------------------------------------------------------------------
 def main(args) -> Dict:
     device = args.device
     assert "cuda" in device, "the sparse decode path is GPU-only (HIP kernels, no CPU fallback)"
-    if getattr(args, "draft_checkpoint_path", None) is not None:
-        raise SystemExit("--draft_checkpoint_path: speculative decoding is not part of this build (the reference lists it as "
-                         "untested with TEAL); run without a draft model")
+    spec = check_speculative_args(args)  # before anything is loaded
     if getattr(args, "interactive", False) and args.synthetic:
         raise SystemExit("--interactive needs a tokenizer (a checkpoint directory), not --synthetic")
     dtype = {"fp16": torch.float16, "bf16": torch.bfloat16}[args.precision]
@@ -518,6 +667,8 @@ def main(args) -> Dict:
     torch.cuda.synchronize()
     print(f"Time to load model: {time.time() - t0:.02f} seconds")
     torch.manual_seed(1234)
+    if spec is not None:
+        return run_speculative(args, model, thresholds, prompt, tokenizer, spec, device, dtype)
     model_size = _get_model_size(model)
     # a hipGraph holds the step only if the ranks' all-reduce can be captured (RCCL); a host-staged gloo reduce decodes eagerly
     # (TEAL_TP_GRAPH=0 keeps a sharded model's decode eager even over RCCL; a capture that fails falls back by itself)
@@ -610,9 +761,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--module_prefill", action="store_true", help="with --compile: the prompt pass through the patched modules (under a "
                    "hipGraph) also for prompts of up to 8 tokens, instead of the hand-fused HIP prompt pass")
     p.add_argument("--profile", type=Path, default=None)
-    p.add_argument("--speculate_k", type=int, default=5, help="accepted for command-line compatibility; only read with a draft model")
-    p.add_argument("--draft_checkpoint_path", type=Path, default=None, help="speculative decoding is outside this build (the "
-                   "reference marks it untested with TEAL: README.md:111, generate.py:393): giving a draft model is an error")
+    p.add_argument("--speculate_k", type=int, default=5, help="speculative decoding: draft tokens per round (1..15)")
+    p.add_argument("--draft_checkpoint_path", type=Path, default=None, help="speculative decoding: the TEAL-sparse draft model (the "
+                   "target verifies dense); the target's own checkpoint path selects self-speculation")
+    p.add_argument("--self_speculate", action="store_true", help="speculative decoding with the target's own weights as the TEAL-sparse "
+                   "draft (--synthetic runs, which have no checkpoint path)")
     p.add_argument("--device", type=str, default=default_device)
     # monkeypatch (reference flags)
     p.add_argument("--hist_path", type=str, default=None)
