@@ -417,6 +417,40 @@ int teal_spec_accept(const float* logit_slabs, int split, const void* draft_logi
                      void* rng_state, int32_t* tokens, int32_t* spec_pos, int32_t* pos_out, int32_t* out_seq, int out_cap, int32_t* out_len,
                      int32_t* n_acc, int32_t* hist, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- batched decode: up to 8 TEAL-sparse sequences per step, teal_amd/csrc/teal_batched.hip -------------------------- */
+
+/* A step of B <= 8 sequences runs the prompt pass's chain (teal_prefill_resid_norm with T = B, the hand-over [feature][8]: slot b =
+ * sequence b) with these GEMM and attention launches.  TEAL's rule per sequence: y_b = W (x_b * [float32(|x_b|) > float32(tau)]),
+ * the mask taken on the 16-bit activation the module path holds. */
+
+/* Threshold segments of one GEMM launch: column ranges [col_end[s - 1], col_end[s]) over the launch's n0 + n1 output columns
+ * (col_end[-1] = 0, ascending, multiples of 8, col_end[nseg - 1] = n0 + n1), one tau each (q / k / v of wqkv; gate / up). */
+typedef struct teal_batched_segs {
+    int nseg;
+    int col_end[3];
+    float tau[3];
+} teal_batched_segs_t;
+
+/* slabs[slice][n][8] (fp32) = sum over the slice's rows m that sequence b keeps under its column's segment threshold of
+ * W^T[m][n] * x_b[m], b < B <= 8 (slots >= B zero); inputs, weights and the slab contract as teal_prefill_gemm (Z, n0, n1 multiples
+ * of 256).  Every weight row that some sequence keeps (the union) is read once; no other row is loaded.  counts (optional, int32
+ * [16][3][9]): slice k's row counts under segment s — counts[k][s][b] rows kept by sequence b, counts[k][s][8] rows of the union —
+ * written for slices k < *split_out (sum them over k; entries of absent segments are not written). */
+int teal_batched_sparse_gemm(const teal_prefill_in_t* in, const teal_batched_segs_t* segs, const void* w0T, int ld0, int n0, const void* w1T,
+                             int ld1, int n1, float* slabs, size_t slabs_bytes, int Z, int B, int32_t* counts, int dtype, int* split_out,
+                             void* stream);
+/* y[b][n] (16-bit, row stride N) = the `split` slabs [slice][N][8] of column n summed in slice order and rounded once, b < B. */
+int teal_batched_round_rows(const float* slabs, int split, int N, int B, void* y, int dtype, void* stream);
+/* Bytes of `partials` teal_batched_decode_attention may need (any cache length). */
+size_t teal_batched_decode_attention_ws_bytes(int B, int n_head, int head_dim);
+/* One decode token per sequence: q | k | v of sequence b from slot b of the wqkv slabs [split][(n_head + 2 n_kv_head) * head_dim][8],
+ * RoPE at p_b = clamp(pos[b], 0, max_seq - 1) (pos: int32 [B] on the DEVICE, positions may differ), the K / V row p_b written to
+ * sequence b's cache, attention over its rows 0 .. p_b -> yt [n_head * head_dim][8] (slots >= B zero).  Caches [B][n_kv_head][max_seq]
+ * [head_dim] (setup_caches(max_batch_size=B)).  head_dim 64 or 128, GQA or MHA, B <= 8.  Two launches (split-KV, merge). */
+int teal_batched_decode_attention(const float* qkv_slabs, int split, const void* rope, const int32_t* pos, void* k_cache, void* v_cache,
+                                  void* yt, float* partials, size_t partials_bytes, int B, int n_head, int n_kv_head, int head_dim,
+                                  int max_seq, int dtype, void* stream);
+
 /* ---- benchmark comparator (scripts/benchmark_gemv.py only; not on the decode path) ----------- */
 
 /* The Deja Vu gather GEMV the reference's kernel benchmark plots next to TEAL's (scripts/benchmark_gemv.py:32-107,170-172),

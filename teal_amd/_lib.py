@@ -22,7 +22,7 @@ CSRC = os.path.join(_PKG, "csrc")
 SOURCES = ("teal_kernels.hip", "teal_attention.hip", "teal_gemv_w16_f16.hip", "teal_gemv_w16_bf16.hip",
            "teal_gemv_w8_f16.hip", "teal_gemv_w8_bf16.hip", "teal_gemv_fast_f16.hip", "teal_gemv_fast_bf16.hip", "teal_gemv_int4.hip",
            "teal_gemv_fast_w8_f16.hip", "teal_gemv_fast_w8_bf16.hip", "teal_comparators.hip", "teal_prefill.hip",
-           "teal_speculative.hip")
+           "teal_speculative.hip", "teal_batched.hip")
 # translation units whose kernels take their hot arguments as scalar parameters: the command processor preloads the
 # first 11 dwords into SGPRs at wave launch (no scalar-cache miss before the first activation load)
 PRELOAD = {"teal_gemv_fast_f16.hip": 12, "teal_gemv_fast_bf16.hip": 12, "teal_gemv_fast_w8_f16.hip": 12,
@@ -57,7 +57,9 @@ DIAG_LIB_PATH = os.path.join(_PKG, "libteal_hip_diag.so")
 # lacks are tolerated (OPTIONAL_WITH_OVERRIDE).
 LIB_OVERRIDE = os.environ.get("TEAL_LIB_PATH") or None
 OPTIONAL_WITH_OVERRIDE = ("teal_decode_attention_split_roped", "teal_prefill_gemm", "teal_prefill_resid_norm", "teal_prefill_attention",
-                          "teal_verify_attention_ws_bytes", "teal_verify_attention", "teal_spec_accept_scratch_bytes", "teal_spec_accept")
+                          "teal_verify_attention_ws_bytes", "teal_verify_attention", "teal_spec_accept_scratch_bytes", "teal_spec_accept",
+                          "teal_batched_sparse_gemm", "teal_batched_round_rows", "teal_batched_decode_attention_ws_bytes",
+                          "teal_batched_decode_attention")
 
 # every symbol include/teal_hip.h declares
 EXPORTS = (
@@ -68,6 +70,7 @@ EXPORTS = (
     "teal_decode_attention_split_roped",
     "teal_prefill_gemm", "teal_prefill_resid_norm", "teal_prefill_attention",
     "teal_verify_attention_ws_bytes", "teal_verify_attention", "teal_spec_accept_scratch_bytes", "teal_spec_accept",
+    "teal_batched_sparse_gemm", "teal_batched_round_rows", "teal_batched_decode_attention_ws_bytes", "teal_batched_decode_attention",
 )
 
 # what libteal_hip_diag.so exports on top (include/teal_hip.h, #ifdef TEAL_DIAGNOSTICS); libteal_hip.so must export NONE of them
@@ -201,6 +204,12 @@ def _open(path: str, diag: bool) -> ctypes.CDLL:
         L.teal_spec_accept_scratch_bytes.argtypes = [ci, ci]
         L.teal_spec_accept_scratch_bytes.restype = sz
         L.teal_spec_accept.argtypes = [vp, ci, vp, ci, ci, ci, ci, cf, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, sz, vp]
+    if hasattr(L, "teal_batched_sparse_gemm"):
+        L.teal_batched_sparse_gemm.argtypes = [vp, vp, vp, ci, ci, vp, ci, ci, vp, sz, ci, ci, vp, ci, ctypes.POINTER(ci), vp]
+        L.teal_batched_round_rows.argtypes = [vp, ci, ci, ci, vp, ci, vp]
+        L.teal_batched_decode_attention_ws_bytes.argtypes = [ci, ci, ci]
+        L.teal_batched_decode_attention_ws_bytes.restype = sz
+        L.teal_batched_decode_attention.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, ci, ci, ci, vp]
     for name in EXPORTS + (DIAG_EXPORTS if diag else ()):
         if LIB_OVERRIDE and name in OPTIONAL_WITH_OVERRIDE and not hasattr(L, name):
             continue  # an older build loaded for A/B: callers of this entry point fail with AttributeError when they reach it

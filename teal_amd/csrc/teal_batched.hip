@@ -1,0 +1,650 @@
+// teal_batched.hip — batched decode: up to 8 sequences per fused step, hand-fused for gfx950 / CDNA4, wave64.
+//
+// TEAL's rule is per token: sequence b's projection is W . (x_b (.) [|x_b| > tau]) (the reference's SparsifyFn masks every
+// token's activations element-wise against the site's threshold).  One step of B sequences therefore needs every weight row
+// that ANY of them keeps — the union — read once, and each sequence adds only its own kept rows.  The layer is the prompt
+// pass's chain over the same transposed hand-over layout [feature][8] (teal_prefill.hip), with two launches of its own:
+//
+//   batched_gemm_kernel       the prompt pass's GEMM (256-column tiles, row groups dealt to slices, the slice's activation rows
+//                             staged in LDS once, one broadcast LDS read per row for the 8 sequences) plus one step after the
+//                             staging: per tile, the slice's UNION row list (wave ballot over the OR of the B per-sequence
+//                             compares, prefix sum into LDS).  Waves stream only listed rows; a sequence that does not keep a
+//                             listed row sees a zero activation.  Rows outside the union are never loaded.
+//   batched_attention_kernel  split-KV attention of B single-token queries, each at its own device position, over its own
+//                             [n_kv][max_seq][hd] cache slab (the verify attention's structure, the sequence as a grid
+//                             dimension), then batched_merge_kernel.
+//
+// Rounding points are the module path's (16-bit projection outputs, RoPE, attention output); sums are fp32.
+#include "teal_common.h"
+
+#include <limits.h>
+
+namespace teal {
+namespace {
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+constexpr int kBatchMax = 8;           // sequences per launch: one 16-byte word of 16-bit activations per feature
+constexpr int kBMaxSplit = 16;
+constexpr int kBPhaseRows = 2048;      // rows a workgroup stages per phase (128 groups of 16)
+constexpr int kBChunks = kBPhaseRows / 64;
+constexpr int kBCountStride = 9;       // counts[slice][segment][9]: kept per sequence (0 .. 7), union (8)
+constexpr int kBAttnChunk = 32;        // context rows a workgroup stages per round
+constexpr int kBAttnMaxQ = 16;         // query heads of one KV head per workgroup
+constexpr int kBAttnMaxSplit = 64;
+
+struct BProd {
+    const uint16_t* xt;      // PROD 0: [Z][8];  PROD 1: the residual rows ht [Z][8]
+    const float* sumsq;      // PROD 1: [nwg][8]
+    const uint16_t* norm_w;  // PROD 1: [Z]
+    const float* gu;         // PROD 2: slabs [gu_split][2 Z][8] of the gate | up launch
+    float eps;
+    int nwg, gu_split, B;
+};
+
+struct BSegs {
+    int nseg;
+    int end[3];   // exclusive end column of each segment over [0, n_total)
+    float tau[3];
+};
+
+// sum of `split` slabs [slice][n_total][8] of one column in slice order, rounded once to the activation dtype
+template <bool BF16>
+__device__ __forceinline__ void b_rounded_row(const float* __restrict__ slabs, const int split, const size_t n_total, const size_t col,
+                                              float (&out)[8]) {
+    f32x4 a0 = (f32x4){0.f, 0.f, 0.f, 0.f}, a1 = a0;
+    for (int s = 0; s < split; ++s) {
+        const float* p = slabs + ((size_t)s * n_total + col) * 8;
+        a0 += *reinterpret_cast<const f32x4*>(p);
+        a1 += *reinterpret_cast<const f32x4*>(p + 4);
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        out[s] = bits_to_float(float_to_bits<BF16>(a0[s]), BF16);
+        out[4 + s] = bits_to_float(float_to_bits<BF16>(a1[s]), BF16);
+    }
+}
+
+template <bool BF16>
+__device__ __forceinline__ u32x4 b_pack_row(const float (&v)[8]) {
+    u32x4 r;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r[j] = (uint32_t)float_to_bits<BF16>(v[2 * j]) | ((uint32_t)float_to_bits<BF16>(v[2 * j + 1]) << 16);
+    return r;
+}
+
+template <bool BF16>
+__device__ __forceinline__ void b_unpack_row(const u32x4 v, float (&x)[8]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { x[2 * j] = bits_to_float(v[j] & 0xFFFFu, BF16); x[2 * j + 1] = bits_to_float(v[j] >> 16, BF16); }
+}
+
+// ------------------------------------------------------------------------------------------------
+// slabs[slice][n][8] (fp32) = sum over the slice's rows m with float32(|x_b[m]|) > tau_seg of W^T[m][n] * x_b[m], sequences b < B.
+//   grid (256-column tiles, row slices); rows in groups of 16, group q belongs to slice q mod split (teal_prefill.hip's layout).
+// Per phase (<= 2048 rows of the slice): stage the rows' 8 activations in LDS, each with a keep mask (bit 8 * ls + b: sequence b
+// keeps the row under the threshold of the tile's ls-th segment), then compact the rows with a non-zero mask — the union of the
+// tile — into a list in row order (chunks of 64 rows: one ballot each, a prefix sum over the chunk counts).  Wave w streams list
+// entries w, w + 16, ...: one 512-byte row segment per load, the row's activations through one broadcast LDS read, and a lane's
+// four columns take the mask bits of their own segment (a tile may hold up to three: the narrow k | v of small models).
+// counts (optional): the first tile of each segment also writes, per slice, how many of the slice's rows each sequence keeps and
+// how many the union holds under that segment's threshold.
+// ------------------------------------------------------------------------------------------------
+template <bool BF16, int NP, int PROD>
+__global__ __launch_bounds__(1024) void batched_gemm_kernel(const BProd pr, const BSegs sg, const uint16_t* __restrict__ w0, const int ld0,
+                                                            const uint16_t* __restrict__ w1, const int ld1, const int tiles0,
+                                                            float* __restrict__ slabs, int* __restrict__ counts, const int Z, const int n_total) {
+    constexpr int WAVES = 16, CPL = 4, BN = 256, U = NP <= 2 ? 8 : 4, PHASE_GROUPS = kBPhaseRows / 16;
+    extern __shared__ __align__(16) unsigned char smem[];
+    u32x4* xs = reinterpret_cast<u32x4*>(smem);                                     // [kBPhaseRows] activations of the phase's rows
+    u32x2* list = reinterpret_cast<u32x2*>(smem + kBPhaseRows * 16);                // [kBPhaseRows] {local row, keep mask}
+    uint32_t* msk = reinterpret_cast<uint32_t*>(smem + kBPhaseRows * 24);           // [kBPhaseRows] keep mask per local row
+    int* coff = reinterpret_cast<int*>(smem + kBPhaseRows * 28);                    // [kBChunks + 1] list offset per chunk, total
+    int* ccnt = coff + kBChunks + 1;                                                // [kBChunks] union rows per chunk
+    int* wcnt = ccnt + kBChunks;                                                    // [WAVES][3][9] counts per wave
+    float* red = reinterpret_cast<float*>(smem);                                    // epilogue: [WAVES][BN][2]
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tile = blockIdx.x, slice = blockIdx.y, split = gridDim.y;
+    const bool second = tile >= tiles0;
+    const uint32_t ld = (uint32_t)(second ? ld1 : ld0);
+    const int c0 = tile * BN;
+    // the segments this tile's columns fall in: sfirst .. slast (local index ls = s - sfirst)
+    // (the kernel-argument arrays are read with constant indices only: a dynamic index would copy them to scratch)
+    const int e0 = sg.end[0], e1 = sg.end[1];
+    const int sfirst = (c0 >= e0 ? 1 : 0) + (c0 >= e1 ? 1 : 0);
+    const int slast = (c0 + BN - 1 >= e0 ? 1 : 0) + (c0 + BN - 1 >= e1 ? 1 : 0);
+    const int nls = slast - sfirst + 1;
+    const float tau_s[3] = {sg.tau[0], sg.tau[1], sg.tau[2]};
+    float tau[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) tau[i] = sfirst + i == 0 ? tau_s[0] : (sfirst + i == 1 ? tau_s[1] : tau_s[2]);
+    const int lc = c0 + lane * CPL;  // this lane's four columns: one segment (boundaries are multiples of 8 columns)
+    const uint32_t lshift = 8u * (uint32_t)((lc >= e0 ? 1 : 0) + (lc >= e1 ? 1 : 0) - sfirst);
+    // segments whose kept counts this tile reports: those that start in it
+    uint32_t count_segs = 0;
+    if (counts) {
+        const int starts[3] = {0, e0, e1};
+#pragma unroll
+        for (int s = 0; s < 3; ++s)
+            if (s < sg.nseg && s >= sfirst && s <= slast && starts[s] / BN == tile) count_segs |= 1u << (s - sfirst);
+    }
+    int* mycnt = wcnt + wave * 3 * kBCountStride;  // this wave's counts, kept in LDS (registers are the streaming loop's)
+    if (count_segs && lane < 3 * kBCountStride) mycnt[lane] = 0;
+
+    const int ngroups = Z >> 4;
+    const int nj = (ngroups - slice + split - 1) / split;  // row groups of this slice
+    const uint16_t* wbase = (second ? w1 : w0) + (size_t)(second ? tile - tiles0 : tile) * BN;
+    f32x2 acc[CPL][NP];
+#pragma unroll
+    for (int c = 0; c < CPL; ++c)
+#pragma unroll
+        for (int p = 0; p < NP; ++p) acc[c][p] = (f32x2){0.0f, 0.0f};
+    auto consume = [&](const u32x2 w, u32x4 xv, const uint32_t mk) {
+        const uint32_t m8 = (mk >> lshift) & 0xFFu;  // this lane's segment: which sequences keep the row
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint32_t keep = ((m8 >> (2 * q)) & 1u ? 0x0000FFFFu : 0u) | ((m8 >> (2 * q + 1)) & 1u ? 0xFFFF0000u : 0u);
+            xv[q] &= keep;  // a dropped activation reads as +0
+        }
+        f32x2 xp[NP];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) xp[p] = (f32x2){bits_to_float(xv[p] & 0xFFFFu, BF16), bits_to_float(xv[p] >> 16, BF16)};
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const float wl = bits_to_float(w[j] & 0xFFFFu, BF16), wh = bits_to_float(w[j] >> 16, BF16);
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                acc[2 * j][p] = __builtin_elementwise_fma((f32x2){wl, wl}, xp[p], acc[2 * j][p]);
+                acc[2 * j + 1][p] = __builtin_elementwise_fma((f32x2){wh, wh}, xp[p], acc[2 * j + 1][p]);
+            }
+        }
+    };
+    for (int jb = 0; jb < nj; jb += PHASE_GROUPS) {
+        const int nrows = min(PHASE_GROUPS, nj - jb) * 16;
+        if (jb) __syncthreads();  // the previous phase's list and rows are consumed
+        [[maybe_unused]] float rstd[8];
+        if constexpr (PROD == 1) {
+            f32x4 pw[2];
+#pragma unroll
+            for (int w = 0; w < 2; ++w) pw[w] = lane < pr.nwg ? *reinterpret_cast<const f32x4*>(pr.sumsq + (size_t)lane * 8 + 4 * w) : (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < 8; ++s) rstd[s] = rsqrtf(wave_sum_f(pw[s >> 2][s & 3]) / (float)Z + pr.eps);
+        }
+        // ---- staging: the rows' activations (16-bit, what the module path holds) and their keep masks
+        for (int r = tid; r < nrows; r += 1024) {
+            const uint32_t m = (uint32_t)(slice + split * (jb + (r >> 4))) * 16u + (uint32_t)(r & 15);
+            float x[8];
+            if constexpr (PROD == 0) {
+                b_unpack_row<BF16>(*reinterpret_cast<const u32x4*>(pr.xt + (size_t)m * 8), x);
+            } else if constexpr (PROD == 1) {  // x = round(round(h * rstd) * w)  (gpt-fast/model.py:289-291)
+                const float nw = bits_to_float(pr.norm_w[m], BF16);
+                b_unpack_row<BF16>(*reinterpret_cast<const u32x4*>(pr.xt + (size_t)m * 8), x);
+#pragma unroll
+                for (int s = 0; s < 8; ++s) {
+                    const float xn = bits_to_float(float_to_bits<BF16>(x[s] * rstd[s]), BF16);
+                    x[s] = bits_to_float(float_to_bits<BF16>(xn * nw), BF16);
+                }
+            } else {  // x = round(round(silu(round(gate))) * round(up))  (gpt-fast/model.py:258-259)
+                float gv[8], uv[8];
+                b_rounded_row<BF16>(pr.gu, pr.gu_split, (size_t)2 * Z, (size_t)m, gv);
+                b_rounded_row<BF16>(pr.gu, pr.gu_split, (size_t)2 * Z, (size_t)Z + m, uv);
+#pragma unroll
+                for (int s = 0; s < 8; ++s) {
+                    const float sl = bits_to_float(float_to_bits<BF16>(gv[s] / (1.0f + expf(-gv[s]))), BF16);
+                    x[s] = bits_to_float(float_to_bits<BF16>(sl * uv[s]), BF16);
+                }
+            }
+            uint32_t mk = 0;
+#pragma unroll
+            for (int s = 0; s < 8; ++s) {
+                x[s] = s < pr.B ? x[s] : 0.0f;  // slots of absent sequences: zero, never kept
+#pragma unroll
+                for (int i = 0; i < 3; ++i)
+                    if (i < nls && s < pr.B && keep_rule(x[s], tau[i])) mk |= 1u << (8 * i + s);
+            }
+            xs[r] = b_pack_row<BF16>(x);
+            msk[r] = mk;
+        }
+        __syncthreads();
+        // ---- the union row list: chunk counts (and the reported kept counts), prefix sum, compaction in row order
+        const int nchunks = (nrows + 63) >> 6;
+        for (int c = wave; c < nchunks; c += WAVES) {
+            const int r = c * 64 + lane;
+            const uint32_t mk = r < nrows ? msk[r] : 0u;
+            const unsigned long long ball = __ballot(mk != 0u);
+            if (lane == 0) ccnt[c] = __popcll(ball);
+            if (count_segs) {
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    if (!((count_segs >> i) & 1u)) continue;
+                    int n[kBCountStride];
+#pragma unroll
+                    for (int b = 0; b < 8; ++b) n[b] = __popcll(__ballot((mk >> (8 * i + b)) & 1u));
+                    n[8] = __popcll(__ballot(((mk >> (8 * i)) & 0xFFu) != 0u));
+                    if (lane == 0) {
+#pragma unroll
+                        for (int b = 0; b < kBCountStride; ++b) mycnt[i * kBCountStride + b] += n[b];
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        if (wave == 0) {
+            const int v = lane < nchunks ? ccnt[lane] : 0;
+            const int incl = wave_incl_scan(v, lane);
+            if (lane < nchunks) coff[lane] = incl - v;
+            if (lane == 63) coff[kBChunks] = incl;
+        }
+        __syncthreads();
+        for (int c = wave; c < nchunks; c += WAVES) {
+            const int r = c * 64 + lane;
+            const uint32_t mk = r < nrows ? msk[r] : 0u;
+            const unsigned long long ball = __ballot(mk != 0u);
+            if (mk) list[coff[c] + lane_rank(ball)] = (u32x2){(uint32_t)r, mk};
+        }
+        __syncthreads();
+        const int nlist = coff[kBChunks];
+        const int njw = nlist > wave ? (nlist - wave + WAVES - 1) / WAVES : 0;  // this wave's entries: wave + 16 j
+        // ---- stream the listed rows: two batches of U rows in flight (teal_prefill.hip's pipeline)
+        // (the list entry is read again where the row is consumed: held across the pipeline it cost 32 scalar registers and
+        //  spilled the kernel)
+        auto issue = [&](u32x2 (&w)[U], const int j0, auto guard) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = decltype(guard)::value ? min(j0 + u, njw - 1) : j0 + u;
+                const uint32_t lr = __builtin_amdgcn_readfirstlane(list[j * WAVES + wave][0]);  // wave-uniform: one broadcast read
+                const uint32_t m = (uint32_t)(slice + split * (jb + (int)(lr >> 4))) * 16u + (lr & 15u);
+                w[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(wbase + (size_t)m * ld) + (uint32_t)lane);
+            }
+        };
+        auto consume_batch = [&](const u32x2 (&w)[U], const int j0, auto guard) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = decltype(guard)::value ? min(j0 + u, njw - 1) : j0 + u;
+                const u32x2 e = list[j * WAVES + wave];
+                const uint32_t mk = (decltype(guard)::value && j0 + u >= njw) ? 0u : e[1];  // repeated entries add nothing
+                consume(w[u], xs[e[0]], mk);
+            }
+        };
+        constexpr std::false_type full{};
+        constexpr std::true_type guarded{};
+        u32x2 wa[U], wb[U];
+        const int nfull = njw / (2 * U);
+        int j0 = 0;
+        if (nfull > 0) {
+            issue(wa, 0, full);
+            __builtin_amdgcn_sched_barrier(0);
+            for (int it = 0; it < nfull; ++it, j0 += 2 * U) {
+                issue(wb, j0 + U, full);
+                __builtin_amdgcn_sched_barrier(0);
+                consume_batch(wa, j0, full);
+                __builtin_amdgcn_sched_barrier(0);
+                if (it + 1 < nfull) issue(wa, j0 + 2 * U, full);
+                __builtin_amdgcn_sched_barrier(0);
+                consume_batch(wb, j0 + U, full);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        if (j0 < njw) {  // the partial pair: entries past the wave's last repeat it with an all-zero mask
+            issue(wa, j0, guarded);
+            const bool two = j0 + U < njw;
+            if (two) issue(wb, j0 + U, guarded);
+            __builtin_amdgcn_sched_barrier(0);
+            consume_batch(wa, j0, guarded);
+            if (two) consume_batch(wb, j0 + U, guarded);
+        }
+    }
+    // the 16 waves in fixed order through LDS, one sequence pair per round
+    const uint32_t col_base = (uint32_t)tile * BN;
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < CPL; ++c) *reinterpret_cast<f32x2*>(red + ((size_t)wave * BN + lane * CPL + c) * 2) = acc[c][p];
+        __syncthreads();
+        if (tid < BN * 2) {
+            const int col = tid >> 1, e = tid & 1;
+            float sum = 0.0f;
+#pragma unroll
+            for (int w = 0; w < WAVES; ++w) sum += red[((size_t)w * BN + col) * 2 + e];
+            slabs[((size_t)slice * n_total + col_base + col) * 8 + 2 * p + e] = sum;
+        }
+    }
+    if (count_segs) {  // (workgroup-uniform) the waves' counts, added in wave order: counts[slice][segment][9]
+        __syncthreads();
+        if (tid < 3 * kBCountStride) {
+            const int i = tid / kBCountStride, b = tid % kBCountStride;
+            if ((count_segs >> i) & 1u) {
+                int s = 0;
+                for (int w = 0; w < WAVES; ++w) s += wcnt[(w * 3 + i) * kBCountStride + b];
+                counts[((size_t)slice * 3 + sfirst + i) * kBCountStride + b] = s;
+            }
+        }
+    }
+}
+
+// y[b][n] = round(sum of `split` slabs [slice][n][8] in slice order), b < B
+template <bool BF16>
+__global__ __launch_bounds__(256) void batched_round_rows_kernel(const float* __restrict__ slabs, const int split, const int N, const int B,
+                                                                 uint16_t* __restrict__ y) {
+    const int col = blockIdx.x * 256 + threadIdx.x;
+    if (col >= N) return;
+    float r[8];
+    b_rounded_row<BF16>(slabs, split, (size_t)N, (size_t)col, r);
+#pragma unroll
+    for (int b = 0; b < 8; ++b)
+        if (b < B) y[(size_t)b * N + col] = float_to_bits<BF16>(r[b]);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Attention of B single-token queries, sequence b at position p_b = clamp(pos[b], 0, max_seq - 1) against ITS cache rows 0 .. p_b.
+// Grid (nsplit, n_kv, groups * B): a workgroup serves hq query heads of one KV head of one sequence.  The new row (q of the hq
+// heads, k and v of the KV head) is rebuilt from the wqkv slabs (slot b, rounded) with RoPE at p_b (rounded) by every workgroup
+// that needs it and read from LDS; split 0 of group 0 stores it to the cache for LATER launches.  Context rows in chunks of 32,
+// chunk c to split c mod nsplit; each workgroup leaves {m, l, o[hd]} per (head, sequence), merged in split order.
+// ------------------------------------------------------------------------------------------------
+template <bool BF16, int HD>
+__global__ __launch_bounds__(256) void batched_attention_kernel(const float* __restrict__ slabs, const int split,
+                                                                const int* __restrict__ pos_ptr, const uint16_t* __restrict__ rope,
+                                                                uint16_t* __restrict__ k_cache, uint16_t* __restrict__ v_cache,
+                                                                float* __restrict__ partials, const int B, const int n_head,
+                                                                const int n_kv, const int hq, const int groups, const int max_seq,
+                                                                const float scale) {
+    constexpr int C = kBAttnChunk, NT = 256, OJ = (kBAttnMaxQ * HD + NT - 1) / NT, QSTEP = NT / HD;
+    __shared__ float qs[kBAttnMaxQ][HD + 1];
+    __shared__ float kn[HD], vn[HD];
+    __shared__ float ks[C][HD + 1];
+    __shared__ float vs[C][HD];
+    __shared__ float sc[kBAttnMaxQ][C + 1];
+    __shared__ float mrow[kBAttnMaxQ], lrow[kBAttnMaxQ], alph[kBAttnMaxQ];
+    const int tid = threadIdx.x, sp = blockIdx.x, nsplit = gridDim.x, kvh = blockIdx.y;
+    const int b = blockIdx.z / groups, grp = blockIdx.z % groups;
+    const int rep = n_head / n_kv, h0 = kvh * rep + grp * hq, NQ = hq;
+    const int p = min(max(pos_ptr[b], 0), max_seq - 1);  // (a position past the cache is clamped into it)
+    const int ctx = p + 1;
+    const size_t nq = (size_t)n_head * HD, nkv = (size_t)n_kv * HD, ntot = nq + 2 * nkv;
+    const size_t seq_off = (size_t)b * n_kv * max_seq * HD;
+
+    const int ncols = (hq + 2) * HD;
+    for (int c = tid; c < ncols; c += NT) {
+        const int part = c < hq * HD ? 0 : (c < (hq + 1) * HD ? 1 : 2);
+        const int d = part == 0 ? c % HD : c - (hq + part - 1) * HD;
+        const size_t col = part == 0 ? (size_t)h0 * HD + c : (part == 1 ? nq : nq + nkv) + (size_t)kvh * HD + d;
+        float a = 0.0f;
+        for (int s = 0; s < split; ++s) a += slabs[((size_t)s * ntot + col) * 8 + b];
+        const float r = bits_to_float(float_to_bits<BF16>(a), BF16);
+        if (part == 0) qs[c / HD][d] = r;
+        else if (part == 1) kn[d] = r;
+        else vn[d] = r;
+    }
+    if (tid < kBAttnMaxQ) { mrow[tid] = -INFINITY; lrow[tid] = 0.0f; }
+    __syncthreads();
+    for (int e = tid; e < (NQ + 1) * (HD / 2); e += NT) {  // one (even, odd) pair per thread
+        const int row = e / (HD / 2), i = e % (HD / 2);
+        float* x = row < NQ ? &qs[row][0] : &kn[0];
+        const uint32_t cs = *reinterpret_cast<const uint32_t*>(rope + ((size_t)p * (HD / 2) + i) * 2);
+        const float c = bits_to_float(cs & 0xFFFFu, BF16), sn = bits_to_float(cs >> 16, BF16);
+        const float x0 = x[2 * i], x1 = x[2 * i + 1];
+        x[2 * i] = bits_to_float(float_to_bits<BF16>(rope_even(x0, x1, c, sn)), BF16);
+        x[2 * i + 1] = bits_to_float(float_to_bits<BF16>(rope_odd(x0, x1, c, sn)), BF16);
+    }
+    __syncthreads();
+    uint16_t* kc_b = k_cache + seq_off + (size_t)kvh * max_seq * HD;
+    uint16_t* vc_b = v_cache + seq_off + (size_t)kvh * max_seq * HD;
+    if (sp == 0 && grp == 0) {  // one writer per (sequence, KV head): row p <= max_seq - 1
+        for (int d = tid; d < HD; d += NT) {
+            kc_b[(size_t)p * HD + d] = float_to_bits<BF16>(kn[d]);
+            vc_b[(size_t)p * HD + d] = float_to_bits<BF16>(vn[d]);
+        }
+    }
+
+    const int d_own = tid % HD;
+    float o[OJ];
+#pragma unroll
+    for (int j = 0; j < OJ; ++j) o[j] = 0.0f;
+    const int nchunks = (ctx + C - 1) / C;
+    for (int ch = sp; ch < nchunks; ch += nsplit) {
+        const int r0 = ch * C;
+        __syncthreads();  // the previous chunk's ks / vs / sc are consumed
+        for (int e = tid; e < C * (HD / 8); e += NT) {
+            const int rr = e / (HD / 8), seg = e % (HD / 8), r = r0 + rr;
+            float kf[8], vf[8];
+            if (r < p) {  // cached rows (never the row this launch writes)
+                const u32x4 kw = *reinterpret_cast<const u32x4*>(kc_b + (size_t)r * HD + seg * 8);
+                const u32x4 vw = *reinterpret_cast<const u32x4*>(vc_b + (size_t)r * HD + seg * 8);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    kf[2 * j] = bits_to_float(kw[j] & 0xFFFFu, BF16); kf[2 * j + 1] = bits_to_float(kw[j] >> 16, BF16);
+                    vf[2 * j] = bits_to_float(vw[j] & 0xFFFFu, BF16); vf[2 * j + 1] = bits_to_float(vw[j] >> 16, BF16);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    kf[j] = r == p ? kn[seg * 8 + j] : 0.0f;
+                    vf[j] = r == p ? vn[seg * 8 + j] : 0.0f;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { ks[rr][seg * 8 + j] = kf[j]; vs[rr][seg * 8 + j] = vf[j]; }
+        }
+        __syncthreads();
+        for (int pq = tid; pq < NQ * C; pq += NT) {
+            const int qi = pq / C, rr = pq % C, r = r0 + rr;
+            float s = -INFINITY;
+            if (r <= p) {
+                float a = 0.0f;
+#pragma unroll 16
+                for (int j = 0; j < HD; ++j) a = fmaf(qs[qi][j], ks[rr][j], a);
+                s = bits_to_float(float_to_bits<BF16>(a * scale), BF16);
+            }
+            sc[qi][rr] = s;
+        }
+        __syncthreads();
+        if (tid < NQ) {
+            const int qi = tid;
+            float mx = mrow[qi];
+            for (int rr = 0; rr < C; ++rr) mx = fmaxf(mx, sc[qi][rr]);
+            float a = 1.0f, l = lrow[qi];
+            if (mx != -INFINITY) {
+                a = mrow[qi] == -INFINITY ? 0.0f : expf(mrow[qi] - mx);
+                l *= a;
+                for (int rr = 0; rr < C; ++rr) {
+                    const float e = sc[qi][rr] == -INFINITY ? 0.0f : expf(sc[qi][rr] - mx);
+                    sc[qi][rr] = e;
+                    l += e;
+                }
+                mrow[qi] = mx;
+            } else {
+                for (int rr = 0; rr < C; ++rr) sc[qi][rr] = 0.0f;
+            }
+            lrow[qi] = l;
+            alph[qi] = a;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < OJ; ++j) {
+            const int qi = tid / HD + j * QSTEP;
+            if (qi < NQ) {
+                float acc = o[j] * alph[qi];
+#pragma unroll 8
+                for (int rr = 0; rr < C; ++rr) acc = fmaf(sc[qi][rr], vs[rr][d_own], acc);
+                o[j] = acc;
+            }
+        }
+    }
+    __syncthreads();
+    // partials[((h * B + b) * nsplit + sp) * (HD + 2)] = {m, l, o[HD]}
+#pragma unroll
+    for (int j = 0; j < OJ; ++j) {
+        const int qi = tid / HD + j * QSTEP;
+        if (qi < NQ) {
+            const int h = h0 + qi;
+            float* q = partials + (((size_t)h * B + b) * nsplit + sp) * (HD + 2);
+            q[2 + d_own] = o[j];
+            if (d_own == 0) { q[0] = mrow[qi]; q[1] = lrow[qi]; }
+        }
+    }
+}
+
+// yt[(h * hd + d) * 8 + b] = round(sum_s o_s e^(m_s - M) / sum_s l_s e^(m_s - M)), splits in order; slots b >= B are zero
+template <bool BF16>
+__global__ __launch_bounds__(128) void batched_merge_kernel(const float* __restrict__ partials, uint16_t* __restrict__ yt, const int B,
+                                                            const int hd, const int nsplit) {
+    const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
+    if (d >= hd) return;
+    uint16_t* y = yt + ((size_t)h * hd + d) * 8 + b;
+    if (b >= B) { *y = 0; return; }
+    const float* p = partials + ((size_t)h * B + b) * nsplit * (hd + 2);
+    float M = -INFINITY;
+    for (int s = 0; s < nsplit; ++s) M = fmaxf(M, p[(size_t)s * (hd + 2)]);
+    float L = 0.0f, O = 0.0f;
+    for (int s = 0; s < nsplit; ++s) {
+        const float* q = p + (size_t)s * (hd + 2);
+        const float l = q[1];
+        if (l > 0.0f) {
+            const float f = expf(q[0] - M);
+            L = fmaf(l, f, L);
+            O = fmaf(q[2 + d], f, O);
+        }
+    }
+    *y = float_to_bits<BF16>(O / L);
+}
+
+}  // namespace
+}  // namespace teal
+
+using namespace teal;
+
+extern "C" {
+
+int teal_batched_sparse_gemm(const teal_prefill_in_t* in, const teal_batched_segs_t* segs, const void* w0T, int ld0, int n0, const void* w1T,
+                             int ld1, int n1, float* slabs, size_t slabs_bytes, int Z, int B, int32_t* counts, int dtype, int* split_out,
+                             void* stream) {
+    if (!in || !segs || !w0T || !slabs || !split_out || Z <= 0 || n0 <= 0 || n1 < 0 || (n1 > 0 && !w1T)) return TEAL_ERR_ARG;
+    if (dtype != TEAL_F16 && dtype != TEAL_BF16) return TEAL_ERR_DTYPE;
+    if (B < 1 || B > kBatchMax || (Z & 255) || Z > 65536 || (ld0 & 7) || (ld1 & 7) || ld0 < n0 || (n1 > 0 && ld1 < n1)) return TEAL_ERR_SHAPE;
+    const int ntot = n0 + n1;
+    if (n0 % 256 || n1 % 256) return TEAL_ERR_SHAPE;
+    BSegs sg = {};
+    sg.nseg = segs->nseg;
+    if (sg.nseg < 1 || sg.nseg > 3) return TEAL_ERR_ARG;
+    for (int s = 0; s < sg.nseg; ++s) {
+        const int lo = s == 0 ? 0 : segs->col_end[s - 1];
+        if (segs->col_end[s] <= lo || (segs->col_end[s] & 7)) return TEAL_ERR_SHAPE;
+        sg.end[s] = segs->col_end[s];
+        sg.tau[s] = segs->tau[s];
+    }
+    if (sg.end[sg.nseg - 1] != ntot) return TEAL_ERR_SHAPE;
+    for (int s = sg.nseg; s < 3; ++s) { sg.end[s] = ntot; sg.tau[s] = sg.tau[sg.nseg - 1]; }
+    BProd pr = {};
+    pr.B = B;
+    switch (in->mode) {
+        case TEAL_PREFILL_IN_XT:
+            if (!in->xt || !aligned16(in->xt)) return TEAL_ERR_ARG;
+            pr.xt = reinterpret_cast<const uint16_t*>(in->xt);
+            break;
+        case TEAL_PREFILL_IN_NORM:
+            if (!in->xt || !aligned16(in->xt) || !in->sumsq || !aligned16(in->sumsq) || !in->norm_w || in->nwg < 1 || in->nwg > 64) return TEAL_ERR_ARG;
+            pr.xt = reinterpret_cast<const uint16_t*>(in->xt);
+            pr.sumsq = in->sumsq; pr.nwg = in->nwg; pr.norm_w = reinterpret_cast<const uint16_t*>(in->norm_w); pr.eps = in->eps;
+            break;
+        case TEAL_PREFILL_IN_SILU_MUL:
+            if (!in->gu_slabs || !aligned16(in->gu_slabs) || in->gu_split < 1 || in->gu_split > kBMaxSplit) return TEAL_ERR_ARG;
+            if (in->gu_slabs == slabs) return TEAL_ERR_ARG;  // the launch reads its producer's slabs while it writes its own
+            pr.gu = in->gu_slabs; pr.gu_split = in->gu_split;
+            break;
+        default: return TEAL_ERR_ARG;
+    }
+    if (!aligned16(w0T) || (w1T && !aligned16(w1T)) || !aligned16(slabs)) return TEAL_ERR_ALIGN;
+    DeviceCtx* ctx = device_ctx();
+    if (!ctx) return TEAL_ERR_NO_DEVICE;
+    // the prompt pass's geometry (teal_prefill_gemm): never more workgroups than CUs, every wave keeping a full pair of batches
+    // of a dense slice, the fewest 8-row batches per wave (ties: the fewer slabs)
+    constexpr int bn = 256;
+    const int tiles = ntot / bn, ngroups = Z >> 4;
+    int smax = ctx->num_cu / tiles;
+    if (smax > Z / 256) smax = Z / 256;
+    if (smax > kBMaxSplit) smax = kBMaxSplit;
+    if (smax < 1) smax = 1;
+    int split = 1, best = INT_MAX;
+    for (int c = 1; c <= smax; ++c) {
+        const int batches = ((ngroups + c - 1) / c + 7) / 8;
+        if (batches < best) { best = batches; split = c; }
+    }
+    if (slabs_bytes < (size_t)split * ntot * 8 * sizeof(float)) return TEAL_ERR_WORKSPACE;
+    const dim3 grid(tiles, split), block(1024);
+    const size_t lds = (size_t)kBPhaseRows * 28 + (size_t)(2 * kBChunks + 1) * sizeof(int) + (size_t)16 * 3 * kBCountStride * sizeof(int);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int np = (B + 1) / 2, tiles0 = n0 / bn;
+    auto* a = reinterpret_cast<const uint16_t*>(w0T);
+    auto* b = reinterpret_cast<const uint16_t*>(w1T);
+    int* cnt = reinterpret_cast<int*>(counts);
+#define TEAL_BG(BF, NPV, PR) hipLaunchKernelGGL((batched_gemm_kernel<BF, NPV, PR>), grid, block, lds, st, pr, sg, a, ld0, b, ld1, tiles0, slabs, cnt, Z, ntot)
+#define TEAL_BG_PR(BF, NPV) do { if (in->mode == TEAL_PREFILL_IN_NORM) TEAL_BG(BF, NPV, 1); else if (in->mode == TEAL_PREFILL_IN_SILU_MUL) TEAL_BG(BF, NPV, 2); else TEAL_BG(BF, NPV, 0); } while (0)
+#define TEAL_BG_NP(BF) do { switch (np) { case 1: TEAL_BG_PR(BF, 1); break; case 2: TEAL_BG_PR(BF, 2); break; case 3: TEAL_BG_PR(BF, 3); break; \
+    default: TEAL_BG_PR(BF, 4); } } while (0)
+    if (dtype == TEAL_BF16) TEAL_BG_NP(true); else TEAL_BG_NP(false);
+#undef TEAL_BG_NP
+#undef TEAL_BG_PR
+#undef TEAL_BG
+    *split_out = split;
+    return hipGetLastError() == hipSuccess ? TEAL_OK : TEAL_ERR_LAUNCH;
+}
+
+int teal_batched_round_rows(const float* slabs, int split, int N, int B, void* y, int dtype, void* stream) {
+    if (!slabs || !y || split < 1 || split > kBMaxSplit || N <= 0) return TEAL_ERR_ARG;
+    if (dtype != TEAL_F16 && dtype != TEAL_BF16) return TEAL_ERR_DTYPE;
+    if (B < 1 || B > kBatchMax) return TEAL_ERR_SHAPE;
+    if (!aligned16(slabs)) return TEAL_ERR_ALIGN;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid((N + 255) / 256);
+    auto* yo = reinterpret_cast<uint16_t*>(y);
+    if (dtype == TEAL_BF16) hipLaunchKernelGGL((batched_round_rows_kernel<true>), grid, dim3(256), 0, st, slabs, split, N, B, yo);
+    else hipLaunchKernelGGL((batched_round_rows_kernel<false>), grid, dim3(256), 0, st, slabs, split, N, B, yo);
+    return hipGetLastError() == hipSuccess ? TEAL_OK : TEAL_ERR_LAUNCH;
+}
+
+size_t teal_batched_decode_attention_ws_bytes(int B, int n_head, int head_dim) {
+    return (size_t)n_head * (B < 1 ? 1 : B) * kBAttnMaxSplit * (head_dim + 2) * sizeof(float);
+}
+
+int teal_batched_decode_attention(const float* qkv_slabs, int split, const void* rope, const int32_t* pos, void* k_cache, void* v_cache,
+                                  void* yt, float* partials, size_t partials_bytes, int B, int n_head, int n_kv_head, int head_dim,
+                                  int max_seq, int dtype, void* stream) {
+    if (!qkv_slabs || !rope || !pos || !k_cache || !v_cache || !yt || !partials || split < 1 || split > kBMaxSplit) return TEAL_ERR_ARG;
+    if (dtype != TEAL_F16 && dtype != TEAL_BF16) return TEAL_ERR_DTYPE;
+    if ((head_dim != 64 && head_dim != 128) || n_head <= 0 || n_kv_head <= 0 || n_head % n_kv_head || B < 1 || B > kBatchMax || max_seq < 1)
+        return TEAL_ERR_SHAPE;
+    if (!aligned16(qkv_slabs) || !aligned16(k_cache) || !aligned16(v_cache)) return TEAL_ERR_ALIGN;
+    DeviceCtx* ctx = device_ctx();
+    if (!ctx) return TEAL_ERR_NO_DEVICE;
+    const int rep = n_head / n_kv_head;
+    int hq = 1;  // the most query heads of a group that fit a workgroup and divide the group
+    for (int c = 1; c <= rep; ++c)
+        if (rep % c == 0 && c <= kBAttnMaxQ) hq = c;
+    const int groups = rep / hq;
+    // about two workgroups per CU at the longest context the cache holds; never more splits than chunks
+    const int chunks = (max_seq + kBAttnChunk - 1) / kBAttnChunk;
+    const int wg = n_kv_head * groups * B;
+    int nsplit = (2 * ctx->num_cu + wg - 1) / wg;
+    nsplit = nsplit < 1 ? 1 : (nsplit > kBAttnMaxSplit ? kBAttnMaxSplit : nsplit);
+    if (nsplit > chunks) nsplit = chunks;
+    if (partials_bytes < (size_t)n_head * B * nsplit * (head_dim + 2) * sizeof(float)) return TEAL_ERR_WORKSPACE;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const float scale = 1.0f / sqrtf((float)head_dim);
+    const dim3 grid(nsplit, n_kv_head, groups * B);
+    auto* rp = reinterpret_cast<const uint16_t*>(rope);
+    auto* kc = reinterpret_cast<uint16_t*>(k_cache);
+    auto* vc = reinterpret_cast<uint16_t*>(v_cache);
+    auto* y = reinterpret_cast<uint16_t*>(yt);
+#define TEAL_BA(BF, HDV) do { \
+        hipLaunchKernelGGL((batched_attention_kernel<BF, HDV>), grid, dim3(256), 0, st, qkv_slabs, split, pos, rp, kc, vc, partials, B, \
+                           n_head, n_kv_head, hq, groups, max_seq, scale); \
+        hipLaunchKernelGGL((batched_merge_kernel<BF>), dim3(n_head, kBatchMax), dim3(128), 0, st, partials, y, B, head_dim, nsplit); } while (0)
+    if (dtype == TEAL_BF16) { if (head_dim == 128) TEAL_BA(true, 128); else TEAL_BA(true, 64); }
+    else { if (head_dim == 128) TEAL_BA(false, 128); else TEAL_BA(false, 64); }
+#undef TEAL_BA
+    return hipGetLastError() == hipSuccess ? TEAL_OK : TEAL_ERR_LAUNCH;
+}
+
+}  // extern "C"

@@ -1,0 +1,293 @@
+"""Batched decode: one fused step for B <= 8 TEAL-sparse sequences (teal_amd/csrc/teal_batched.hip).
+
+TEAL's rule is per token (the reference's SparsifyFn masks every token's activations against the site's threshold), so
+sequence b's projection is W . (x_b * [|x_b| > tau]).  A step streams every weight row that ANY sequence keeps — the union —
+once, and each sequence adds only its own kept rows.  With independent activations at 50 % kept per sequence the union holds
+about 1 - 0.5^B of the rows, so the bytes per step grow with B while the tokens per step grow as B.
+
+One layer, the prompt pass's hand-over layout [feature][8] (slot b = sequence b):
+
+    gemm(wqkv, tau_q | tau_k | tau_v) [RMSNorm while staging] -> attention (RoPE at pos[b], row pos[b] of cache b, split-KV)
+    -> gemm(wo, tau_o) -> resid -> gemm(w1 | w3, tau_gate | tau_up) [RMSNorm while staging]
+    -> gemm(w2, tau_down) [silu * up while staging] -> resid
+                                 ... -> gemm(lm_head, tau = -inf) [final RMSNorm while staging] -> logits [B, vocab]
+
+The embedding rows of the B current tokens enter through teal_prefill_resid_norm.  Sampling is B launches of the fused sampler,
+each with its own rng_state / token / position / history, so one hipGraph replay is one step for all B sequences.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Dict, List, Optional
+
+import torch
+
+from .. import _lib, runtime
+from ..kernels.sparse_gemv import BATCH_MAX, batched_segs
+from ..monkeypatch import UP_SHIFT_BYTES, to_column_major
+from .model import Transformer
+from .prefill import IN_NORM, IN_SILU_MUL, IN_XT, PrefillIn
+
+PROJ_LAUNCHES = (("qkv", ("q", "k", "v")), ("o", ("o",)), ("gateup", ("gate", "up")), ("down", ("down",)))
+NINF = float("-inf")
+
+
+class BatchedDecodeEngine:
+    @staticmethod
+    def supports(model: Transformer) -> Optional[str]:
+        """None if the batched step can run `model` as it stands (batch = the caches' max_batch_size), else the reason."""
+        cfg = model.config
+        if int(getattr(model, "tp_world", 1)) > 1:
+            return "tensor-parallel models are not batched (decode them one sequence at a time)"
+        lins = [lin for layer in model.layers for lin in (layer.attention.wqkv, layer.attention.wo, layer.feed_forward.w1,
+                                                         layer.feed_forward.w3, layer.feed_forward.w2)] + [model.output]
+        if any(hasattr(lin, "scales_and_zeros") or hasattr(lin, "scales") or lin.weight.dtype == torch.int8 for lin in lins):
+            return "quantised (int8 / int4) weights are not batched"
+        dt = model.output.weight.dtype
+        if dt not in (torch.float16, torch.bfloat16) or any(lin.weight.dtype != dt for lin in lins):
+            return f"weights are not uniformly fp16 / bf16: {dt}"
+        if not model.output.weight.is_cuda:
+            return "model is not on a HIP device"
+        inter = model.layers[0].feed_forward.w1.out_features
+        qd, kv = cfg.n_head * cfg.head_dim, cfg.n_local_heads * cfg.head_dim
+        if (cfg.head_dim not in (64, 128) or cfg.dim != qd or cfg.dim % 256 or cfg.dim > 16384 or inter % 256 or inter > 65536
+                or (qd + 2 * kv) % 256 or kv % 8 or cfg.vocab_size % 256):
+            return ("shape outside the batched kernels' contract (head_dim 64 / 128, dim = n_head * head_dim <= 16384, "
+                    "dim / intermediate / qkv width / vocab multiples of 256)")
+        if model.freqs_cis is None or model.freqs_cis.dtype != dt:
+            return "caches are not set up (model.setup_caches) in the model dtype"
+        B = None
+        for layer in model.layers:
+            kc = getattr(layer.attention, "kv_cache", None)
+            if kc is None or kc.k_cache.dim() != 4 or not kc.k_cache.is_contiguous() or not kc.v_cache.is_contiguous():
+                return "KV caches must be contiguous [B, n_kv, max_seq, head_dim] tensors"
+            B = kc.k_cache.shape[0] if B is None else B
+            if kc.k_cache.shape[0] != B or kc.v_cache.shape[0] != B:
+                return "KV caches must share one batch size"
+        if B is None or not 1 <= B <= BATCH_MAX:
+            return f"batch size {B} outside 1..{BATCH_MAX} (setup_caches(max_batch_size=B))"
+        return None
+
+    def __init__(self, model: Transformer, thresholds: List[Dict[str, float]], batch: int):
+        why = BatchedDecodeEngine.supports(model)
+        if why is not None:
+            raise ValueError(f"BatchedDecodeEngine cannot run this model: {why}")
+        B = int(batch)
+        cache_b = model.layers[0].attention.kv_cache.k_cache.shape[0]
+        if not 1 <= B <= BATCH_MAX or B != cache_b:
+            raise ValueError(f"BatchedDecodeEngine: batch {B} must equal the caches' max_batch_size ({cache_b}) and be <= {BATCH_MAX}")
+        if len(thresholds) != len(model.layers):
+            raise ValueError("one thresholds dict per layer")
+        self.L = _lib.load()
+        runtime.init()
+        self.model, self.cfg, self.B = model, model.config, B
+        cfg = self.cfg
+        dev, dt = model.output.weight.device, model.output.weight.dtype
+        self.dtype, self.code = dt, runtime.dtype_code(dt)
+        for layer in model.layers:  # the decode step's layout (idempotent)
+            for lin in (layer.attention.wqkv, layer.attention.wo, layer.feed_forward.w1, layer.feed_forward.w3, layer.feed_forward.w2):
+                to_column_major(lin, shift_bytes=UP_SHIFT_BYTES if lin is layer.feed_forward.w3 else 0)
+        to_column_major(model.output)
+        self.ths = [dict(t) for t in thresholds]
+        self.dim, self.hd = cfg.dim, cfg.head_dim
+        self.kv = cfg.n_local_heads * cfg.head_dim
+        self.nqkv = self.dim + 2 * self.kv
+        self.inter = model.layers[0].feed_forward.w1.out_features
+        self.max_seq = model.max_seq_length
+        V = cfg.vocab_size
+        z = lambda *shape, dtype=dt: torch.zeros(*shape, device=dev, dtype=dtype)  # noqa: E731
+        i32 = dict(dtype=torch.int32)
+        self.tok_buf = z(BATCH_MAX, **i32)   # the B current tokens
+        self.pos_buf = z(BATCH_MAX, **i32)   # the B positions (device; may differ)
+        self.ht, self.yt = z(self.dim, BATCH_MAX), z(self.dim, BATCH_MAX)
+        n = 16 * max(self.nqkv, 2 * self.inter, self.dim) * BATCH_MAX
+        self.slabs = [z(n, dtype=torch.float32), z(n, dtype=torch.float32)]
+        self.lm_slabs = z(16 * V * BATCH_MAX, dtype=torch.float32)
+        self.sumsq = z(64 * BATCH_MAX, dtype=torch.float32)
+        self.logits = z(B, V)
+        nb = int(self.L.teal_batched_decode_attention_ws_bytes(B, cfg.n_head, cfg.head_dim))
+        self.partials = z((nb + 3) // 4, dtype=torch.float32)
+        # kept counts of the last step: [layer][launch][slice 16][segment 3][9] (per sequence, union)
+        self.counts = z(len(model.layers), len(PROJ_LAUNCHES), 16 * 3 * 9, **i32)
+        self.splits = [[0] * len(PROJ_LAUNCHES) for _ in model.layers]
+        self.rope = model.freqs_cis.contiguous()
+        self.eps = float(cfg.norm_eps)
+        self.nwg = (self.dim + 255) // 256
+        self._split = ctypes.c_int(0)
+        # sampling state, one set per sequence
+        self.ws = runtime.new_workspace(self.dim, V)
+        self.rng_state = torch.zeros(B, 2, dtype=torch.int64, device=dev)
+        self.history = z(B, self.max_seq + 1, **i32)
+        self._seed = 1234
+        self._graph = None
+        self._graph_key = None
+        kvw = self.kv
+        self._segs = [{
+            "qkv": batched_segs([self.dim, self.dim + kvw, self.nqkv], [t["q"], t["k"], t["v"]]),
+            "o": batched_segs([self.dim], [t["o"]]),
+            "gateup": batched_segs([self.inter, 2 * self.inter], [t["gate"], t["up"]]),
+            "down": batched_segs([self.dim], [t["down"]]),
+        } for t in self.ths]
+        self._lm_segs = batched_segs([V], [NINF])
+
+    # ---- launches ---------------------------------------------------------------------------------
+    def _gemm(self, gin: PrefillIn, segs, lin0, lin1, Z: int, out: torch.Tensor, counts: Optional[torch.Tensor], st) -> int:
+        w0 = lin0.weight
+        rc = self.L.teal_batched_sparse_gemm(ctypes.byref(gin), ctypes.byref(segs), w0.data_ptr(), w0.stride(1), w0.shape[0],
+                                             lin1.weight.data_ptr() if lin1 is not None else None,
+                                             lin1.weight.stride(1) if lin1 is not None else 0, lin1.weight.shape[0] if lin1 is not None else 0,
+                                             out.data_ptr(), out.numel() * 4, Z, self.B, counts.data_ptr() if counts is not None else None,
+                                             self.code, ctypes.byref(self._split), st)
+        if rc != 0:
+            _lib.check(rc, "teal_batched_sparse_gemm")
+        return self._split.value
+
+    def _resid(self, tokens: bool, slabs: Optional[torch.Tensor], split: int, st):
+        m = self.model
+        rc = self.L.teal_prefill_resid_norm(m.tok_embeddings.weight.data_ptr() if tokens else None,
+                                            self.tok_buf.data_ptr() if tokens else None, self.B, None if tokens else self.ht.data_ptr(),
+                                            slabs.data_ptr() if slabs is not None else None, split, None, self.eps, self.dim,
+                                            self.ht.data_ptr(), None, None, self.sumsq.data_ptr(), self.code, st)
+        if rc != 0:
+            _lib.check(rc, "teal_prefill_resid_norm")
+
+    def _norm_in(self, norm_w) -> PrefillIn:
+        return PrefillIn(mode=IN_NORM, xt=self.ht.data_ptr(), sumsq=self.sumsq.data_ptr(), nwg=self.nwg, norm_w=norm_w.data_ptr(), eps=self.eps)
+
+    def _step(self, ths_override: Optional[float] = None):
+        """one step for all B sequences from tok_buf / pos_buf -> self.logits [B, vocab] (no host synchronisation)"""
+        m, cfg, L, st = self.model, self.cfg, self.L, runtime.stream_ptr()
+        A, Bs = self.slabs
+        self._resid(True, None, 0, st)
+        for i, layer in enumerate(m.layers):
+            at, ff, sg, cnt = layer.attention, layer.feed_forward, self._segs[i], self.counts[i]
+            sp = self.splits[i]
+            sp[0] = ns = self._gemm(self._norm_in(layer.attention_norm.weight), sg["qkv"], at.wqkv, None, self.dim, A, cnt[0], st)
+            kc, vc = at.kv_cache.k_cache, at.kv_cache.v_cache
+            rc = L.teal_batched_decode_attention(A.data_ptr(), ns, self.rope.data_ptr(), self.pos_buf.data_ptr(), kc.data_ptr(), vc.data_ptr(),
+                                                 self.yt.data_ptr(), self.partials.data_ptr(), self.partials.numel() * 4, self.B, cfg.n_head,
+                                                 cfg.n_local_heads, cfg.head_dim, self.max_seq, self.code, st)
+            if rc != 0:
+                _lib.check(rc, "teal_batched_decode_attention")
+            sp[1] = ns = self._gemm(PrefillIn(mode=IN_XT, xt=self.yt.data_ptr()), sg["o"], at.wo, None, self.dim, Bs, cnt[1], st)
+            self._resid(False, Bs, ns, st)
+            sp[2] = ns = self._gemm(self._norm_in(layer.ffn_norm.weight), sg["gateup"], ff.w1, ff.w3, self.dim, A, cnt[2], st)
+            sp[3] = ns = self._gemm(PrefillIn(mode=IN_SILU_MUL, gu_slabs=A.data_ptr(), gu_split=ns), sg["down"], ff.w2, None, self.inter, Bs,
+                                    cnt[3], st)
+            self._resid(False, Bs, ns, st)
+        ns = self._gemm(self._norm_in(m.norm.weight), self._lm_segs, m.output, None, self.dim, self.lm_slabs, None, st)
+        rc = L.teal_batched_round_rows(self.lm_slabs.data_ptr(), ns, cfg.vocab_size, self.B, self.logits.data_ptr(), self.code, st)
+        if rc != 0:
+            _lib.check(rc, "teal_batched_round_rows (lm_head)")
+        return self.logits
+
+    @torch.no_grad()
+    def __call__(self, tokens: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
+        """tokens [B], pos [B] (ints; positions may differ) -> logits [B, vocab] (a view of the engine's buffer).  Writes KV row
+        pos[b] of sequence b in every layer."""
+        B = self.B
+        assert tokens.numel() == B and pos.numel() == B
+        self.tok_buf[:B].copy_(tokens.view(-1).to(torch.int32))
+        self.pos_buf[:B].copy_(pos.view(-1).to(torch.int32))
+        return self._step()
+
+    # ---- sampling and the device-resident loop ----------------------------------------------------
+    def _sample(self, temperature: float, top_k: Optional[int]):
+        st, V = runtime.stream_ptr(), self.cfg.vocab_size
+        for b in range(self.B):
+            rc = self.L.teal_sample_topk_ws(self.logits[b].data_ptr(), V, self.code, int(top_k or 0), float(temperature),
+                                            self.rng_state[b].data_ptr(), self.tok_buf[b:].data_ptr(), self.pos_buf[b:].data_ptr(),
+                                            self.history[b].data_ptr(), self.history.shape[1], self.ws.data_ptr(), self.ws.numel() * 4, st)
+            if rc != 0:
+                _lib.check(rc, "teal_sample_topk (batched)")
+
+    def _self_step(self, temperature, top_k):
+        self._step()
+        self._sample(temperature, top_k)
+
+    def capture(self, temperature: float = 0.8, top_k: Optional[int] = 200):
+        """hipGraph of one step for all B sequences: the forward pass and B sampler launches (each sequence's token, position and
+        draw counter stay on the device).  The warm-up step's state is put back."""
+        key = (float(temperature), int(top_k or 0))
+        if self._graph is not None and self._graph_key == key:
+            return self._graph
+        state = (self.tok_buf.clone(), self.pos_buf.clone(), self.rng_state.clone(), self.history.clone())
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            self._self_step(temperature, top_k)
+        torch.cuda.current_stream().wait_stream(s)
+        g = torch.cuda.CUDAGraph()
+        try:
+            self._restore(state)
+            with runtime.graph_capture(g):
+                self._self_step(temperature, top_k)
+        finally:
+            self._restore(state)
+        self._graph, self._graph_key = g, key
+        return g
+
+    def _restore(self, state):
+        for dst, src in zip((self.tok_buf, self.pos_buf, self.rng_state, self.history), state):
+            dst.copy_(src)
+
+    def manual_seed(self, seed: int):
+        self._seed = int(seed)
+
+    @torch.no_grad()
+    def decode_n(self, first_tokens: torch.Tensor, pos, n: int, temperature: float = 0.8, top_k: Optional[int] = 200,
+                 use_graph: bool = True) -> torch.Tensor:
+        """n steps from first_tokens [B] at positions pos (int or [B]); returns the sampled tokens [B, n] (one read-back at the
+        end).  Sequence b draws from its own stream (seed + b)."""
+        B = self.B
+        pos_t = torch.as_tensor(pos).to(torch.int32).reshape(-1).cpu()
+        pos_t = pos_t.expand(B) if pos_t.numel() == 1 else pos_t
+        assert int(pos_t.max()) + n <= self.max_seq and n <= self.history.shape[1]
+        self.tok_buf[:B].copy_(first_tokens.view(-1).to(torch.int32))
+        self.pos_buf[:B].copy_(pos_t.to(self.pos_buf.device))
+        self.rng_state.copy_(torch.tensor([[self._seed + b, 0] for b in range(B)], dtype=torch.int64))
+        if use_graph:
+            g = self.capture(temperature, top_k)
+            for _ in range(n):
+                g.replay()
+        else:
+            for _ in range(n):
+                self._self_step(temperature, top_k)
+        return self.history[:, :n].clone()
+
+    # ---- reporting --------------------------------------------------------------------------------
+    def kept_fractions(self) -> Dict[str, Dict[str, float]]:
+        """of the last step: per projection, the mean over layers and sequences of the fraction of rows a sequence keeps
+        ("per_seq") and the mean over layers of the fraction the union keeps ("union") — the rows the step read"""
+        c = self.counts.view(len(self.model.layers), len(PROJ_LAUNCHES), 16, 3, 9).cpu()
+        out = {}
+        for j, (_, projs) in enumerate(PROJ_LAUNCHES):
+            Z = self.inter if projs == ("down",) else self.dim
+            for s, proj in enumerate(projs):
+                per, uni = [], []
+                for i in range(len(self.model.layers)):
+                    tot = c[i, j, :self.splits[i][j], s].sum(0)
+                    per.append(tot[:self.B].double().mean().item() / Z)
+                    uni.append(tot[8].item() / Z)
+                out[proj] = {"per_seq": sum(per) / len(per), "union": sum(uni) / len(uni)}
+        return out
+
+    def weight_bytes_per_step(self) -> int:
+        """bytes of weights the last step streamed: every projection's union rows x its row width, plus the dense lm_head"""
+        c = self.counts.view(len(self.model.layers), len(PROJ_LAUNCHES), 16, 3, 9).cpu()
+        es = self.model.output.weight.element_size()
+        widths = {"q": self.dim, "k": self.kv, "v": self.kv, "o": self.dim, "gate": self.inter, "up": self.inter, "down": self.dim}
+        total = 0
+        for i in range(len(self.model.layers)):
+            for j, (_, projs) in enumerate(PROJ_LAUNCHES):
+                for s, proj in enumerate(projs):
+                    total += int(c[i, j, :self.splits[i][j], s, 8].sum()) * widths[proj] * es
+        return total + self.dim * self.cfg.vocab_size * es
+
+    @property
+    def config(self):
+        return self.cfg
+
+    @property
+    def device(self):
+        return self.logits.device

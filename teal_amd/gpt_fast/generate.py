@@ -623,10 +623,95 @@ def run_speculative(args, model: Transformer, thresholds, prompt: torch.Tensor, 
 
 
 # ------------------------------------------------------------------------------------------------
+# ------------------------------------------------------------------------------------------------
+# batched decode (--batch_size B): B sequences per step, each TEAL-masked by its own activations
+# ------------------------------------------------------------------------------------------------
+def check_batched_args(args) -> int:
+    """the batch size; every refusal is raised here, before anything is loaded"""
+    from teal_amd.kernels.sparse_gemv import BATCH_MAX
+    B = int(getattr(args, "batch_size", 1) or 1)
+    if B == 1:
+        return 1
+    if not 1 <= B <= BATCH_MAX:
+        raise SystemExit(f"batched decode: --batch_size must be in 1..{BATCH_MAX}, got {B}")
+    if getattr(args, "draft_checkpoint_path", None) is not None or getattr(args, "self_speculate", False):
+        raise SystemExit("batched decode does not combine with speculative decoding")
+    if int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1"))) > 1:
+        raise SystemExit("batched decode does not run under tensor parallelism")
+    if getattr(args, "interactive", False):
+        raise SystemExit("batched decode does not combine with --interactive")
+    if args.precision not in ("fp16", "bf16") or (not args.synthetic and ("int8" in str(args.checkpoint_path) or "int4" in str(args.checkpoint_path))):
+        raise SystemExit("batched decode needs 16-bit weights (int8 / int4 checkpoints decode one sequence at a time)")
+    return B
+
+
+@torch.no_grad()
+def run_batched(args, model: Transformer, thresholds, prompts: torch.Tensor, tokenizer, use_engine: bool) -> Dict:
+    """prompts [B, T]: a dense prompt pass through the module path at batch B, then max_new_tokens - 1 steps through
+    BatchedDecodeEngine (one hipGraph replay per step under --compile) or the patched ops at batch B"""
+    B, T = prompts.shape
+    dev = prompts.device
+    n_new = args.max_new_tokens
+    max_seq = min(T + n_new, model.config.block_size)
+    n_new = max_seq - T
+    model.setup_caches(max_batch_size=B, max_seq_length=max_seq)
+    eng = None
+    if use_engine:
+        from teal_amd.gpt_fast.batched import BatchedDecodeEngine
+        why = BatchedDecodeEngine.supports(model)
+        if why is None:
+            eng = BatchedDecodeEngine(model, thresholds, B)
+        else:
+            print(f"batched engine not used: {why}")
+    tps, seqs = [], []
+    for i in range(-1 if args.compile else 0, args.num_samples):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        seq = torch.empty(B, T + n_new, dtype=torch.int64, device=dev)
+        seq[:, :T] = prompts
+        logits = model(prompts.long(), torch.arange(0, T, device=dev))  # [B, T, V], dense (the ops' prefill path)
+        first = sample_batch(logits[:, -1], args.temperature, args.top_k)
+        seq[:, T] = first
+        if n_new > 1:
+            if eng is not None:
+                eng.manual_seed(1234 + max(i, 0))
+                seq[:, T + 1:] = eng.decode_n(first, T, n_new - 1, args.temperature, args.top_k, use_graph=bool(args.compile)).long()
+            else:
+                cur, pos = first.view(B, 1), torch.tensor([T], device=dev)
+                for j in range(n_new - 1):
+                    cur = sample_batch(model(cur, pos)[:, -1], args.temperature, args.top_k).view(B, 1)
+                    seq[:, T + 1 + j] = cur.view(B)
+                    pos += 1
+        torch.cuda.synchronize()
+        t = time.perf_counter() - t0
+        if i == -1:
+            print(f"Graph capture + warm-up time: {t:.2f} seconds")
+            continue
+        tps.append(B * n_new / t)
+        seqs.append(seq.tolist())
+        for b in range(B):
+            text = tokenizer.decode(seq[b].tolist()) if tokenizer is not None else seq[b, T:].tolist()
+            print(f"[sample {i + 1}, sequence {b}] {text}")
+        print(f"Time for inference {i + 1}: {t:.02f} sec total, {tps[-1]:.02f} tokens/sec aggregate, "
+              f"{tps[-1] / B:.02f} tokens/sec per sequence (batch {B})")
+    print("==========")
+    mean = sum(tps) / max(1, len(tps))
+    print(f"Average tokens/sec: {mean:.2f} aggregate, {mean / B:.2f} per sequence")
+    print(f"Memory used: {torch.cuda.max_memory_reserved() / 1e9:.02f} GB")
+    return {"tokens_per_sec": tps, "mean_tokens_per_sec": mean, "mean_tokens_per_sec_per_sequence": mean / B, "batch_size": B,
+            "thresholds": thresholds, "decoder": type(eng).__name__ if eng is not None else "module", "sequences": seqs}
+
+
+def sample_batch(logits: torch.Tensor, temperature: float, top_k: Optional[int]) -> torch.Tensor:
+    """one token per row of logits [B, V] (generate.sample's rule, row by row)"""
+    return torch.cat([sample(logits[b:b + 1].unsqueeze(0), temperature=temperature, top_k=top_k)[0].view(1) for b in range(logits.shape[0])])
+
+
 def main(args) -> Dict:
     device = args.device
     assert "cuda" in device, "the sparse decode path is GPU-only (HIP kernels, no CPU fallback)"
     spec = check_speculative_args(args)  # before anything is loaded
+    batch = check_batched_args(args)
     if getattr(args, "interactive", False) and args.synthetic:
         raise SystemExit("--interactive needs a tokenizer (a checkpoint directory), not --synthetic")
     dtype = {"fp16": torch.float16, "bf16": torch.bfloat16}[args.precision]
@@ -669,6 +754,15 @@ def main(args) -> Dict:
     torch.manual_seed(1234)
     if spec is not None:
         return run_speculative(args, model, thresholds, prompt, tokenizer, spec, device, dtype)
+    if batch > 1:
+        if args.synthetic:  # B distinct seeded prompts of equal length
+            prompts = torch.randint(0, model.config.vocab_size, (batch, prompt.numel()), device=device, dtype=torch.int,
+                                    generator=torch.Generator(device=device).manual_seed(7))
+            prompts[0] = prompt
+        else:  # the prompt repeated B times (gpt-fast's batched generate)
+            prompts = prompt.view(1, -1).repeat(batch, 1)
+        use_engine = thresholds is not None and (args.engine or (args.compile and not getattr(args, "no_engine", False)))
+        return run_batched(args, model, thresholds, prompts, tokenizer, use_engine)
     model_size = _get_model_size(model)
     # a hipGraph holds the step only if the ranks' all-reduce can be captured (RCCL); a host-staged gloo reduce decodes eagerly
     # (TEAL_TP_GRAPH=0 keeps a sharded model's decode eager even over RCCL; a capture that fails falls back by itself)
@@ -782,6 +876,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--no_engine", action="store_true", help="with --compile: drive the patched model exactly as the reference "
                    "harness does (model(token, pos) -> torch sampler, captured in a hipGraph) instead of the device-resident "
                    "engine loop; single-token calls still run the fused HIP decode step (Transformer.fused_decode)")
+    p.add_argument("--batch_size", type=int, default=1, help="batched decode: B <= 8 sequences per step (the prompt repeated B "
+                   "times; --synthetic: B seeded prompts); through BatchedDecodeEngine under --compile / --engine")
     p.add_argument("--no_fused_decode", action="store_true", help="op-by-op module path (torch.ops.teal.* + eager glue) for "
                    "single-token calls: A/B against the fused decode step")
     return p

@@ -15,6 +15,8 @@ Differences, all deliberate:
 """
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
 from .. import _lib, runtime
@@ -43,9 +45,60 @@ def _prep(x: torch.Tensor, weight: torch.Tensor):
     return L, x, N, Z, code, ws
 
 
+BATCH_MAX = 8  # sequences per batched launch (teal_batched_sparse_gemm); larger batches run in chunks of 8
+
+
+class BatchedSegs(ctypes.Structure):  # teal_batched_segs_t
+    _fields_ = [("nseg", ctypes.c_int), ("col_end", ctypes.c_int * 3), ("tau", ctypes.c_float * 3)]
+
+
+def batched_segs(bounds, taus) -> BatchedSegs:
+    """threshold segments: exclusive end columns `bounds` (ascending, the last = the launch's width) with one tau each"""
+    sg = BatchedSegs(nseg=len(bounds))
+    for i, (e, t) in enumerate(zip(bounds, taus)):
+        sg.col_end[i], sg.tau[i] = int(e), float(t)
+    return sg
+
+
+def _batched_gemv(x: torch.Tensor, weight: torch.Tensor, bounds, taus, what: str) -> torch.Tensor:
+    """x [B, 1, Z], B > 1, 16-bit: each row is masked against its own activations (TEAL's rule per token) and the batch reads
+    the union of the kept weight rows once per chunk of 8 (teal_batched_sparse_gemm + teal_batched_round_rows)."""
+    L, x, N, Z, code, _ = _prep(x, weight)
+    B, S, _ = x.shape
+    if S != 1:
+        raise RuntimeError(f"{what}: batched decode takes x [B, 1, Z]")
+    if Z % 256 or N % 256:
+        raise RuntimeError(f"{what}: batched decode needs Z and N multiples of 256 (got Z={Z}, N={N})")
+    from ..gpt_fast.prefill import IN_XT, PrefillIn
+    dev = x.device
+    y = torch.empty(B, 1, N, device=dev, dtype=x.dtype)
+    xt = torch.zeros(Z, BATCH_MAX, device=dev, dtype=x.dtype)
+    slabs = torch.empty(16 * N * BATCH_MAX, device=dev, dtype=torch.float32)
+    sg = batched_segs(bounds, taus)
+    split = ctypes.c_int(0)
+    st = runtime.stream_ptr()
+    for b0 in range(0, B, BATCH_MAX):
+        nb = min(BATCH_MAX, B - b0)
+        xt[:, :nb].copy_(x[b0:b0 + nb, 0, :].t())
+        gin = PrefillIn(mode=IN_XT, xt=xt.data_ptr())
+        rc = L.teal_batched_sparse_gemm(ctypes.byref(gin), ctypes.byref(sg), weight.data_ptr(), weight.stride(1), N, None, 0, 0,
+                                        slabs.data_ptr(), slabs.numel() * 4, Z, nb, None, code, ctypes.byref(split), st)
+        _lib.check(rc, f"teal_batched_sparse_gemm ({what})")
+        rc = L.teal_batched_round_rows(slabs.data_ptr(), split.value, N, nb, y[b0:b0 + nb].data_ptr(), code, st)
+        _lib.check(rc, f"teal_batched_round_rows ({what})")
+    return y
+
+
+def _batched(x: torch.Tensor) -> bool:
+    return x.dim() == 3 and x.shape[0] > 1 and x.shape[1] == 1
+
+
 def splitk_sparse_gemv(x: torch.Tensor, weight: torch.Tensor, threshold: float, sparsity_bin: int = 0) -> torch.Tensor:
     """y = sparse(x) @ weight.T for x [1, 1, Z], weight [N, Z] column-major; rows with
-    float32(|x|) <= float32(threshold) are never read from HBM."""
+    float32(|x|) <= float32(threshold) are never read from HBM.  x [B, 1, Z], B > 1: every row masked by its own
+    activations, the union of the kept rows read once per 8 rows (the batched kernel)."""
+    if _batched(x):
+        return _batched_gemv(x, weight, [weight.shape[0]], [threshold], "splitk_sparse_gemv")
     L, x, N, Z, code, ws = _prep(x, weight)
     B, S, _ = x.shape
     if B * S != 1:
@@ -61,7 +114,12 @@ def splitk_sparse_gemv(x: torch.Tensor, weight: torch.Tensor, threshold: float, 
 
 def qkv_gemv(x: torch.Tensor, weight: torch.Tensor, threshold_q: float, threshold_k: float, threshold_v: float,
              sparsity_bin: int, kv_size: int) -> torch.Tensor:
-    """Fused wqkv projection with one threshold per q / k / v column range."""
+    """Fused wqkv projection with one threshold per q / k / v column range (x [B, 1, Z], B > 1: the batched kernel)."""
+    if _batched(x):
+        N = weight.shape[0]
+        if kv_size > 0:
+            return _batched_gemv(x, weight, [N - 2 * kv_size, N - kv_size, N], [threshold_q, threshold_k, threshold_v], "qkv_gemv")
+        return _batched_gemv(x, weight, [N], [threshold_q], "qkv_gemv")
     L, x, N, Z, code, ws = _prep(x, weight)
     B, S, _ = x.shape
     if B * S != 1:
@@ -76,7 +134,9 @@ def qkv_gemv(x: torch.Tensor, weight: torch.Tensor, threshold_q: float, threshol
 
 
 def dense_gemv(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
-    """x @ weight.T at one token with every row kept (same kernel, threshold -inf)."""
+    """x @ weight.T at one token with every row kept (same kernel, threshold -inf; x [B, 1, Z], B > 1: the batched kernel)."""
+    if _batched(x):
+        return _batched_gemv(x, weight, [weight.shape[0]], [float("-inf")], "dense_gemv")
     L, x, N, Z, code, ws = _prep(x, weight)
     B, S, _ = x.shape
     if B * S != 1:
@@ -204,8 +264,8 @@ class SparseGEMV(BaseKernel):
 
     def forward(self, hidden_states: torch.Tensor, weights: torch.Tensor, threshold: float,
                 sparsity_bin: int) -> torch.Tensor:
-        # decode -> HIP sparse GEMV; prefill -> dense matmul (kernels/sparse_gemv.py:271)
-        if hidden_states.shape[1] == 1 and hidden_states.shape[0] == 1:
+        # decode -> HIP sparse GEMV (batched decode: the batched kernel); prefill -> dense matmul (kernels/sparse_gemv.py:271)
+        if hidden_states.shape[1] == 1:
             return splitk_sparse_gemv(hidden_states, weights, threshold, sparsity_bin)
         return torch.matmul(hidden_states, weights.T)
 
@@ -217,7 +277,7 @@ class SparseQKVGEMV(BaseKernel):
 
     def forward(self, x: torch.Tensor, weight: torch.Tensor, threshold_q: float, threshold_k: float,
                 threshold_v: float, sparsity_bin: int, kv_size: int) -> torch.Tensor:
-        if x.shape[1] == 1 and x.shape[0] == 1:
+        if x.shape[1] == 1:
             return qkv_gemv(x, weight, threshold_q, threshold_k, threshold_v, sparsity_bin, kv_size)
         return torch.matmul(x, weight.T)
 
@@ -230,7 +290,7 @@ class DenseGEMV(BaseKernel):
         return x.new_empty(x.shape[0], x.shape[1], W.shape[0])
 
     def forward(self, x: torch.Tensor, W: torch.Tensor, threshold: float, sparsity_bin: int) -> torch.Tensor:
-        if x.shape[1] == 1 and x.shape[0] == 1:
+        if x.shape[1] == 1:
             return dense_gemv(x, W)
         return torch.matmul(x, W.T)
 
