@@ -451,6 +451,45 @@ int teal_batched_decode_attention(const float* qkv_slabs, int split, const void*
                                   void* yt, float* partials, size_t partials_bytes, int B, int n_head, int n_kv_head, int head_dim,
                                   int max_seq, int dtype, void* stream);
 
+/* ---- continuous batching: slots that drop out of the batched step on the device, teal_amd/csrc/teal_batched.hip ------------
+ * A slot is one running request.  The slot state is ONE int32 buffer of TEAL_SLOT_WORDS words per engine, at a fixed address (a
+ * captured step holds it): TEAL_SLOT_ACTIVE (bit b: slot b runs), TEAL_SLOT_STEP (steps retired so far), and per slot b the words
+ * TEAL_SLOT_BUDGET + b (tokens it may still produce), TEAL_SLOT_PRODUCED + b (tokens produced), TEAL_SLOT_EOS + b (EOS id, -1: none)
+ * and TEAL_SLOT_FINISH + b (the step on which it stopped).  The host writes a slot's words between steps (admission) and reads
+ * the whole buffer back in one copy. */
+#define TEAL_SLOT_ACTIVE 0
+#define TEAL_SLOT_STEP 1
+#define TEAL_SLOT_BUDGET 8
+#define TEAL_SLOT_PRODUCED 16
+#define TEAL_SLOT_EOS 24
+#define TEAL_SLOT_FINISH 32
+#define TEAL_SLOT_WORDS 40
+
+/* teal_batched_sparse_gemm with the slots whose bit of active[0] (device int32) is clear left out: read once per workgroup, such a
+ * slot's activation is +0 (whatever its hand-over holds, NaN and Inf included) and never kept, so it adds nothing to the union,
+ * to the kept counts or to any other slot's sums, and its slab columns are exactly 0.  On the active slots the results are
+ * bit-identical to teal_batched_sparse_gemm of the compacted batch. */
+int teal_batched_sparse_gemm_slots(const teal_prefill_in_t* in, const teal_batched_segs_t* segs, const void* w0T, int ld0, int n0,
+                                   const void* w1T, int ld1, int n1, float* slabs, size_t slabs_bytes, int Z, int B, const int32_t* active,
+                                   int32_t* counts, int dtype, int* split_out, void* stream);
+/* teal_batched_decode_attention where the workgroups of a slot whose bit of active[0] is clear exit at once: no cache row written,
+ * no partials, yt slot zero.  Same grid and nsplit as the unmasked launch at the same B (nsplit never depends on the active set). */
+int teal_batched_decode_attention_slots(const float* qkv_slabs, int split, const void* rope, const int32_t* pos, const int32_t* active,
+                                        void* k_cache, void* v_cache, void* yt, float* partials, size_t partials_bytes, int B, int n_head,
+                                        int n_kv_head, int head_dim, int max_seq, int dtype, void* stream);
+/* One launch after the B samplers of a step: every slot b < B that is active and in slot_mask counts its token (tokens[b]), spends
+ * one unit of budget and stops — bit cleared, TEAL_SLOT_FINISH + b = the current step — when tokens[b] is its EOS id, when its
+ * budget is spent, or when its next position pos[b] would be max_seq (pos[b] is then set to max_seq - 1: a slot's position never
+ * passes the cache).  count_step != 0: TEAL_SLOT_STEP += 1 (the decode step; an admission's first draw passes 0). */
+int teal_batched_retire(int32_t* slot_state, const int32_t* tokens, int32_t* pos, int B, int slot_mask, int max_seq, int count_step,
+                        void* stream);
+/* teal_sample_topk_ws predicated on bit `slot` of active[0] (device int32): set, exactly teal_sample_topk_ws; clear, nothing changes —
+ * token, position, rng_state, history and the workspace's ticket and scratch stay as they were (every workgroup of the
+ * multi-workgroup form exits before the ticket). */
+int teal_sample_topk_slot(const void* logits, int vocab, int dtype, int top_k, float temperature, void* rng_state, int32_t* token_out,
+                          int32_t* pos_inout, int32_t* history, int history_len, void* ws, size_t ws_bytes, const int32_t* active, int slot,
+                          void* stream);
+
 /* ---- benchmark comparator (scripts/benchmark_gemv.py only; not on the decode path) ----------- */
 
 /* The Deja Vu gather GEMV the reference's kernel benchmark plots next to TEAL's (scripts/benchmark_gemv.py:32-107,170-172),

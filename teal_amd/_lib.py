@@ -59,7 +59,8 @@ LIB_OVERRIDE = os.environ.get("TEAL_LIB_PATH") or None
 OPTIONAL_WITH_OVERRIDE = ("teal_decode_attention_split_roped", "teal_prefill_gemm", "teal_prefill_resid_norm", "teal_prefill_attention",
                           "teal_verify_attention_ws_bytes", "teal_verify_attention", "teal_spec_accept_scratch_bytes", "teal_spec_accept",
                           "teal_batched_sparse_gemm", "teal_batched_round_rows", "teal_batched_decode_attention_ws_bytes",
-                          "teal_batched_decode_attention")
+                          "teal_batched_decode_attention", "teal_batched_sparse_gemm_slots", "teal_batched_decode_attention_slots",
+                          "teal_batched_retire", "teal_sample_topk_slot")
 
 # every symbol include/teal_hip.h declares
 EXPORTS = (
@@ -71,6 +72,7 @@ EXPORTS = (
     "teal_prefill_gemm", "teal_prefill_resid_norm", "teal_prefill_attention",
     "teal_verify_attention_ws_bytes", "teal_verify_attention", "teal_spec_accept_scratch_bytes", "teal_spec_accept",
     "teal_batched_sparse_gemm", "teal_batched_round_rows", "teal_batched_decode_attention_ws_bytes", "teal_batched_decode_attention",
+    "teal_batched_sparse_gemm_slots", "teal_batched_decode_attention_slots", "teal_batched_retire", "teal_sample_topk_slot",
 )
 
 # what libteal_hip_diag.so exports on top (include/teal_hip.h, #ifdef TEAL_DIAGNOSTICS); libteal_hip.so must export NONE of them
@@ -210,6 +212,11 @@ def _open(path: str, diag: bool) -> ctypes.CDLL:
         L.teal_batched_decode_attention_ws_bytes.argtypes = [ci, ci, ci]
         L.teal_batched_decode_attention_ws_bytes.restype = sz
         L.teal_batched_decode_attention.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, ci, ci, ci, vp]
+    if hasattr(L, "teal_batched_retire"):
+        L.teal_batched_sparse_gemm_slots.argtypes = [vp, vp, vp, ci, ci, vp, ci, ci, vp, sz, ci, ci, vp, vp, ci, ctypes.POINTER(ci), vp]
+        L.teal_batched_decode_attention_slots.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, ci, ci, ci, vp]
+        L.teal_batched_retire.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp]
+        L.teal_sample_topk_slot.argtypes = [vp, ci, ci, ci, cf, vp, vp, vp, vp, ci, vp, sz, vp, ci, vp]
     for name in EXPORTS + (DIAG_EXPORTS if diag else ()):
         if LIB_OVERRIDE and name in OPTIONAL_WITH_OVERRIDE and not hasattr(L, name):
             continue  # an older build loaded for A/B: callers of this entry point fail with AttributeError when they reach it

@@ -1000,6 +1000,21 @@ __global__ __launch_bounds__(1024) void sample_topk_kernel(const uint16_t* __res
     sample_full<BF16>(logits, V, top_k, inv_temp, rng_state, token_out, pos_inout, history, history_len);
 }
 
+// the slot-predicated forms (teal_sample_topk_slot): bit `slot` of active[0] clear -> the whole launch exits before it reads or
+// writes anything else
+__device__ __forceinline__ bool slot_off(const int* __restrict__ active, const int slot) { return !((active[0] >> slot) & 1); }
+
+template <bool BF16>
+__global__ __launch_bounds__(1024) void sample_topk_slot_kernel(const uint16_t* __restrict__ logits, const int V,
+                                                                 const int top_k, const float inv_temp,
+                                                                 unsigned long long* __restrict__ rng_state,
+                                                                 int* __restrict__ token_out, int* __restrict__ pos_inout,
+                                                                 int* __restrict__ history, const int history_len,
+                                                                 const int* __restrict__ active, const int slot) {
+    if (slot_off(active, slot)) return;
+    sample_full<BF16>(logits, V, top_k, inv_temp, rng_state, token_out, pos_inout, history, history_len);
+}
+
 
 // ------------------------------------------------------------------------------------------------
 // Register-resident sampler for vocab % 8 == 0, vocab <= NV * 8192 (Llama-2: NV = 4, Llama-3: NV = 16).
@@ -1017,12 +1032,10 @@ __global__ __launch_bounds__(1024) void sample_topk_kernel(const uint16_t* __res
 //     generic kernel (tests/test_engine.py).
 // ------------------------------------------------------------------------------------------------
 template <bool BF16, int NV>
-__global__ __launch_bounds__(1024) void sample_topk_window_kernel(const uint16_t* __restrict__ logits, const int V,
-                                                                   const int top_k, const float inv_temp,
-                                                                   unsigned long long* __restrict__ rng_state,
-                                                                   int* __restrict__ token_out, int* __restrict__ pos_inout,
-                                                                   int* __restrict__ history, const int history_len,
-                                                                   unsigned long long* __restrict__ phase) {
+__device__ __forceinline__ void sample_window_body(const uint16_t* __restrict__ logits, const int V, const int top_k, const float inv_temp,
+                                                   unsigned long long* __restrict__ rng_state, int* __restrict__ token_out,
+                                                   int* __restrict__ pos_inout, int* __restrict__ history, const int history_len,
+                                                   unsigned long long* __restrict__ phase) {
     auto stamp_s = [&](const int i) { if (phase && threadIdx.x == 0) phase[i] = wall_clock64(); };
     stamp_s(0);
     __shared__ unsigned int hist[256];
@@ -1174,6 +1187,27 @@ __global__ __launch_bounds__(1024) void sample_topk_window_kernel(const uint16_t
     stamp_s(4);
 }
 
+template <bool BF16, int NV>
+__global__ __launch_bounds__(1024) void sample_topk_window_kernel(const uint16_t* __restrict__ logits, const int V,
+                                                                   const int top_k, const float inv_temp,
+                                                                   unsigned long long* __restrict__ rng_state,
+                                                                   int* __restrict__ token_out, int* __restrict__ pos_inout,
+                                                                   int* __restrict__ history, const int history_len,
+                                                                   unsigned long long* __restrict__ phase) {
+    sample_window_body<BF16, NV>(logits, V, top_k, inv_temp, rng_state, token_out, pos_inout, history, history_len, phase);
+}
+
+template <bool BF16, int NV>
+__global__ __launch_bounds__(1024) void sample_topk_window_slot_kernel(const uint16_t* __restrict__ logits, const int V,
+                                                                        const int top_k, const float inv_temp,
+                                                                        unsigned long long* __restrict__ rng_state,
+                                                                        int* __restrict__ token_out, int* __restrict__ pos_inout,
+                                                                        int* __restrict__ history, const int history_len,
+                                                                        const int* __restrict__ active, const int slot) {
+    if (slot_off(active, slot)) return;
+    sample_window_body<BF16, NV>(logits, V, top_k, inv_temp, rng_state, token_out, pos_inout, history, history_len, nullptr);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Multi-workgroup sampler (vocab % 8 == 0, vocab <= 16 x 8192, 0 < top_k < vocab): the single workgroup above spends
 // its time in NV sequential passes over its registers (14 us at 32 k, 37 us at 128 k logits).  Here workgroup g owns
@@ -1274,12 +1308,10 @@ __device__ __forceinline__ uint32_t block_max_u32(uint32_t v, int* ired, const i
 }
 
 template <bool BF16>
-__global__ __launch_bounds__(1024) void sample_topk_multi_kernel(const uint16_t* __restrict__ logits, const int V,
-                                                                  const int top_k, const float inv_temp,
-                                                                  unsigned long long* __restrict__ rng_state,
-                                                                  int* __restrict__ token_out, int* __restrict__ pos_inout,
-                                                                  int* __restrict__ history, const int history_len,
-                                                                  unsigned char* __restrict__ slot) {
+__device__ __forceinline__ void sample_multi_body(const uint16_t* __restrict__ logits, const int V, const int top_k, const float inv_temp,
+                                                  unsigned long long* __restrict__ rng_state, int* __restrict__ token_out,
+                                                  int* __restrict__ pos_inout, int* __restrict__ history, const int history_len,
+                                                  unsigned char* __restrict__ slot) {
     __shared__ unsigned int hist[256];
     __shared__ unsigned int whist[16][256];
     __shared__ float fred[16];
@@ -1402,6 +1434,29 @@ __global__ __launch_bounds__(1024) void sample_topk_multi_kernel(const uint16_t*
         rng_state[1] = ctr64 + 1ull;
         if (pos_inout) pos_inout[0] = pos0 + 1;
     }
+}
+
+template <bool BF16>
+__global__ __launch_bounds__(1024) void sample_topk_multi_kernel(const uint16_t* __restrict__ logits, const int V,
+                                                                  const int top_k, const float inv_temp,
+                                                                  unsigned long long* __restrict__ rng_state,
+                                                                  int* __restrict__ token_out, int* __restrict__ pos_inout,
+                                                                  int* __restrict__ history, const int history_len,
+                                                                  unsigned char* __restrict__ slot) {
+    sample_multi_body<BF16>(logits, V, top_k, inv_temp, rng_state, token_out, pos_inout, history, history_len, slot);
+}
+
+// every workgroup reads the same word and takes the same exit decision, before the ticket
+template <bool BF16>
+__global__ __launch_bounds__(1024) void sample_topk_multi_slot_kernel(const uint16_t* __restrict__ logits, const int V,
+                                                                       const int top_k, const float inv_temp,
+                                                                       unsigned long long* __restrict__ rng_state,
+                                                                       int* __restrict__ token_out, int* __restrict__ pos_inout,
+                                                                       int* __restrict__ history, const int history_len,
+                                                                       unsigned char* __restrict__ scratch, const int* __restrict__ active,
+                                                                       const int slot) {
+    if (slot_off(active, slot)) return;
+    sample_multi_body<BF16>(logits, V, top_k, inv_temp, rng_state, token_out, pos_inout, history, history_len, scratch);
 }
 
 constexpr int kGqaMinSeq8 = 2048;           // cache length from which 8-heads-per-KV-head models take the grouped kernel
@@ -1583,9 +1638,13 @@ int teal_sample_topk(const void* logits, int vocab, int dtype, int top_k, float 
                                nullptr, 0, stream);
 }
 
-int teal_sample_topk_ws(const void* logits, int vocab, int dtype, int top_k, float temperature, void* rng_state,
-                        int32_t* token_out, int32_t* pos_inout, int32_t* history, int history_len, void* ws, size_t ws_bytes,
-                        void* stream) {
+}  // extern "C"
+
+namespace {
+// teal_sample_topk_ws (active == nullptr) and teal_sample_topk_slot: the same kernel choice, the slot forms of the same kernels
+int sample_launch(const void* logits, int vocab, int dtype, int top_k, float temperature, void* rng_state, int32_t* token_out,
+                  int32_t* pos_inout, int32_t* history, int history_len, void* ws, size_t ws_bytes, const int32_t* active, int slot_id,
+                  void* stream) {
     if (!logits || !rng_state || !token_out || vocab <= 0) return TEAL_ERR_ARG;
     if (dtype != TEAL_F16 && dtype != TEAL_BF16) return TEAL_ERR_DTYPE;
     if (!aligned16(logits)) return TEAL_ERR_ALIGN;
@@ -1595,23 +1654,51 @@ int teal_sample_topk_ws(const void* logits, int vocab, int dtype, int top_k, flo
     auto* rs = reinterpret_cast<unsigned long long*>(rng_state);
 #define TEAL_SAMPLE(KERNEL) hipLaunchKernelGGL((KERNEL), dim3(1), dim3(1024), 0, st, lg, vocab, top_k, inv_temp, rs, token_out, pos_inout, history, history_len)
 #define TEAL_SAMPLE_W(KERNEL) hipLaunchKernelGGL((KERNEL), dim3(1), dim3(1024), 0, st, lg, vocab, top_k, inv_temp, rs, token_out, pos_inout, history, history_len, phase_start_only())
+#define TEAL_SAMPLE_S(KERNEL) hipLaunchKernelGGL((KERNEL), dim3(1), dim3(1024), 0, st, lg, vocab, top_k, inv_temp, rs, token_out, pos_inout, history, history_len, active, slot_id)
     const bool bf = dtype == TEAL_BF16;
     if ((vocab & 7) == 0 && vocab > 8192 && vocab <= kSampMaxGroups * 8192 && top_k > 0 && top_k < vocab && ws_prepared(ws, ws_bytes)) {
         // one workgroup per 8192 logits + the last arriver (sample_topk_multi_kernel)
         unsigned char* slot = ws_sampler(ws);  // scratch of the caller's prepared workspace (one per stream)
         const dim3 grid((vocab / 8 + 1023) / 1024), block(1024);
-        if (bf) hipLaunchKernelGGL((sample_topk_multi_kernel<true>), grid, block, 0, st, lg, vocab, top_k, inv_temp, rs, token_out, pos_inout, history, history_len, slot);
-        else hipLaunchKernelGGL((sample_topk_multi_kernel<false>), grid, block, 0, st, lg, vocab, top_k, inv_temp, rs, token_out, pos_inout, history, history_len, slot);
+        if (active) {
+            if (bf) hipLaunchKernelGGL((sample_topk_multi_slot_kernel<true>), grid, block, 0, st, lg, vocab, top_k, inv_temp, rs, token_out, pos_inout, history, history_len, slot, active, slot_id);
+            else hipLaunchKernelGGL((sample_topk_multi_slot_kernel<false>), grid, block, 0, st, lg, vocab, top_k, inv_temp, rs, token_out, pos_inout, history, history_len, slot, active, slot_id);
+        } else {
+            if (bf) hipLaunchKernelGGL((sample_topk_multi_kernel<true>), grid, block, 0, st, lg, vocab, top_k, inv_temp, rs, token_out, pos_inout, history, history_len, slot);
+            else hipLaunchKernelGGL((sample_topk_multi_kernel<false>), grid, block, 0, st, lg, vocab, top_k, inv_temp, rs, token_out, pos_inout, history, history_len, slot);
+        }
     } else if ((vocab & 7) == 0 && vocab <= 4 * 8192) {  // register-resident keys, window select: 4 vectors per thread
-        if (bf) TEAL_SAMPLE_W((sample_topk_window_kernel<true, 4>)); else TEAL_SAMPLE_W((sample_topk_window_kernel<false, 4>));
+        if (active) { if (bf) TEAL_SAMPLE_S((sample_topk_window_slot_kernel<true, 4>)); else TEAL_SAMPLE_S((sample_topk_window_slot_kernel<false, 4>)); }
+        else if (bf) TEAL_SAMPLE_W((sample_topk_window_kernel<true, 4>)); else TEAL_SAMPLE_W((sample_topk_window_kernel<false, 4>));
     } else if ((vocab & 7) == 0 && vocab <= 16 * 8192) {  // 16 vectors per thread (Llama-3's 128256)
-        if (bf) TEAL_SAMPLE_W((sample_topk_window_kernel<true, 16>)); else TEAL_SAMPLE_W((sample_topk_window_kernel<false, 16>));
+        if (active) { if (bf) TEAL_SAMPLE_S((sample_topk_window_slot_kernel<true, 16>)); else TEAL_SAMPLE_S((sample_topk_window_slot_kernel<false, 16>)); }
+        else if (bf) TEAL_SAMPLE_W((sample_topk_window_kernel<true, 16>)); else TEAL_SAMPLE_W((sample_topk_window_kernel<false, 16>));
     } else {  // any size: two full radix passes over memory
-        if (bf) TEAL_SAMPLE((sample_topk_kernel<true>)); else TEAL_SAMPLE((sample_topk_kernel<false>));
+        if (active) { if (bf) TEAL_SAMPLE_S((sample_topk_slot_kernel<true>)); else TEAL_SAMPLE_S((sample_topk_slot_kernel<false>)); }
+        else if (bf) TEAL_SAMPLE((sample_topk_kernel<true>)); else TEAL_SAMPLE((sample_topk_kernel<false>));
     }
 #undef TEAL_SAMPLE
 #undef TEAL_SAMPLE_W
+#undef TEAL_SAMPLE_S
     return hipGetLastError() == hipSuccess ? TEAL_OK : TEAL_ERR_LAUNCH;
+}
+}  // namespace
+
+extern "C" {
+
+int teal_sample_topk_ws(const void* logits, int vocab, int dtype, int top_k, float temperature, void* rng_state,
+                        int32_t* token_out, int32_t* pos_inout, int32_t* history, int history_len, void* ws, size_t ws_bytes,
+                        void* stream) {
+    return sample_launch(logits, vocab, dtype, top_k, temperature, rng_state, token_out, pos_inout, history, history_len, ws, ws_bytes,
+                         nullptr, 0, stream);
+}
+
+int teal_sample_topk_slot(const void* logits, int vocab, int dtype, int top_k, float temperature, void* rng_state, int32_t* token_out,
+                          int32_t* pos_inout, int32_t* history, int history_len, void* ws, size_t ws_bytes, const int32_t* active, int slot,
+                          void* stream) {
+    if (!active || slot < 0 || slot > 31) return TEAL_ERR_ARG;
+    return sample_launch(logits, vocab, dtype, top_k, temperature, rng_state, token_out, pos_inout, history, history_len, ws, ws_bytes,
+                         active, slot, stream);
 }
 
 

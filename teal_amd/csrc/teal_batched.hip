@@ -90,10 +90,14 @@ __device__ __forceinline__ void b_unpack_row(const u32x4 v, float (&x)[8]) {
 // counts (optional): the first tile of each segment also writes, per slice, how many of the slice's rows each sequence keeps and
 // how many the union holds under that segment's threshold.
 // ------------------------------------------------------------------------------------------------
-template <bool BF16, int NP, int PROD>
+// SLOTS: `active` (device int32, bit b = slot b runs) is read once per workgroup; an inactive slot's activation is +0 and never
+// kept, so it adds nothing to the union, the counts or any slab (its own columns are exactly 0).  SLOTS = false is the code of
+// teal_batched_sparse_gemm.
+template <bool BF16, int NP, int PROD, bool SLOTS>
 __global__ __launch_bounds__(1024) void batched_gemm_kernel(const BProd pr, const BSegs sg, const uint16_t* __restrict__ w0, const int ld0,
                                                             const uint16_t* __restrict__ w1, const int ld1, const int tiles0,
-                                                            float* __restrict__ slabs, int* __restrict__ counts, const int Z, const int n_total) {
+                                                            float* __restrict__ slabs, int* __restrict__ counts, const int Z, const int n_total,
+                                                            const int* __restrict__ active) {
     constexpr int WAVES = 16, CPL = 4, BN = 256, U = NP <= 2 ? 8 : 4, PHASE_GROUPS = kBPhaseRows / 16;
     extern __shared__ __align__(16) unsigned char smem[];
     u32x4* xs = reinterpret_cast<u32x4*>(smem);                                     // [kBPhaseRows] activations of the phase's rows
@@ -131,6 +135,8 @@ __global__ __launch_bounds__(1024) void batched_gemm_kernel(const BProd pr, cons
     int* mycnt = wcnt + wave * 3 * kBCountStride;  // this wave's counts, kept in LDS (registers are the streaming loop's)
     if (count_segs && lane < 3 * kBCountStride) mycnt[lane] = 0;
 
+    uint32_t on = 0xFFu;  // slots that run
+    if constexpr (SLOTS) on = (uint32_t)__builtin_amdgcn_readfirstlane(active[0]) & 0xFFu;
     const int ngroups = Z >> 4;
     const int nj = (ngroups - slice + split - 1) / split;  // row groups of this slice
     const uint16_t* wbase = (second ? w1 : w0) + (size_t)(second ? tile - tiles0 : tile) * BN;
@@ -197,10 +203,18 @@ __global__ __launch_bounds__(1024) void batched_gemm_kernel(const BProd pr, cons
             uint32_t mk = 0;
 #pragma unroll
             for (int s = 0; s < 8; ++s) {
-                x[s] = s < pr.B ? x[s] : 0.0f;  // slots of absent sequences: zero, never kept
+                if constexpr (SLOTS) {
+                    const bool live = s < pr.B && ((on >> s) & 1u);
+                    x[s] = live ? x[s] : 0.0f;  // slots of absent or inactive sequences: zero, never kept
 #pragma unroll
-                for (int i = 0; i < 3; ++i)
-                    if (i < nls && s < pr.B && keep_rule(x[s], tau[i])) mk |= 1u << (8 * i + s);
+                    for (int i = 0; i < 3; ++i)
+                        if (i < nls && live && keep_rule(x[s], tau[i])) mk |= 1u << (8 * i + s);
+                } else {
+                    x[s] = s < pr.B ? x[s] : 0.0f;  // slots of absent sequences: zero, never kept
+#pragma unroll
+                    for (int i = 0; i < 3; ++i)
+                        if (i < nls && s < pr.B && keep_rule(x[s], tau[i])) mk |= 1u << (8 * i + s);
+                }
             }
             xs[r] = b_pack_row<BF16>(x);
             msk[r] = mk;
@@ -343,13 +357,14 @@ __global__ __launch_bounds__(256) void batched_round_rows_kernel(const float* __
 // that needs it and read from LDS; split 0 of group 0 stores it to the cache for LATER launches.  Context rows in chunks of 32,
 // chunk c to split c mod nsplit; each workgroup leaves {m, l, o[hd]} per (head, sequence), merged in split order.
 // ------------------------------------------------------------------------------------------------
-template <bool BF16, int HD>
+// SLOTS: a workgroup of a slot whose `active` bit is clear exits before anything else (no cache row, no partials).
+template <bool BF16, int HD, bool SLOTS>
 __global__ __launch_bounds__(256) void batched_attention_kernel(const float* __restrict__ slabs, const int split,
                                                                 const int* __restrict__ pos_ptr, const uint16_t* __restrict__ rope,
                                                                 uint16_t* __restrict__ k_cache, uint16_t* __restrict__ v_cache,
                                                                 float* __restrict__ partials, const int B, const int n_head,
                                                                 const int n_kv, const int hq, const int groups, const int max_seq,
-                                                                const float scale) {
+                                                                const float scale, const int* __restrict__ active) {
     constexpr int C = kBAttnChunk, NT = 256, OJ = (kBAttnMaxQ * HD + NT - 1) / NT, QSTEP = NT / HD;
     __shared__ float qs[kBAttnMaxQ][HD + 1];
     __shared__ float kn[HD], vn[HD];
@@ -359,6 +374,9 @@ __global__ __launch_bounds__(256) void batched_attention_kernel(const float* __r
     __shared__ float mrow[kBAttnMaxQ], lrow[kBAttnMaxQ], alph[kBAttnMaxQ];
     const int tid = threadIdx.x, sp = blockIdx.x, nsplit = gridDim.x, kvh = blockIdx.y;
     const int b = blockIdx.z / groups, grp = blockIdx.z % groups;
+    if constexpr (SLOTS) {
+        if (!((active[0] >> b) & 1)) return;  // workgroup-uniform
+    }
     const int rep = n_head / n_kv, h0 = kvh * rep + grp * hq, NQ = hq;
     const int p = min(max(pos_ptr[b], 0), max_seq - 1);  // (a position past the cache is clamped into it)
     const int ctx = p + 1;
@@ -487,13 +505,14 @@ __global__ __launch_bounds__(256) void batched_attention_kernel(const float* __r
 }
 
 // yt[(h * hd + d) * 8 + b] = round(sum_s o_s e^(m_s - M) / sum_s l_s e^(m_s - M)), splits in order; slots b >= B are zero
-template <bool BF16>
+// (SLOTS: so are the slots whose `active` bit is clear)
+template <bool BF16, bool SLOTS>
 __global__ __launch_bounds__(128) void batched_merge_kernel(const float* __restrict__ partials, uint16_t* __restrict__ yt, const int B,
-                                                            const int hd, const int nsplit) {
+                                                            const int hd, const int nsplit, const int* __restrict__ active) {
     const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
     if (d >= hd) return;
     uint16_t* y = yt + ((size_t)h * hd + d) * 8 + b;
-    if (b >= B) { *y = 0; return; }
+    if (b >= B || (SLOTS && !((active[0] >> b) & 1))) { *y = 0; return; }
     const float* p = partials + ((size_t)h * B + b) * nsplit * (hd + 2);
     float M = -INFINITY;
     for (int s = 0; s < nsplit; ++s) M = fmaxf(M, p[(size_t)s * (hd + 2)]);
@@ -510,16 +529,47 @@ __global__ __launch_bounds__(128) void batched_merge_kernel(const float* __restr
     *y = float_to_bits<BF16>(O / L);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Retirement after the B samplers of one step (or after the first draw of an admission): thread b serves slot b.  An active
+// slot in `mask` counts its token, spends one unit of budget, and stops — its bit cleared, the step recorded — on its EOS id,
+// on an empty budget, or when its next position would be max_seq (that position is pulled back to max_seq - 1: no later
+// launch may address a row past the cache).  Every field is written by plain vector stores; the active mask is assembled with
+// a ballot and written by lane 0.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void batched_retire_kernel(int* __restrict__ st, const int* __restrict__ tokens, int* __restrict__ pos,
+                                                            const int B, const uint32_t mask, const int max_seq, const int count_step) {
+    const int b = threadIdx.x;
+    const uint32_t act = (uint32_t)st[TEAL_SLOT_ACTIVE];
+    const int step = st[TEAL_SLOT_STEP];
+    const bool mine = b < B && ((mask >> b) & 1u) && ((act >> b) & 1u);
+    bool stop = false;
+    if (mine) {
+        const int budget = st[TEAL_SLOT_BUDGET + b] - 1, eos = st[TEAL_SLOT_EOS + b], p = pos[b];
+        stop = budget <= 0 || (eos >= 0 && tokens[b] == eos) || p >= max_seq;
+        st[TEAL_SLOT_BUDGET + b] = budget;
+        st[TEAL_SLOT_PRODUCED + b] = st[TEAL_SLOT_PRODUCED + b] + 1;
+        if (stop) {
+            st[TEAL_SLOT_FINISH + b] = step;
+            if (p > max_seq - 1) pos[b] = max_seq - 1;
+        }
+    }
+    const uint32_t stopped = (uint32_t)__ballot(stop);
+    if (b == 0) {
+        st[TEAL_SLOT_ACTIVE] = (int)(act & ~stopped);
+        if (count_step) st[TEAL_SLOT_STEP] = step + 1;
+    }
+}
+
 }  // namespace
 }  // namespace teal
 
 using namespace teal;
 
-extern "C" {
-
-int teal_batched_sparse_gemm(const teal_prefill_in_t* in, const teal_batched_segs_t* segs, const void* w0T, int ld0, int n0, const void* w1T,
-                             int ld1, int n1, float* slabs, size_t slabs_bytes, int Z, int B, int32_t* counts, int dtype, int* split_out,
-                             void* stream) {
+namespace {
+// teal_batched_sparse_gemm (active == nullptr) and teal_batched_sparse_gemm_slots
+int batched_gemm_launch(const teal_prefill_in_t* in, const teal_batched_segs_t* segs, const void* w0T, int ld0, int n0, const void* w1T,
+                        int ld1, int n1, float* slabs, size_t slabs_bytes, int Z, int B, const int32_t* active, int32_t* counts, int dtype,
+                        int* split_out, void* stream) {
     if (!in || !segs || !w0T || !slabs || !split_out || Z <= 0 || n0 <= 0 || n1 < 0 || (n1 > 0 && !w1T)) return TEAL_ERR_ARG;
     if (dtype != TEAL_F16 && dtype != TEAL_BF16) return TEAL_ERR_DTYPE;
     if (B < 1 || B > kBatchMax || (Z & 255) || Z > 65536 || (ld0 & 7) || (ld1 & 7) || ld0 < n0 || (n1 > 0 && ld1 < n1)) return TEAL_ERR_SHAPE;
@@ -579,7 +629,10 @@ int teal_batched_sparse_gemm(const teal_prefill_in_t* in, const teal_batched_seg
     auto* a = reinterpret_cast<const uint16_t*>(w0T);
     auto* b = reinterpret_cast<const uint16_t*>(w1T);
     int* cnt = reinterpret_cast<int*>(counts);
-#define TEAL_BG(BF, NPV, PR) hipLaunchKernelGGL((batched_gemm_kernel<BF, NPV, PR>), grid, block, lds, st, pr, sg, a, ld0, b, ld1, tiles0, slabs, cnt, Z, ntot)
+#define TEAL_BG(BF, NPV, PR) do { if (active) hipLaunchKernelGGL((batched_gemm_kernel<BF, NPV, PR, true>), grid, block, lds, st, pr, sg, a, ld0, b, \
+        ld1, tiles0, slabs, cnt, Z, ntot, active); \
+    else hipLaunchKernelGGL((batched_gemm_kernel<BF, NPV, PR, false>), grid, block, lds, st, pr, sg, a, ld0, b, ld1, tiles0, slabs, cnt, Z, ntot, \
+                            nullptr); } while (0)
 #define TEAL_BG_PR(BF, NPV) do { if (in->mode == TEAL_PREFILL_IN_NORM) TEAL_BG(BF, NPV, 1); else if (in->mode == TEAL_PREFILL_IN_SILU_MUL) TEAL_BG(BF, NPV, 2); else TEAL_BG(BF, NPV, 0); } while (0)
 #define TEAL_BG_NP(BF) do { switch (np) { case 1: TEAL_BG_PR(BF, 1); break; case 2: TEAL_BG_PR(BF, 2); break; case 3: TEAL_BG_PR(BF, 3); break; \
     default: TEAL_BG_PR(BF, 4); } } while (0)
@@ -589,6 +642,22 @@ int teal_batched_sparse_gemm(const teal_prefill_in_t* in, const teal_batched_seg
 #undef TEAL_BG
     *split_out = split;
     return hipGetLastError() == hipSuccess ? TEAL_OK : TEAL_ERR_LAUNCH;
+}
+}  // namespace
+
+extern "C" {
+
+int teal_batched_sparse_gemm(const teal_prefill_in_t* in, const teal_batched_segs_t* segs, const void* w0T, int ld0, int n0, const void* w1T,
+                             int ld1, int n1, float* slabs, size_t slabs_bytes, int Z, int B, int32_t* counts, int dtype, int* split_out,
+                             void* stream) {
+    return batched_gemm_launch(in, segs, w0T, ld0, n0, w1T, ld1, n1, slabs, slabs_bytes, Z, B, nullptr, counts, dtype, split_out, stream);
+}
+
+int teal_batched_sparse_gemm_slots(const teal_prefill_in_t* in, const teal_batched_segs_t* segs, const void* w0T, int ld0, int n0,
+                                   const void* w1T, int ld1, int n1, float* slabs, size_t slabs_bytes, int Z, int B, const int32_t* active,
+                                   int32_t* counts, int dtype, int* split_out, void* stream) {
+    if (!active) return TEAL_ERR_ARG;
+    return batched_gemm_launch(in, segs, w0T, ld0, n0, w1T, ld1, n1, slabs, slabs_bytes, Z, B, active, counts, dtype, split_out, stream);
 }
 
 int teal_batched_round_rows(const float* slabs, int split, int N, int B, void* y, int dtype, void* stream) {
@@ -608,9 +677,13 @@ size_t teal_batched_decode_attention_ws_bytes(int B, int n_head, int head_dim) {
     return (size_t)n_head * (B < 1 ? 1 : B) * kBAttnMaxSplit * (head_dim + 2) * sizeof(float);
 }
 
-int teal_batched_decode_attention(const float* qkv_slabs, int split, const void* rope, const int32_t* pos, void* k_cache, void* v_cache,
-                                  void* yt, float* partials, size_t partials_bytes, int B, int n_head, int n_kv_head, int head_dim,
-                                  int max_seq, int dtype, void* stream) {
+}  // extern "C"
+
+namespace {
+// teal_batched_decode_attention (active == nullptr) and teal_batched_decode_attention_slots: the same grid and nsplit either way
+int batched_attention_launch(const float* qkv_slabs, int split, const void* rope, const int32_t* pos, const int32_t* active, void* k_cache,
+                             void* v_cache, void* yt, float* partials, size_t partials_bytes, int B, int n_head, int n_kv_head, int head_dim,
+                             int max_seq, int dtype, void* stream) {
     if (!qkv_slabs || !rope || !pos || !k_cache || !v_cache || !yt || !partials || split < 1 || split > kBMaxSplit) return TEAL_ERR_ARG;
     if (dtype != TEAL_F16 && dtype != TEAL_BF16) return TEAL_ERR_DTYPE;
     if ((head_dim != 64 && head_dim != 128) || n_head <= 0 || n_kv_head <= 0 || n_head % n_kv_head || B < 1 || B > kBatchMax || max_seq < 1)
@@ -638,12 +711,48 @@ int teal_batched_decode_attention(const float* qkv_slabs, int split, const void*
     auto* vc = reinterpret_cast<uint16_t*>(v_cache);
     auto* y = reinterpret_cast<uint16_t*>(yt);
 #define TEAL_BA(BF, HDV) do { \
-        hipLaunchKernelGGL((batched_attention_kernel<BF, HDV>), grid, dim3(256), 0, st, qkv_slabs, split, pos, rp, kc, vc, partials, B, \
-                           n_head, n_kv_head, hq, groups, max_seq, scale); \
-        hipLaunchKernelGGL((batched_merge_kernel<BF>), dim3(n_head, kBatchMax), dim3(128), 0, st, partials, y, B, head_dim, nsplit); } while (0)
+        if (active) { \
+            hipLaunchKernelGGL((batched_attention_kernel<BF, HDV, true>), grid, dim3(256), 0, st, qkv_slabs, split, pos, rp, kc, vc, partials, \
+                               B, n_head, n_kv_head, hq, groups, max_seq, scale, active); \
+            hipLaunchKernelGGL((batched_merge_kernel<BF, true>), dim3(n_head, kBatchMax), dim3(128), 0, st, partials, y, B, head_dim, nsplit, \
+                               active); \
+        } else { \
+            hipLaunchKernelGGL((batched_attention_kernel<BF, HDV, false>), grid, dim3(256), 0, st, qkv_slabs, split, pos, rp, kc, vc, partials, \
+                               B, n_head, n_kv_head, hq, groups, max_seq, scale, nullptr); \
+            hipLaunchKernelGGL((batched_merge_kernel<BF, false>), dim3(n_head, kBatchMax), dim3(128), 0, st, partials, y, B, head_dim, nsplit, \
+                               nullptr); \
+        } } while (0)
     if (dtype == TEAL_BF16) { if (head_dim == 128) TEAL_BA(true, 128); else TEAL_BA(true, 64); }
     else { if (head_dim == 128) TEAL_BA(false, 128); else TEAL_BA(false, 64); }
 #undef TEAL_BA
+    return hipGetLastError() == hipSuccess ? TEAL_OK : TEAL_ERR_LAUNCH;
+}
+}  // namespace
+
+extern "C" {
+
+int teal_batched_decode_attention(const float* qkv_slabs, int split, const void* rope, const int32_t* pos, void* k_cache, void* v_cache,
+                                  void* yt, float* partials, size_t partials_bytes, int B, int n_head, int n_kv_head, int head_dim,
+                                  int max_seq, int dtype, void* stream) {
+    return batched_attention_launch(qkv_slabs, split, rope, pos, nullptr, k_cache, v_cache, yt, partials, partials_bytes, B, n_head,
+                                    n_kv_head, head_dim, max_seq, dtype, stream);
+}
+
+int teal_batched_decode_attention_slots(const float* qkv_slabs, int split, const void* rope, const int32_t* pos, const int32_t* active,
+                                        void* k_cache, void* v_cache, void* yt, float* partials, size_t partials_bytes, int B, int n_head,
+                                        int n_kv_head, int head_dim, int max_seq, int dtype, void* stream) {
+    if (!active) return TEAL_ERR_ARG;
+    return batched_attention_launch(qkv_slabs, split, rope, pos, active, k_cache, v_cache, yt, partials, partials_bytes, B, n_head,
+                                    n_kv_head, head_dim, max_seq, dtype, stream);
+}
+
+int teal_batched_retire(int32_t* slot_state, const int32_t* tokens, int32_t* pos, int B, int slot_mask, int max_seq, int count_step,
+                        void* stream) {
+    if (!slot_state || !tokens || !pos || max_seq < 1) return TEAL_ERR_ARG;
+    if (B < 1 || B > kBatchMax) return TEAL_ERR_SHAPE;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(batched_retire_kernel, dim3(1), dim3(64), 0, st, slot_state, tokens, pos, B, (uint32_t)slot_mask & 0xFFu, max_seq,
+                       count_step ? 1 : 0);
     return hipGetLastError() == hipSuccess ? TEAL_OK : TEAL_ERR_LAUNCH;
 }
 

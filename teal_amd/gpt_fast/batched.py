@@ -26,7 +26,7 @@ from .. import _lib, runtime
 from ..kernels.sparse_gemv import BATCH_MAX, batched_segs
 from ..monkeypatch import UP_SHIFT_BYTES, to_column_major
 from .model import Transformer
-from .prefill import IN_NORM, IN_SILU_MUL, IN_XT, PrefillIn
+from .prefill import IN_NORM, IN_SILU_MUL, IN_XT, MAX_T, PrefillEngine, PrefillIn
 
 PROJ_LAUNCHES = (("qkv", ("q", "k", "v")), ("o", ("o",)), ("gateup", ("gate", "up")), ("down", ("down",)))
 NINF = float("-inf")
@@ -142,6 +142,15 @@ class BatchedDecodeEngine:
             _lib.check(rc, "teal_batched_sparse_gemm")
         return self._split.value
 
+    def _attention(self, at, A: torch.Tensor, ns: int, st):
+        cfg = self.cfg
+        kc, vc = at.kv_cache.k_cache, at.kv_cache.v_cache
+        rc = self.L.teal_batched_decode_attention(A.data_ptr(), ns, self.rope.data_ptr(), self.pos_buf.data_ptr(), kc.data_ptr(), vc.data_ptr(),
+                                                  self.yt.data_ptr(), self.partials.data_ptr(), self.partials.numel() * 4, self.B, cfg.n_head,
+                                                  cfg.n_local_heads, cfg.head_dim, self.max_seq, self.code, st)
+        if rc != 0:
+            _lib.check(rc, "teal_batched_decode_attention")
+
     def _resid(self, tokens: bool, slabs: Optional[torch.Tensor], split: int, st):
         m = self.model
         rc = self.L.teal_prefill_resid_norm(m.tok_embeddings.weight.data_ptr() if tokens else None,
@@ -163,12 +172,7 @@ class BatchedDecodeEngine:
             at, ff, sg, cnt = layer.attention, layer.feed_forward, self._segs[i], self.counts[i]
             sp = self.splits[i]
             sp[0] = ns = self._gemm(self._norm_in(layer.attention_norm.weight), sg["qkv"], at.wqkv, None, self.dim, A, cnt[0], st)
-            kc, vc = at.kv_cache.k_cache, at.kv_cache.v_cache
-            rc = L.teal_batched_decode_attention(A.data_ptr(), ns, self.rope.data_ptr(), self.pos_buf.data_ptr(), kc.data_ptr(), vc.data_ptr(),
-                                                 self.yt.data_ptr(), self.partials.data_ptr(), self.partials.numel() * 4, self.B, cfg.n_head,
-                                                 cfg.n_local_heads, cfg.head_dim, self.max_seq, self.code, st)
-            if rc != 0:
-                _lib.check(rc, "teal_batched_decode_attention")
+            self._attention(at, A, ns, st)
             sp[1] = ns = self._gemm(PrefillIn(mode=IN_XT, xt=self.yt.data_ptr()), sg["o"], at.wo, None, self.dim, Bs, cnt[1], st)
             self._resid(False, Bs, ns, st)
             sp[2] = ns = self._gemm(self._norm_in(layer.ffn_norm.weight), sg["gateup"], ff.w1, ff.w3, self.dim, A, cnt[2], st)
@@ -291,3 +295,204 @@ class BatchedDecodeEngine:
     @property
     def device(self):
         return self.logits.device
+
+
+# ---- continuous batching: slots that drop out of the step on the device ---------------------------------------------------
+# The slot state (include/teal_hip.h, TEAL_SLOT_*): one int32 buffer per engine, word offsets below.
+SLOT_ACTIVE, SLOT_STEP, SLOT_BUDGET, SLOT_PRODUCED, SLOT_EOS, SLOT_FINISH, SLOT_WORDS = 0, 1, 8, 16, 24, 32, 40
+
+
+class _SlotCacheView(torch.nn.Module):
+    """slot s of a [B, n_kv, max_seq, hd] KVCache as a batch-1 cache: KVCache.update writes through the view into slot s only (a
+    batch-1 update of the batch-B cache itself would broadcast the rows into every slot)."""
+
+    def __init__(self, kv_cache, s: int):
+        super().__init__()
+        self.k_cache, self.v_cache = kv_cache.k_cache[s:s + 1], kv_cache.v_cache[s:s + 1]
+
+    def update(self, input_pos, k_val, v_val):
+        assert input_pos.shape[0] == k_val.shape[2]
+        self.k_cache[:, :, input_pos] = k_val
+        self.v_cache[:, :, input_pos] = v_val
+        return self.k_cache, self.v_cache
+
+
+class SlotPrefillEngine(PrefillEngine):
+    """The HIP prompt pass (2..16 tokens) of one request into slot `slot` of batch-B caches: slot s of a contiguous
+    [B, n_kv, max_seq, hd] cache is itself a contiguous [1, n_kv, max_seq, hd] cache, so the pass gets its base pointers."""
+
+    @staticmethod
+    def supports(model: Transformer) -> Optional[str]:
+        return PrefillEngine._supports(model, any_batch=True)
+
+    slot = 0
+
+    def _caches(self, at):
+        kc, vc = at.kv_cache.k_cache, at.kv_cache.v_cache
+        off = self.slot * kc[0].numel() * kc.element_size()
+        return kc.data_ptr() + off, vc.data_ptr() + off
+
+
+class SlotDecodeEngine(BatchedDecodeEngine):
+    """BatchedDecodeEngine whose B slots are switched on and off on the device (continuous batching).  One hipGraph replay is the
+    forward pass through the `_slots` launches (an inactive slot adds nothing to the union and writes no cache row), B
+    slot-predicated samplers and teal_batched_retire, which counts each active slot's token and switches the slot off on its EOS
+    id, its budget or the cache end.  `admit` puts one request into a free slot between replays."""
+
+    def __init__(self, model: Transformer, thresholds: List[Dict[str, float]], batch: int):
+        super().__init__(model, thresholds, batch)
+        dev = self.logits.device
+        self.slot_state = torch.zeros(SLOT_WORDS, dtype=torch.int32, device=dev)
+        self.slot_state[SLOT_EOS:SLOT_EOS + 8] = -1
+        self.slot_state[SLOT_FINISH:SLOT_FINISH + 8] = -1
+        self._state_host = torch.zeros(SLOT_WORDS, dtype=torch.int32).pin_memory()
+        self._prefill: Optional[SlotPrefillEngine] = None
+        self._union = []  # per burst: union rows [layer][launch][segment] of the burst's last step
+        self.admit_paths = {"hip": 0, "module": 0}
+
+    @property
+    def _active(self) -> int:
+        return self.slot_state.data_ptr()
+
+    # ---- the step's launches, slot-predicated ----------------------------------------------------------------------------
+    def _gemm(self, gin: PrefillIn, segs, lin0, lin1, Z: int, out: torch.Tensor, counts: Optional[torch.Tensor], st) -> int:
+        w0 = lin0.weight
+        rc = self.L.teal_batched_sparse_gemm_slots(ctypes.byref(gin), ctypes.byref(segs), w0.data_ptr(), w0.stride(1), w0.shape[0],
+                                                   lin1.weight.data_ptr() if lin1 is not None else None,
+                                                   lin1.weight.stride(1) if lin1 is not None else 0, lin1.weight.shape[0] if lin1 is not None else 0,
+                                                   out.data_ptr(), out.numel() * 4, Z, self.B, self._active,
+                                                   counts.data_ptr() if counts is not None else None, self.code, ctypes.byref(self._split), st)
+        if rc != 0:
+            _lib.check(rc, "teal_batched_sparse_gemm_slots")
+        return self._split.value
+
+    def _attention(self, at, A: torch.Tensor, ns: int, st):
+        cfg = self.cfg
+        kc, vc = at.kv_cache.k_cache, at.kv_cache.v_cache
+        rc = self.L.teal_batched_decode_attention_slots(A.data_ptr(), ns, self.rope.data_ptr(), self.pos_buf.data_ptr(), self._active,
+                                                        kc.data_ptr(), vc.data_ptr(), self.yt.data_ptr(), self.partials.data_ptr(),
+                                                        self.partials.numel() * 4, self.B, cfg.n_head, cfg.n_local_heads, cfg.head_dim,
+                                                        self.max_seq, self.code, st)
+        if rc != 0:
+            _lib.check(rc, "teal_batched_decode_attention_slots")
+
+    def _sample_slot(self, b: int, logits: torch.Tensor, temperature: float, top_k: Optional[int], st):
+        rc = self.L.teal_sample_topk_slot(logits.data_ptr(), self.cfg.vocab_size, self.code, int(top_k or 0), float(temperature),
+                                          self.rng_state[b].data_ptr(), self.tok_buf[b:].data_ptr(), self.pos_buf[b:].data_ptr(),
+                                          self.history[b].data_ptr(), self.history.shape[1], self.ws.data_ptr(), self.ws.numel() * 4,
+                                          self._active, b, st)
+        if rc != 0:
+            _lib.check(rc, "teal_sample_topk_slot")
+
+    def _retire(self, mask: int, count_step: bool, st):
+        rc = self.L.teal_batched_retire(self._active, self.tok_buf.data_ptr(), self.pos_buf.data_ptr(), self.B, mask, self.max_seq,
+                                        int(count_step), st)
+        if rc != 0:
+            _lib.check(rc, "teal_batched_retire")
+
+    def _sample(self, temperature: float, top_k: Optional[int]):
+        st = runtime.stream_ptr()
+        for b in range(self.B):
+            self._sample_slot(b, self.logits[b], temperature, top_k, st)
+        self._retire((1 << self.B) - 1, True, st)
+
+    def capture(self, temperature: float = 0.8, top_k: Optional[int] = 200):
+        state = self.slot_state.clone()  # the warm-up step retires too
+        try:
+            return super().capture(temperature, top_k)
+        finally:
+            self.slot_state.copy_(state)
+
+    # ---- admission ---------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def _prompt_pass(self, s: int, prompt: torch.Tensor) -> torch.Tensor:
+        """the dense prompt pass of one request into slot s's caches only -> logits [vocab] of its last token"""
+        T = int(prompt.numel())
+        m = self.model
+        if 2 <= T <= MAX_T:  # the HIP prompt pass at the slot's cache base pointers
+            if self._prefill is None:
+                self._prefill = SlotPrefillEngine(m)
+            self._prefill.slot = s
+            self.admit_paths["hip"] += 1
+            return self._prefill(prompt.to(torch.int32)).view(-1)
+        # the module path on a batch-1 view of slot s (the op-by-op ops: a one-token prompt takes the sparse kernels, a longer
+        # one the dense matmul, as generate()'s module path does)
+        self.admit_paths["module"] += 1
+        saved = [layer.attention.kv_cache for layer in m.layers]
+        fused = m.fused_decode
+        try:
+            for layer, kc in zip(m.layers, saved):
+                layer.attention.kv_cache = _SlotCacheView(kc, s)
+            m.fused_decode = False
+            logits = m(prompt.view(1, -1), torch.arange(0, T, device=prompt.device))
+        finally:
+            for layer, kc in zip(m.layers, saved):
+                layer.attention.kv_cache = kc
+            m.fused_decode = fused
+        return logits[0, -1].contiguous()
+
+    @torch.no_grad()
+    def admit(self, slot: int, tokens, budget: int, eos_id: Optional[int], seed: int, temperature: float = 0.8,
+              top_k: Optional[int] = 200):
+        """Request -> slot `slot` (free): the dense prompt pass into that slot's caches, the first token drawn from the last row's
+        logits (draw 0 of the stream `seed`), the slot's token, position, history, rng state, budget and EOS set on the device and
+        its bit set.  A request whose first token ends it (budget 1, EOS) is switched off again by the same retire rule."""
+        s, B = int(slot), self.B
+        prompt = torch.as_tensor(tokens, dtype=torch.int32).view(-1).to(self.logits.device)
+        T = int(prompt.numel())
+        if not 0 <= s < B:
+            raise ValueError(f"slot {s} outside 0..{B - 1}")
+        if T < 1 or T >= self.max_seq or int(budget) < 1:
+            raise ValueError(f"request of {T} prompt tokens and budget {budget} does not fit a cache of {self.max_seq} rows")
+        logits = self._prompt_pass(s, prompt)
+        self.rng_state[s].copy_(torch.tensor([int(seed), 0], dtype=torch.int64), non_blocking=False)
+        self.pos_buf[s] = T - 1  # the sampler moves it to T: the row the first decode step writes
+        upd = torch.tensor([int(budget), 0, -1 if eos_id is None else int(eos_id), -1], dtype=torch.int32).to(self.slot_state.device)
+        for j, off in enumerate((SLOT_BUDGET, SLOT_PRODUCED, SLOT_EOS, SLOT_FINISH)):
+            self.slot_state[off + s:off + s + 1].copy_(upd[j:j + 1])
+        self.slot_state[SLOT_ACTIVE:SLOT_ACTIVE + 1].bitwise_or_(1 << s)
+        st = runtime.stream_ptr()
+        self._sample_slot(s, logits, temperature, top_k, st)
+        self._retire(1 << s, False, st)
+
+    # ---- the batcher's view ------------------------------------------------------------------------------------------------
+    def run_steps(self, k: int, temperature: float = 0.8, top_k: Optional[int] = 200, use_graph: bool = True):
+        """k steps of every active slot (no host synchronisation); the union counts of the last are kept for the report"""
+        if use_graph:
+            g = self.capture(temperature, top_k)
+            for _ in range(k):
+                g.replay()
+        else:
+            for _ in range(k):
+                self._self_step(temperature, top_k)
+        self._union.append(self.counts.view(len(self.model.layers), len(PROJ_LAUNCHES), 16, 3, 9)[..., 8].sum(2))
+
+    def read_state(self):
+        """the slot state in one device-to-host copy (a list of SLOT_WORDS ints)"""
+        self._state_host.copy_(self.slot_state, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        return self._state_host.tolist()
+
+    def read_history(self, slot: int, n: int) -> List[int]:
+        return self.history[slot, :n].tolist()
+
+    def union_kept(self) -> Dict[str, float]:
+        """per projection: the mean over layers and over the bursts whose last step had an active slot of the fraction of rows
+        the union of the ACTIVE slots kept"""
+        if not self._union:
+            return {}
+        u = torch.stack(self._union).cpu().double()  # [bursts, layer, launch, segment]
+        live = u.flatten(1).sum(1) > 0
+        u = u[live]
+        out = {}
+        if u.shape[0] == 0:
+            return out
+        for j, (_, projs) in enumerate(PROJ_LAUNCHES):
+            Z = self.inter if projs == ("down",) else self.dim
+            for s, proj in enumerate(projs):
+                out[proj] = u[:, :, j, s].mean().item() / Z
+        return out
+
+    def reset_stats(self):
+        self._union = []
+        self.admit_paths = {"hip": 0, "module": 0}

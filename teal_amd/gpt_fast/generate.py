@@ -702,6 +702,67 @@ def run_batched(args, model: Transformer, thresholds, prompts: torch.Tensor, tok
             "thresholds": thresholds, "decoder": type(eng).__name__ if eng is not None else "module", "sequences": seqs}
 
 
+# ------------------------------------------------------------------------------------------------
+# continuous batching (--requests FILE): requests of any prompt length and budget share the --batch_size slots
+# ------------------------------------------------------------------------------------------------
+def check_requests_args(args) -> int:
+    """the number of slots; every refusal of batched decode and those of continuous batching, before anything is loaded"""
+    ns = argparse.Namespace(**vars(args))
+    ns.batch_size = max(2, int(getattr(args, "batch_size", 1) or 1))  # (batch 1 is served as one slot: the same refusals apply)
+    check_batched_args(ns)
+    if getattr(args, "no_engine", False):
+        raise SystemExit("--requests runs through the batched HIP engine: it does not combine with --no_engine")
+    if getattr(args, "no_fused_decode", False):
+        raise SystemExit("--requests runs through the fused batched step: it does not combine with --no_fused_decode")
+    if getattr(args, "dense", False) or (not args.synthetic and args.hist_path is None):
+        raise SystemExit("--requests needs TEAL thresholds (--hist_path, or --synthetic): the batched engine runs patched models only")
+    if int(getattr(args, "sync_every", 8)) < 1:
+        raise SystemExit("--sync_every must be >= 1")
+    if getattr(args, "eos_id", None) is not None and args.eos_id < 0:
+        raise SystemExit("--eos_id must be a token id (>= 0)")
+    return int(getattr(args, "batch_size", 1) or 1)
+
+
+@torch.no_grad()
+def run_continuous(args, model: Transformer, thresholds, tokenizer) -> Dict:
+    """--requests FILE through ContinuousBatcher on a SlotDecodeEngine of --batch_size slots (one hipGraph replay per step under
+    --compile, with one warm-up run first)"""
+    from teal_amd.gpt_fast.batched import SlotDecodeEngine
+    from teal_amd.gpt_fast.continuous import ContinuousBatcher, cache_rows, parse_requests
+    B = int(args.batch_size)
+    try:
+        with open(args.requests) as f:
+            reqs = parse_requests(f.read().splitlines(), args.max_new_tokens, tokenizer, args.eos_id)
+        max_seq = cache_rows(reqs, model.config.block_size)
+    except (OSError, ValueError) as e:
+        raise SystemExit(f"--requests: {e}")
+    model.setup_caches(max_batch_size=B, max_seq_length=max_seq)
+    why = SlotDecodeEngine.supports(model)
+    if why is not None:
+        raise SystemExit(f"--requests: the batched engine cannot run this model: {why}")
+    eng = SlotDecodeEngine(model, thresholds, B)
+    batcher = ContinuousBatcher(eng, sync_every=args.sync_every, temperature=args.temperature, top_k=args.top_k, seed=1234,
+                                use_graph=bool(args.compile))
+    if args.compile:
+        t0 = time.perf_counter()
+        batcher.run(reqs)
+        eng.reset_stats()
+        print(f"Graph capture + warm-up time: {time.perf_counter() - t0:.2f} seconds")
+    res = batcher.run(reqs)
+    for i, toks in enumerate(res["tokens"]):
+        text = tokenizer.decode(reqs[i].tokens + toks) if tokenizer is not None else toks
+        print(f"[request {i}, slot {res['slots'][i]}] {text}")
+    tps = res["useful_tokens_per_sec"]
+    print(f"{len(reqs)} requests, {res['useful_tokens']} useful tokens in {res['wall_s']:.2f} s: {tps:.2f} tokens/sec; "
+          f"{res['steps']} steps, {res['mean_active_slots']:.2f} active slots of {B} on average, "
+          f"{100 * res['admission_share']:.1f} % of the time in {res['admissions']} admissions")
+    print(f"Memory used: {torch.cuda.max_memory_reserved() / 1e9:.02f} GB")
+    return {"tokens_per_sec": [tps], "mean_tokens_per_sec": tps, "useful_tokens_per_sec": tps, "batch_size": B, "thresholds": thresholds,
+            "decoder": type(batcher).__name__, "sequences": res["tokens"], "steps": res["steps"], "admissions": res["admissions"],
+            "admission_share": res["admission_share"], "mean_active_slots": res["mean_active_slots"], "union_kept": res["union_kept"],
+            "sync_every": res["sync_every"]}
+
+
 def sample_batch(logits: torch.Tensor, temperature: float, top_k: Optional[int]) -> torch.Tensor:
     """one token per row of logits [B, V] (generate.sample's rule, row by row)"""
     return torch.cat([sample(logits[b:b + 1].unsqueeze(0), temperature=temperature, top_k=top_k)[0].view(1) for b in range(logits.shape[0])])
@@ -712,6 +773,8 @@ def main(args) -> Dict:
     assert "cuda" in device, "the sparse decode path is GPU-only (HIP kernels, no CPU fallback)"
     spec = check_speculative_args(args)  # before anything is loaded
     batch = check_batched_args(args)
+    if getattr(args, "requests", None) is not None:
+        check_requests_args(args)
     if getattr(args, "interactive", False) and args.synthetic:
         raise SystemExit("--interactive needs a tokenizer (a checkpoint directory), not --synthetic")
     dtype = {"fp16": torch.float16, "bf16": torch.bfloat16}[args.precision]
@@ -754,6 +817,8 @@ def main(args) -> Dict:
     torch.manual_seed(1234)
     if spec is not None:
         return run_speculative(args, model, thresholds, prompt, tokenizer, spec, device, dtype)
+    if getattr(args, "requests", None) is not None:
+        return run_continuous(args, model, thresholds, tokenizer)
     if batch > 1:
         if args.synthetic:  # B distinct seeded prompts of equal length
             prompts = torch.randint(0, model.config.vocab_size, (batch, prompt.numel()), device=device, dtype=torch.int,
@@ -880,6 +945,12 @@ def build_parser() -> argparse.ArgumentParser:
                    "times; --synthetic: B seeded prompts); through BatchedDecodeEngine under --compile / --engine")
     p.add_argument("--no_fused_decode", action="store_true", help="op-by-op module path (torch.ops.teal.* + eager glue) for "
                    "single-token calls: A/B against the fused decode step")
+    p.add_argument("--requests", type=Path, default=None, help="continuous batching: a JSON Lines file, one request per line "
+                   "({\"tokens\": [...]} or {\"prompt\": \"...\"}, optional \"max_new_tokens\"); --batch_size slots, refilled as "
+                   "requests finish")
+    p.add_argument("--eos_id", type=int, default=None, help="with --requests: a request also ends right after this token id (off "
+                   "by default: budgets alone end requests)")
+    p.add_argument("--sync_every", type=int, default=8, help="with --requests: steps per burst between two looks at the slot state")
     return p
 
 

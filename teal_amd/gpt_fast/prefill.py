@@ -41,6 +41,10 @@ class PrefillEngine:
     @staticmethod
     def supports(model: Transformer) -> Optional[str]:
         """None if the fused prompt pass can run `model` as it stands, else the reason (the caller keeps the module path)."""
+        return PrefillEngine._supports(model, any_batch=False)
+
+    @staticmethod
+    def _supports(model: Transformer, any_batch: bool) -> Optional[str]:
         cfg = model.config
         if int(getattr(model, "tp_world", 1)) > 1:
             return "tensor-parallel models prefill through the module path (its all-reduce hooks)"
@@ -63,14 +67,14 @@ class PrefillEngine:
             return "caches are not set up (model.setup_caches) in the model dtype"
         for layer in model.layers:
             kc = getattr(layer.attention, "kv_cache", None)
-            if kc is None or kc.k_cache.shape[0] != 1 or not kc.k_cache.is_contiguous() or not kc.v_cache.is_contiguous():
+            if kc is None or (kc.k_cache.shape[0] != 1 and not any_batch) or not kc.k_cache.is_contiguous() or not kc.v_cache.is_contiguous():
                 return "KV caches must be contiguous with max_batch_size == 1"
         return None
 
     def __init__(self, model: Transformer):
-        why = PrefillEngine.supports(model)
+        why = type(self).supports(model)
         if why is not None:
-            raise ValueError(f"PrefillEngine cannot run this model: {why}")
+            raise ValueError(f"{type(self).__name__} cannot run this model: {why}")
         self.L = _lib.load()
         runtime.init()
         self.model, cfg = model, model.config
@@ -110,6 +114,10 @@ class PrefillEngine:
                                               layer.feed_forward.w1.weight.data_ptr(), layer.feed_forward.w2.weight.data_ptr(),
                                               layer.feed_forward.w3.weight.data_ptr()))
 
+    def _caches(self, at):
+        """the raw K / V cache pointers the pass writes rows 0 .. T-1 of"""
+        return at.kv_cache.k_cache.data_ptr(), at.kv_cache.v_cache.data_ptr()
+
     def _gemm(self, gin: PrefillIn, lin0, lin1, Z, T, out: torch.Tensor, st) -> int:
         w0 = lin0.weight
         n1 = lin1.weight.shape[0] if lin1 is not None else 0
@@ -148,8 +156,8 @@ class PrefillEngine:
         for i, layer in enumerate(layers):
             at, ff = layer.attention, layer.feed_forward
             ns = self._gemm(self._norm_in(layer.attention_norm.weight), at.wqkv, None, self.dim, T, A, st)
-            kc, vc = at.kv_cache.k_cache, at.kv_cache.v_cache
-            rc = L.teal_prefill_attention(A.data_ptr(), ns, self.rope.data_ptr(), kc.data_ptr(), vc.data_ptr(), self.yt.data_ptr(), T,
+            kc, vc = self._caches(at)
+            rc = L.teal_prefill_attention(A.data_ptr(), ns, self.rope.data_ptr(), kc, vc, self.yt.data_ptr(), T,
                                           cfg.n_head, cfg.n_local_heads, cfg.head_dim, self.max_seq, self.code, st)
             if rc != 0:
                 _lib.check(rc, "teal_prefill_attention")
