@@ -490,6 +490,20 @@ int teal_sample_topk_slot(const void* logits, int vocab, int dtype, int top_k, f
                           int32_t* pos_inout, int32_t* history, int history_len, void* ws, size_t ws_bytes, const int32_t* active, int slot,
                           void* stream);
 
+/* ---- shared prompt prefixes of continuous batching, teal_amd/csrc/teal_prefix.hip ------------------------------------
+ * A prefix is a token sequence whose K / V rows (every layer) are computed once and kept in a device store; a request that names
+ * it is admitted by copying those rows into its slot's caches and running a prompt pass over its own tokens only. */
+
+/* Rows 0 .. rows-1 of every head of n_tensors cache tensors in ONE launch: for every tensor t < n_tensors, head h < n_heads and row
+ * r < rows the row_bytes bytes at dst[t] + h * dst_head_stride + r * row_bytes become those at src[t] + h * src_head_stride +
+ * r * row_bytes (16-byte loads and stores); no other byte is written.  src_table / dst_table: DEVICE arrays of n_tensors 64-bit
+ * addresses, each row 0 of head 0 of one tensor (K and V of every layer: n_tensors = 2 L), 16-byte aligned — the caller's contract,
+ * they are read on the device only (no host synchronisation; a captured launch follows the tables' contents at replay).  rows == 0
+ * launches nothing.  TEAL_ERR_ARG: a null table, n_tensors / n_heads / row_bytes <= 0, rows < 0; TEAL_ERR_ALIGN: row_bytes or a head
+ * stride not a multiple of 16; TEAL_ERR_SHAPE: a head stride smaller than rows * row_bytes, n_tensors or n_heads above 65535. */
+int teal_kv_copy_rows(const void* src_table, const void* dst_table, int n_tensors, int n_heads, int rows, int row_bytes,
+                      size_t src_head_stride, size_t dst_head_stride, void* stream);
+
 /* ---- benchmark comparator (scripts/benchmark_gemv.py only; not on the decode path) ----------- */
 
 /* The Deja Vu gather GEMV the reference's kernel benchmark plots next to TEAL's (scripts/benchmark_gemv.py:32-107,170-172),

@@ -8,6 +8,12 @@ Workload: --n requests from a fixed seed, prompt lengths uniform in --prompt (4.
 path) and budgets uniform in 16..256.  Useful tokens are those inside a request's budget.  Per leg: useful tok/s, wall time, steps,
 mean active slots, the share of device time spent in admissions, and the union kept fraction per projection (the last step of
 every burst, active slots only).
+
+--shared_prefix P instead: every request names ONE P-token prefix, with suffixes uniform in 4..16 tokens and the same budgets.  Two
+legs on the same engine, alternated: "shared" (the prefix registered: an admission is one row copy and a HIP pass over the suffix)
+and "unshared" (the same requests with prefix + suffix as plain tokens: the module path).  Per leg also ms per admission.
+
+    python scripts/continuous_bench.py --synthetic 7B --precision fp16 --sparsity 0.5 --shared_prefix 100
 """
 import argparse
 import json
@@ -38,6 +44,36 @@ def rec(leg, B, variant, res):
     return {"leg": leg, "B": B, "prompts": variant, "useful_tok_s": round(res["useful_tokens_per_sec"], 1), "wall_s": round(res["wall_s"], 2),
             "steps": res["steps"], "mean_active_slots": round(res["mean_active_slots"], 2),
             "admission_share": round(res["admission_share"], 3), "union_kept": {k: round(v, 3) for k, v in res["union_kept"].items()}}
+
+
+def shared_prefix(a, m, ths, V):
+    """--shared_prefix: the same 64 requests with the prefix's rows reused ("shared") and recomputed per request ("unshared")"""
+    P = a.shared_prefix
+    prefix = torch.randint(0, V, (P,), generator=torch.Generator().manual_seed(5)).tolist()
+    sfx = workload(a.n, (4, 16), (16, 256), V, 7)
+    shared = [Request(r.tokens, r.max_new_tokens, prefix="sys") for r in sfx]
+    unshared = [Request(prefix + r.tokens, r.max_new_tokens) for r in sfx]
+    max_seq = max(len(r.tokens) + r.max_new_tokens for r in unshared)
+    name = f"{P}+4..16"
+    print(json.dumps({"prompts": name, "useful_tokens": sum(r.max_new_tokens for r in sfx), "max_seq": max_seq}), flush=True)
+    for B in [int(x) for x in a.batches.split(",")]:
+        m.max_seq_length, m.max_batch_size = -1, -1
+        m.setup_caches(max_batch_size=B, max_seq_length=max_seq)
+        eng = SlotDecodeEngine(m, ths, B)
+        with_pf = ContinuousBatcher(eng, sync_every=a.sync_every, refill="free", prefixes={"sys": prefix})
+        without = ContinuousBatcher(eng, sync_every=a.sync_every, refill="free")
+        with_pf.run(shared[:B + 2])  # warm-up: registration, graph capture, both admission paths
+        without.run(unshared[:B + 2])
+        for leg, bt, reqs in (("shared", with_pf, shared), ("unshared", without, unshared)) * 2:
+            eng.reset_stats()
+            res = bt.run(reqs)
+            assert [len(t) for t in res["tokens"]] == [r.max_new_tokens for r in reqs]
+            r = rec(leg, B, name, res)
+            r["ms_per_admission"] = round(1e3 * res["admission_s"] / res["admissions"], 3)
+            r["admit_paths"], r["prefix_paths"], r["prefix_MB"] = dict(eng.admit_paths), dict(eng.prefix_paths), round(eng.prefix_bytes() / 1e6, 1)
+            print(json.dumps(r), flush=True)
+        del eng, with_pf, without
+        torch.cuda.empty_cache()
 
 
 def sequential(m, ths, reqs, max_seq, temperature, top_k):
@@ -71,6 +107,8 @@ def main():
     p.add_argument("--variants", default="4-16,17-128")
     p.add_argument("--sync_every", type=int, default=8)
     p.add_argument("--sequential", action="store_true", help="also the sequential DecodeEngine leg (first variant)")
+    p.add_argument("--shared_prefix", type=int, default=0, help="P > 0: the shared-prefix comparison instead (every request on one "
+                   "P-token prefix, suffixes 4..16)")
     a = p.parse_args()
     runtime.init()
     dev, dt = "cuda", {"fp16": torch.float16, "bf16": torch.bfloat16}[a.precision]
@@ -79,6 +117,8 @@ def main():
     V = m.config.vocab_size
     print(json.dumps({"model": a.synthetic, "precision": a.precision, "sparsity": a.sparsity, "requests": a.n, "budgets": "16..256",
                       "sync_every": a.sync_every}), flush=True)
+    if a.shared_prefix > 0:
+        return shared_prefix(a, m, ths, V)
     variants = [tuple(int(x) for x in v.split("-")) for v in a.variants.split(",")]
     for vi, pr in enumerate(variants):
         reqs = workload(a.n, pr, (16, 256), V, 7 + vi)

@@ -27,6 +27,7 @@ from ..kernels.sparse_gemv import BATCH_MAX, batched_segs
 from ..monkeypatch import UP_SHIFT_BYTES, to_column_major
 from .model import Transformer
 from .prefill import IN_NORM, IN_SILU_MUL, IN_XT, MAX_T, PrefillEngine, PrefillIn
+from .speculative import VerifyPass
 
 PROJ_LAUNCHES = (("qkv", ("q", "k", "v")), ("o", ("o",)), ("gateup", ("gate", "up")), ("down", ("down",)))
 NINF = float("-inf")
@@ -333,6 +334,52 @@ class SlotPrefillEngine(PrefillEngine):
         return kc.data_ptr() + off, vc.data_ptr() + off
 
 
+class SlotVerifyPass(VerifyPass):
+    """The dense pass over T <= 16 tokens at positions p .. p+T-1 (VerifyPass: p on the device, attention against the rows already
+    in the cache) into slot `slot` of batch-B caches — the suffix pass of a request admitted on a shared prefix."""
+
+    @staticmethod
+    def supports(model: Transformer) -> Optional[str]:
+        why = PrefillEngine._supports(model, any_batch=True)
+        if why is None and model.config.vocab_size % 256:
+            why = f"vocab_size {model.config.vocab_size} is not a multiple of 256 (the all-row lm_head GEMM's column contract)"
+        return why
+
+    slot = 0
+
+    def __init__(self, model: Transformer):
+        super().__init__(model)
+        self.rows = torch.zeros(8, 2 * model.config.vocab_size, device=self.lm_slabs.device, dtype=model.output.weight.dtype)
+
+    def _caches(self, at):
+        kc, vc = at.kv_cache.k_cache, at.kv_cache.v_cache
+        off = self.slot * kc[0].numel() * kc.element_size()
+        return kc.data_ptr() + off, vc.data_ptr() + off
+
+    def last_logits(self, ns: int, T: int) -> torch.Tensor:
+        """logits [vocab] of row T - 1 from the `ns` lm_head slabs run() left: summed in slice order, rounded once"""
+        V, st = self.model.config.vocab_size, runtime.stream_ptr()
+        # slabs [ns][V][8] (T <= 8), or [ns][V][16] read as [ns][2 V][8]: column 2 v + j holds rows 8 j .. 8 j + 7 of logit v
+        N, B = (V, T) if T <= 8 else (2 * V, 8)
+        rc = self.L.teal_batched_round_rows(self.lm_slabs.data_ptr(), ns, N, B, self.rows.data_ptr(), self.code, st)
+        if rc != 0:
+            _lib.check(rc, "teal_batched_round_rows (suffix lm_head)")
+        flat = self.rows.view(-1)
+        if T <= 8:
+            return flat[(T - 1) * V:T * V]
+        return flat[((T - 1) % 8) * N:((T - 1) % 8 + 1) * N].view(V, 2)[:, (T - 1) // 8].contiguous()
+
+
+class _Prefix:
+    """one registered prefix: its K / V rows [2 L][n_kv][P][hd] (K, V of layer 0, K, V of layer 1, ...), the device table of the 2 L
+    tensors' addresses and the position of a suffix's first token as a device int32"""
+
+    def __init__(self, rows: int, store: torch.Tensor):
+        self.rows, self.store = rows, store
+        self.table = torch.tensor([store[t].data_ptr() for t in range(store.shape[0])], dtype=torch.int64).to(store.device)
+        self.pos = torch.tensor([rows], dtype=torch.int32).to(store.device)
+
+
 class SlotDecodeEngine(BatchedDecodeEngine):
     """BatchedDecodeEngine whose B slots are switched on and off on the device (continuous batching).  One hipGraph replay is the
     forward pass through the `_slots` launches (an inactive slot adds nothing to the union and writes no cache row), B
@@ -349,6 +396,14 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         self._prefill: Optional[SlotPrefillEngine] = None
         self._union = []  # per burst: union rows [layer][launch][segment] of the burst's last step
         self.admit_paths = {"hip": 0, "module": 0}
+        # shared prefixes: per slot the device table of its 2 L cache tensors' addresses (K, V of layer 0, K, V of layer 1, ...)
+        caches = [c for layer in model.layers for c in (layer.attention.kv_cache.k_cache, layer.attention.kv_cache.v_cache)]
+        self._slot_tables = [torch.tensor([c[s].data_ptr() for c in caches], dtype=torch.int64).to(dev) for s in range(self.B)]
+        self._prefixes: Dict[str, _Prefix] = {}
+        self._verify: Optional[SlotVerifyPass] = None
+        self._verify_why: Optional[str] = None
+        self.prefix_paths = {"hip": 0, "module": 0}
+        self.admit_logits: Optional[torch.Tensor] = None
 
     @property
     def _active(self) -> int:
@@ -418,35 +473,119 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         # the module path on a batch-1 view of slot s (the op-by-op ops: a one-token prompt takes the sparse kernels, a longer
         # one the dense matmul, as generate()'s module path does)
         self.admit_paths["module"] += 1
+        return self._module_pass(s, prompt, 0)
+
+    def _module_pass(self, s: int, prompt: torch.Tensor, start: int) -> torch.Tensor:
+        """the module path over `prompt` at positions start .. start+T-1 on a batch-1 view of slot s -> logits [vocab] of the last"""
+        T = int(prompt.numel())
+        m = self.model
         saved = [layer.attention.kv_cache for layer in m.layers]
         fused = m.fused_decode
         try:
             for layer, kc in zip(m.layers, saved):
                 layer.attention.kv_cache = _SlotCacheView(kc, s)
             m.fused_decode = False
-            logits = m(prompt.view(1, -1), torch.arange(0, T, device=prompt.device))
+            logits = m(prompt.view(1, -1), torch.arange(start, start + T, device=prompt.device))
         finally:
             for layer, kc in zip(m.layers, saved):
                 layer.attention.kv_cache = kc
             m.fused_decode = fused
         return logits[0, -1].contiguous()
 
+    # ---- shared prefixes ---------------------------------------------------------------------------------------------------
+    def _copy_rows(self, src_table: torch.Tensor, dst_table: torch.Tensor, rows: int, src_rows: int, dst_rows: int):
+        """rows 0 .. rows-1 of every head of the 2 L tensors of one table into the other's (heads of src_rows / dst_rows rows)"""
+        rb = self.hd * self.model.output.weight.element_size()
+        rc = self.L.teal_kv_copy_rows(src_table.data_ptr(), dst_table.data_ptr(), 2 * len(self.model.layers), self.cfg.n_local_heads,
+                                      rows, rb, src_rows * rb, dst_rows * rb, runtime.stream_ptr())
+        if rc != 0:
+            _lib.check(rc, "teal_kv_copy_rows")
+
+    @torch.no_grad()
+    def register_prefix(self, name: str, tokens) -> int:
+        """Computes the K / V rows of `tokens` once — the prompt pass admitting them would run, into slot 0's caches — and keeps
+        them in a device store [2 L][n_kv][P][hd] under `name`; returns P.  The engine must be idle (slot 0's cache rows 0 .. P-1
+        are overwritten); no slot state, token, position, history or rng state moves and admit_paths does not count it."""
+        if name in self._prefixes:
+            raise ValueError(f"prefix {name!r} is registered already")
+        if int(self.slot_state[SLOT_ACTIVE].item()) != 0:
+            raise RuntimeError("register_prefix needs an idle engine: a slot is active")
+        toks = torch.as_tensor(tokens, dtype=torch.int32).view(-1).to(self.logits.device)
+        P = int(toks.numel())
+        if P < 1 or P + 1 >= self.max_seq:
+            raise ValueError(f"prefix {name!r} of {P} tokens leaves no room for a suffix in a cache of {self.max_seq} rows")
+        counted = dict(self.admit_paths)
+        try:
+            self._prompt_pass(0, toks)
+        finally:
+            self.admit_paths = counted
+        store = torch.empty(2 * len(self.model.layers), self.cfg.n_local_heads, P, self.hd, device=self.logits.device, dtype=self.dtype)
+        pf = _Prefix(P, store)
+        self._copy_rows(self._slot_tables[0], pf.table, P, self.max_seq, P)
+        self._prefixes[name] = pf
+        return P
+
+    def drop_prefix(self, name: str):
+        if name not in self._prefixes:
+            raise ValueError(f"unknown prefix {name!r}")
+        torch.cuda.current_stream().synchronize()  # (a copy out of the store may still be in flight)
+        del self._prefixes[name]
+
+    def has_prefix(self, name: str) -> bool:
+        return name in self._prefixes
+
+    def prefix_rows(self, name: str) -> int:
+        return self._prefixes[name].rows
+
+    def prefix_store(self, name: str) -> torch.Tensor:
+        """the store [2 L][n_kv][P][hd]: K, V of layer 0, K, V of layer 1, ..."""
+        return self._prefixes[name].store
+
+    def prefix_bytes(self) -> int:
+        return sum(p.store.numel() * p.store.element_size() for p in self._prefixes.values())
+
+    def _suffix_pass(self, s: int, pf: _Prefix, suffix: torch.Tensor) -> torch.Tensor:
+        """the prefix's rows into slot s (one launch), then the dense pass over the suffix at positions P .. P+T-1 into slot s's
+        caches only -> logits [vocab] of its last token"""
+        T = int(suffix.numel())
+        self._copy_rows(pf.table, self._slot_tables[s], pf.rows, pf.rows, self.max_seq)
+        if T <= MAX_T and self._verify is None and self._verify_why is None:
+            self._verify_why = SlotVerifyPass.supports(self.model)
+            if self._verify_why is None:
+                self._verify = SlotVerifyPass(self.model)
+        if T <= MAX_T and self._verify is not None:  # the HIP verify pass at the slot's cache base pointers
+            self._verify.slot = s
+            self.prefix_paths["hip"] += 1
+            return self._verify.last_logits(self._verify.run(suffix, pf.pos, T), T)
+        self.prefix_paths["module"] += 1
+        return self._module_pass(s, suffix, pf.rows)
+
     @torch.no_grad()
     def admit(self, slot: int, tokens, budget: int, eos_id: Optional[int], seed: int, temperature: float = 0.8,
-              top_k: Optional[int] = 200):
+              top_k: Optional[int] = 200, prefix: Optional[str] = None):
         """Request -> slot `slot` (free): the dense prompt pass into that slot's caches, the first token drawn from the last row's
         logits (draw 0 of the stream `seed`), the slot's token, position, history, rng state, budget and EOS set on the device and
-        its bit set.  A request whose first token ends it (budget 1, EOS) is switched off again by the same retire rule."""
+        its bit set.  A request whose first token ends it (budget 1, EOS) is switched off again by the same retire rule.
+        `prefix`: a registered prefix of P rows — `tokens` are the request's own suffix; the store's rows 0 .. P-1 are copied into
+        the slot and only the suffix is run, at positions P .. P+T-1: the request is served as prompt = prefix + suffix."""
         s, B = int(slot), self.B
         prompt = torch.as_tensor(tokens, dtype=torch.int32).view(-1).to(self.logits.device)
         T = int(prompt.numel())
         if not 0 <= s < B:
             raise ValueError(f"slot {s} outside 0..{B - 1}")
-        if T < 1 or T >= self.max_seq or int(budget) < 1:
-            raise ValueError(f"request of {T} prompt tokens and budget {budget} does not fit a cache of {self.max_seq} rows")
-        logits = self._prompt_pass(s, prompt)
+        pf = None
+        if prefix is not None:
+            pf = self._prefixes.get(prefix)
+            if pf is None:
+                raise ValueError(f"unknown prefix {prefix!r} (register_prefix first)")
+        P = pf.rows if pf is not None else 0
+        if T < 1 or P + T >= self.max_seq or int(budget) < 1:
+            raise ValueError(f"request of {T} prompt tokens" + (f" on a prefix of {P}" if pf is not None else "") +
+                             f" and budget {budget} does not fit a cache of {self.max_seq} rows")
+        logits = self._prompt_pass(s, prompt) if pf is None else self._suffix_pass(s, pf, prompt)
+        self.admit_logits = logits  # (the last admission's, for tests and reports: valid until the next one)
         self.rng_state[s].copy_(torch.tensor([int(seed), 0], dtype=torch.int64), non_blocking=False)
-        self.pos_buf[s] = T - 1  # the sampler moves it to T: the row the first decode step writes
+        self.pos_buf[s] = P + T - 1  # the sampler moves it to P + T: the row the first decode step writes
         upd = torch.tensor([int(budget), 0, -1 if eos_id is None else int(eos_id), -1], dtype=torch.int32).to(self.slot_state.device)
         for j, off in enumerate((SLOT_BUDGET, SLOT_PRODUCED, SLOT_EOS, SLOT_FINISH)):
             self.slot_state[off + s:off + s + 1].copy_(upd[j:j + 1])
@@ -496,3 +635,4 @@ class SlotDecodeEngine(BatchedDecodeEngine):
     def reset_stats(self):
         self._union = []
         self.admit_paths = {"hip": 0, "module": 0}
+        self.prefix_paths = {"hip": 0, "module": 0}

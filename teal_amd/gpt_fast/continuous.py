@@ -10,6 +10,11 @@ refill="free" admits into every free slot; refill="all" only when every slot is 
 (the benchmark's baseline).  Request r draws from its own stream, seed + r (draw 0 is its first token, draw i decode step i),
 so its tokens do not depend on its slot, on the requests beside it or on sync_every (where the union does not either: every
 row kept).
+
+Shared prefixes: a request may name a prefix — a token sequence registered with the engine once, whose K / V rows stay in a device
+store.  Its own tokens are then the suffix: it is served as prompt = prefix + suffix, but its admission copies the prefix's rows
+into the slot and runs the prompt pass over the suffix alone.  Prefixes are named, never detected: what a request computes does
+not depend on what happened to be cached when it was admitted.
 """
 from __future__ import annotations
 
@@ -30,11 +35,67 @@ class Request:
     max_new_tokens: int
     eos_id: Optional[int] = None
     seed: Optional[int] = None  # its random stream; None: the batcher's seed + its index
+    prefix: Optional[str] = None  # a shared prefix's id: `tokens` are the suffix after its rows
 
 
-def parse_requests(lines: Sequence[str], default_max_new_tokens: int, tokenizer=None, eos_id: Optional[int] = None) -> List[Request]:
+def _token_list(toks) -> bool:
+    return isinstance(toks, list) and bool(toks) and all(isinstance(t, int) and not isinstance(t, bool) and t >= 0 for t in toks)
+
+
+def parse_prefixes(lines: Sequence[str], tokenizer=None) -> Dict[str, List[int]]:
+    """JSON Lines, one shared prefix per line: {"id": "sys", "tokens": [...]} or {"id": "sys", "prompt": "..."} (needs a tokenizer;
+    BOS prepended as for prompts).  Blank lines are skipped; an empty file is an empty mapping."""
+    out: Dict[str, List[int]] = {}
+    for i, line in enumerate(lines):
+        if not line.strip():
+            continue
+        try:
+            d = json.loads(line)
+        except json.JSONDecodeError as e:
+            raise ValueError(f"prefix line {i + 1}: not JSON ({e})") from None
+        if not isinstance(d, dict) or not isinstance(d.get("id"), str) or not d["id"]:
+            raise ValueError(f"prefix line {i + 1}: needs an \"id\" (a non-empty string)")
+        if ("tokens" in d) == ("prompt" in d):
+            raise ValueError(f"prefix line {i + 1}: needs exactly one of \"tokens\" and \"prompt\"")
+        if d["id"] in out:
+            raise ValueError(f"prefix line {i + 1}: duplicate id {d['id']!r}")
+        if "tokens" in d:
+            toks = d["tokens"]
+            if not _token_list(toks):
+                raise ValueError(f"prefix line {i + 1}: \"tokens\" must be a non-empty list of token ids")
+        else:
+            if tokenizer is None:
+                raise ValueError(f"prefix line {i + 1}: a \"prompt\" needs a tokenizer (a checkpoint), not --synthetic")
+            if not isinstance(d["prompt"], str):
+                raise ValueError(f"prefix line {i + 1}: \"prompt\" must be a string")
+            toks = [tokenizer.bos_id()] + tokenizer.encode(d["prompt"])
+        out[d["id"]] = [int(t) for t in toks]
+    return out
+
+
+def check_prefix_ids(request_lines: Sequence[str], prefix_lines: Sequence[str]) -> None:
+    """every "prefix" a request line names is an "id" of a prefix line — needs no tokenizer, so it runs before anything is loaded
+    (malformed lines are left to parse_prefixes / parse_requests, which name them)"""
+    def objs(lines):
+        for i, line in enumerate(lines):
+            try:
+                d = json.loads(line) if line.strip() else None
+            except json.JSONDecodeError:
+                d = None
+            if isinstance(d, dict):
+                yield i, d
+    ids = {d.get("id") for _, d in objs(prefix_lines)}
+    for i, d in objs(request_lines):
+        if d.get("prefix") is not None and d["prefix"] not in ids:
+            raise ValueError(f"request line {i + 1}: unknown prefix {d['prefix']!r}" + ("" if ids else " (no prefixes were given)"))
+
+
+def parse_requests(lines: Sequence[str], default_max_new_tokens: int, tokenizer=None, eos_id: Optional[int] = None,
+                   prefixes: Optional[Dict[str, List[int]]] = None) -> List[Request]:
     """JSON Lines, one request per line: {"tokens": [...]} or {"prompt": "..."} (needs a tokenizer; BOS prepended as generate.py
-    does), with an optional "max_new_tokens" (default: `default_max_new_tokens`).  Blank lines are skipped."""
+    does), with an optional "max_new_tokens" (default: `default_max_new_tokens`).  Blank lines are skipped.  A line may carry
+    "prefix": an id of `prefixes`; its tokens / prompt are then the suffix, and a prompt is encoded WITHOUT a BOS (the prefix
+    holds it)."""
     out = []
     for i, line in enumerate(lines):
         if not line.strip():
@@ -45,6 +106,9 @@ def parse_requests(lines: Sequence[str], default_max_new_tokens: int, tokenizer=
             raise ValueError(f"request line {i + 1}: not JSON ({e})") from None
         if not isinstance(d, dict) or ("tokens" in d) == ("prompt" in d):
             raise ValueError(f"request line {i + 1}: needs exactly one of \"tokens\" and \"prompt\"")
+        pid = d.get("prefix")
+        if pid is not None and (not isinstance(pid, str) or pid not in (prefixes or {})):
+            raise ValueError(f"request line {i + 1}: unknown prefix {pid!r}" + ("" if prefixes else " (no prefixes were given)"))
         if "tokens" in d:
             toks = d["tokens"]
             if not isinstance(toks, list) or not toks or not all(isinstance(t, int) and t >= 0 for t in toks):
@@ -52,38 +116,56 @@ def parse_requests(lines: Sequence[str], default_max_new_tokens: int, tokenizer=
         else:
             if tokenizer is None:
                 raise ValueError(f"request line {i + 1}: a \"prompt\" needs a tokenizer (a checkpoint), not --synthetic")
-            toks = [tokenizer.bos_id()] + tokenizer.encode(d["prompt"])
+            toks = ([] if pid is not None else [tokenizer.bos_id()]) + tokenizer.encode(d["prompt"])
+            if not toks:
+                raise ValueError(f"request line {i + 1}: the \"prompt\" under prefix {pid!r} encodes to no tokens (an empty suffix)")
         n = d.get("max_new_tokens", default_max_new_tokens)
         if not isinstance(n, int) or n < 1:
             raise ValueError(f"request line {i + 1}: \"max_new_tokens\" must be a positive integer")
-        out.append(Request([int(t) for t in toks], n, eos_id))
+        out.append(Request([int(t) for t in toks], n, eos_id, prefix=pid))
     if not out:
         raise ValueError("no requests")
     return out
 
 
-def cache_rows(requests: Sequence[Request], block_size: int) -> int:
-    """the cache length a run needs: the longest prompt + budget, capped at block_size; a request that cannot fit is refused"""
+def _prefix_len(i: int, r: Request, prefixes) -> int:
+    """rows of request i's prefix (0: none); `prefixes` maps an id to its tokens"""
+    if getattr(r, "prefix", None) is None:
+        return 0
+    if not prefixes or r.prefix not in prefixes:
+        raise ValueError(f"request {i}: unknown prefix {r.prefix!r}")
+    return len(prefixes[r.prefix])
+
+
+def cache_rows(requests: Sequence[Request], block_size: int, prefixes: Optional[Dict[str, List[int]]] = None) -> int:
+    """the cache length a run needs: the longest (prefix +) prompt + budget, capped at block_size; a request that cannot fit is
+    refused"""
+    rows = []
     for i, r in enumerate(requests):
-        if len(r.tokens) + r.max_new_tokens > block_size:
-            raise ValueError(f"request {i}: {len(r.tokens)} prompt tokens + {r.max_new_tokens} new tokens exceed the model's "
-                             f"block_size {block_size}")
-    return min(max(len(r.tokens) + r.max_new_tokens for r in requests), block_size)
+        P = _prefix_len(i, r, prefixes)
+        if P + len(r.tokens) + r.max_new_tokens > block_size:
+            raise ValueError(f"request {i}: " + (f"{P} prefix tokens + " if P else "") + f"{len(r.tokens)} prompt tokens + "
+                             f"{r.max_new_tokens} new tokens exceed the model's block_size {block_size}")
+        rows.append(P + len(r.tokens) + r.max_new_tokens)
+    return min(max(rows), block_size)
 
 
 class ContinuousBatcher:
     """Runs requests through an engine with B slots.  The engine offers B, max_seq, admit(slot, tokens, budget, eos_id, seed,
     temperature, top_k), run_steps(k, temperature, top_k, use_graph), read_state() (the slot state words, one copy),
-    read_history(slot, n) and union_kept()."""
+    read_history(slot, n) and union_kept().  `prefixes` (id -> tokens): the engine also offers has_prefix(id),
+    register_prefix(id, tokens) and admit(..., prefix=id); run() registers every prefix the engine does not hold yet before its
+    first admission, and only requests that name a prefix are admitted with `prefix=`."""
 
     def __init__(self, engine, sync_every: int = 8, refill: str = "free", temperature: float = 0.8, top_k: Optional[int] = 200,
-                 seed: int = 1234, use_graph: bool = True):
+                 seed: int = 1234, use_graph: bool = True, prefixes: Optional[Dict[str, List[int]]] = None):
         if refill not in REFILL:
             raise ValueError(f"refill must be one of {REFILL}")
         if int(sync_every) < 1:
             raise ValueError("sync_every must be >= 1")
         self.eng, self.K, self.refill = engine, int(sync_every), refill
         self.temperature, self.top_k, self.seed, self.use_graph = temperature, top_k, int(seed), use_graph
+        self.prefixes = {k: [int(t) for t in v] for k, v in (prefixes or {}).items()}
 
     def _clock(self):
         try:
@@ -102,16 +184,22 @@ class ContinuousBatcher:
 
     def run(self, requests: Sequence[Request]) -> Dict:
         eng, B = self.eng, self.eng.B
+        plen = []
         for i, r in enumerate(requests):  # refused before anything runs
-            if len(r.tokens) < 1 or r.max_new_tokens < 1 or len(r.tokens) + r.max_new_tokens > eng.max_seq:
-                raise ValueError(f"request {i}: {len(r.tokens)} prompt tokens + {r.max_new_tokens} new tokens do not fit a cache of "
-                                 f"{eng.max_seq} rows")
+            P = _prefix_len(i, r, self.prefixes)
+            if len(r.tokens) < 1 or r.max_new_tokens < 1 or P + len(r.tokens) + r.max_new_tokens > eng.max_seq:
+                raise ValueError(f"request {i}: " + (f"{P} prefix tokens + " if P else "") + f"{len(r.tokens)} prompt tokens + "
+                                 f"{r.max_new_tokens} new tokens do not fit a cache of {eng.max_seq} rows")
+            plen.append(P)
+        for name, toks in self.prefixes.items():  # once per prefix, before the first admission (the engine is idle)
+            if not eng.has_prefix(name):
+                eng.register_prefix(name, toks)
         pending = deque(range(len(requests)))
         slot_req: List[Optional[int]] = [None] * B
         admitted_at = [0] * B
         out: List[Optional[List[int]]] = [None] * len(requests)
         slots_used: List[int] = [-1] * len(requests)
-        steps = admissions = slot_steps = 0
+        steps = admissions = slot_steps = prefix_admissions = prefix_rows = 0
         step0 = eng.read_state()[SLOT_STEP]  # the engine's step counter (finish steps are on its scale)
         admit_spans = []
         t0 = time.perf_counter()
@@ -125,8 +213,11 @@ class ContinuousBatcher:
                         break
                     r = pending.popleft()
                     q = requests[r]
+                    kw = {"prefix": q.prefix} if plen[r] else {}
                     eng.admit(s, q.tokens, q.max_new_tokens, q.eos_id, self.seed + r if q.seed is None else q.seed, self.temperature,
-                              self.top_k)
+                              self.top_k, **kw)
+                    prefix_admissions += 1 if plen[r] else 0
+                    prefix_rows += plen[r]
                     slot_req[s], admitted_at[s], slots_used[r] = r, step0 + steps, s
                     admissions += 1
                 admit_spans.append((a0, self._clock()))
@@ -153,4 +244,6 @@ class ContinuousBatcher:
             "mean_active_slots": slot_steps / steps if steps else 0.0, "useful_tokens": useful,
             "useful_tokens_per_sec": useful / wall if wall > 0 else 0.0, "union_kept": eng.union_kept(),
             "refill": self.refill, "sync_every": self.K, "batch_size": B,
+            "prefix_admissions": prefix_admissions, "prefix_rows_reused": prefix_rows,
+            "prefix_paths": dict(getattr(eng, "prefix_paths", {})),
         }

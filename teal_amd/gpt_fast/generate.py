@@ -728,12 +728,21 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer) -> Dict:
     """--requests FILE through ContinuousBatcher on a SlotDecodeEngine of --batch_size slots (one hipGraph replay per step under
     --compile, with one warm-up run first)"""
     from teal_amd.gpt_fast.batched import SlotDecodeEngine
-    from teal_amd.gpt_fast.continuous import ContinuousBatcher, cache_rows, parse_requests
+    from teal_amd.gpt_fast.continuous import ContinuousBatcher, cache_rows, parse_prefixes, parse_requests
     B = int(args.batch_size)
+    prefixes = {}
+    if getattr(args, "prefixes", None) is not None:
+        try:
+            with open(args.prefixes) as f:
+                prefixes = parse_prefixes(f.read().splitlines(), tokenizer)
+        except (OSError, ValueError) as e:
+            raise SystemExit(f"--prefixes: {e}")
     try:
         with open(args.requests) as f:
-            reqs = parse_requests(f.read().splitlines(), args.max_new_tokens, tokenizer, args.eos_id)
-        max_seq = cache_rows(reqs, model.config.block_size)
+            reqs = parse_requests(f.read().splitlines(), args.max_new_tokens, tokenizer, args.eos_id, prefixes=prefixes)
+        max_seq = cache_rows(reqs, model.config.block_size, prefixes)
+        if prefixes:  # (a prefix no request names is registered too: it needs room for a one-token suffix)
+            max_seq = max(max_seq, min(max(len(t) for t in prefixes.values()) + 2, model.config.block_size))
     except (OSError, ValueError) as e:
         raise SystemExit(f"--requests: {e}")
     model.setup_caches(max_batch_size=B, max_seq_length=max_seq)
@@ -742,7 +751,14 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer) -> Dict:
         raise SystemExit(f"--requests: the batched engine cannot run this model: {why}")
     eng = SlotDecodeEngine(model, thresholds, B)
     batcher = ContinuousBatcher(eng, sync_every=args.sync_every, temperature=args.temperature, top_k=args.top_k, seed=1234,
-                                use_graph=bool(args.compile))
+                                use_graph=bool(args.compile), prefixes=prefixes)
+    try:
+        for name, toks in prefixes.items():  # once, before the warm-up run
+            eng.register_prefix(name, toks)
+    except ValueError as e:
+        raise SystemExit(f"--prefixes: {e}")
+    if prefixes:
+        print(f"{len(prefixes)} shared prefixes registered: {eng.prefix_bytes() / 1e6:.2f} MB of K / V rows kept on the device")
     if args.compile:
         t0 = time.perf_counter()
         batcher.run(reqs)
@@ -750,17 +766,21 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer) -> Dict:
         print(f"Graph capture + warm-up time: {time.perf_counter() - t0:.2f} seconds")
     res = batcher.run(reqs)
     for i, toks in enumerate(res["tokens"]):
-        text = tokenizer.decode(reqs[i].tokens + toks) if tokenizer is not None else toks
+        text = tokenizer.decode(prefixes.get(reqs[i].prefix, []) + reqs[i].tokens + toks) if tokenizer is not None else toks
         print(f"[request {i}, slot {res['slots'][i]}] {text}")
     tps = res["useful_tokens_per_sec"]
     print(f"{len(reqs)} requests, {res['useful_tokens']} useful tokens in {res['wall_s']:.2f} s: {tps:.2f} tokens/sec; "
           f"{res['steps']} steps, {res['mean_active_slots']:.2f} active slots of {B} on average, "
           f"{100 * res['admission_share']:.1f} % of the time in {res['admissions']} admissions")
+    if prefixes:
+        print(f"{res['prefix_admissions']} admissions on a shared prefix reused {res['prefix_rows_reused']} rows; suffix passes: "
+              f"{res['prefix_paths']}")
     print(f"Memory used: {torch.cuda.max_memory_reserved() / 1e9:.02f} GB")
     return {"tokens_per_sec": [tps], "mean_tokens_per_sec": tps, "useful_tokens_per_sec": tps, "batch_size": B, "thresholds": thresholds,
             "decoder": type(batcher).__name__, "sequences": res["tokens"], "steps": res["steps"], "admissions": res["admissions"],
             "admission_share": res["admission_share"], "mean_active_slots": res["mean_active_slots"], "union_kept": res["union_kept"],
-            "sync_every": res["sync_every"]}
+            "sync_every": res["sync_every"], "prefix_admissions": res["prefix_admissions"],
+            "prefix_rows_reused": res["prefix_rows_reused"], "prefix_paths": res["prefix_paths"]}
 
 
 def sample_batch(logits: torch.Tensor, temperature: float, top_k: Optional[int]) -> torch.Tensor:
@@ -773,8 +793,16 @@ def main(args) -> Dict:
     assert "cuda" in device, "the sparse decode path is GPU-only (HIP kernels, no CPU fallback)"
     spec = check_speculative_args(args)  # before anything is loaded
     batch = check_batched_args(args)
+    if getattr(args, "prefixes", None) is not None and getattr(args, "requests", None) is None:
+        raise SystemExit("--prefixes names shared prefixes of continuous batching: it needs --requests")
     if getattr(args, "requests", None) is not None:
         check_requests_args(args)
+        from teal_amd.gpt_fast.continuous import check_prefix_ids
+        try:  # a request on a prefix nobody defined: refused before anything is loaded, too
+            pf = getattr(args, "prefixes", None)
+            check_prefix_ids(Path(args.requests).read_text().splitlines(), Path(pf).read_text().splitlines() if pf is not None else [])
+        except (OSError, ValueError) as e:
+            raise SystemExit(f"--requests: {e}")
     if getattr(args, "interactive", False) and args.synthetic:
         raise SystemExit("--interactive needs a tokenizer (a checkpoint directory), not --synthetic")
     dtype = {"fp16": torch.float16, "bf16": torch.bfloat16}[args.precision]
@@ -948,6 +976,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--requests", type=Path, default=None, help="continuous batching: a JSON Lines file, one request per line "
                    "({\"tokens\": [...]} or {\"prompt\": \"...\"}, optional \"max_new_tokens\"); --batch_size slots, refilled as "
                    "requests finish")
+    p.add_argument("--prefixes", type=Path, default=None, help="with --requests: a JSON Lines file of shared prefixes, one per line "
+                   "({\"id\": \"sys\", \"tokens\": [...]} or {\"id\": \"sys\", \"prompt\": \"...\"}); a request line that carries "
+                   "\"prefix\": \"sys\" gives only its own suffix and reuses the prefix's K / V rows, computed once")
     p.add_argument("--eos_id", type=int, default=None, help="with --requests: a request also ends right after this token id (off "
                    "by default: budgets alone end requests)")
     p.add_argument("--sync_every", type=int, default=8, help="with --requests: steps per burst between two looks at the slot state")

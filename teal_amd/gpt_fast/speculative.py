@@ -44,7 +44,7 @@ class VerifyPass(PrefillEngine):
         return None
 
     def __init__(self, model: Transformer):
-        why = VerifyPass.supports(model)
+        why = type(self).supports(model)
         if why is not None:
             raise ValueError(f"speculative decoding cannot verify with this model: {why}")
         super().__init__(model)
@@ -68,8 +68,8 @@ class VerifyPass(PrefillEngine):
         for layer in m.layers:
             at, ff = layer.attention, layer.feed_forward
             ns = self._gemm(self._norm_in(layer.attention_norm.weight), at.wqkv, None, self.dim, T, A, st)
-            kc, vc = at.kv_cache.k_cache, at.kv_cache.v_cache
-            rc = L.teal_verify_attention(A.data_ptr(), ns, self.rope.data_ptr(), pos.data_ptr(), kc.data_ptr(), vc.data_ptr(), self.yt.data_ptr(),
+            kc, vc = self._caches(at)
+            rc = L.teal_verify_attention(A.data_ptr(), ns, self.rope.data_ptr(), pos.data_ptr(), kc, vc, self.yt.data_ptr(),
                                          self.partials.data_ptr(), self.partials.numel() * 4, T, cfg.n_head, cfg.n_local_heads, cfg.head_dim,
                                          self.max_seq, self.code, st)
             if rc != 0:
