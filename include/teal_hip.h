@@ -313,6 +313,8 @@ int teal_decode_attention_split_roped(const void* q, const int32_t* pos, const v
  * projection merges them in its own prologue (nsplit 4 or 8) — one launch less per layer, and 4 CUs per head pull the KV
  * cache instead of one (a single CU sustains ~50 GB/s, which bounds the one-workgroup-per-head kernel). */
 
+/* ---- fused top-k sampler, teal_amd/csrc/teal_sampler.hip --------------------------------------- */
+
 /* Sampling step of the decode loop (gpt-fast/generate.py:49-66): logits / temperature, top-k filter
  * (ties at the pivot kept), softmax, exponential-race multinomial.  rng_state = device uint64[2]
  * {seed, draw counter}; the kernel bumps the counter so hipGraph replays draw fresh numbers.
@@ -483,7 +485,8 @@ int teal_batched_decode_attention_slots(const float* qkv_slabs, int split, const
  * passes the cache).  count_step != 0: TEAL_SLOT_STEP += 1 (the decode step; an admission's first draw passes 0). */
 int teal_batched_retire(int32_t* slot_state, const int32_t* tokens, int32_t* pos, int B, int slot_mask, int max_seq, int count_step,
                         void* stream);
-/* teal_sample_topk_ws predicated on bit `slot` of active[0] (device int32): set, exactly teal_sample_topk_ws; clear, nothing changes —
+/* (teal_amd/csrc/teal_sampler.hip) teal_sample_topk_ws predicated on bit `slot` of active[0] (device int32): set, exactly
+ * teal_sample_topk_ws; clear, nothing changes —
  * token, position, rng_state, history and the workspace's ticket and scratch stay as they were (every workgroup of the
  * multi-workgroup form exits before the ticket). */
 int teal_sample_topk_slot(const void* logits, int vocab, int dtype, int top_k, float temperature, void* rng_state, int32_t* token_out,
@@ -549,11 +552,21 @@ int teal_set_phase_buffer(void* dev_u64);
 int teal_set_phase_stride(size_t u64_per_launch);
 #endif /* TEAL_DIAGNOSTICS */
 
-/* ---- introspection (pure function of its arguments and the device's CU count) ------------------ */
+/* ---- introspection (pure functions of their arguments; teal_get_config also of the device's CU count) - */
 
 /* The geometry a GEMV of this shape would use: out[0..5) = {lanes_per_row, waves, split, unroll,
  * workgroups}. */
 int teal_get_config(int Z, int N, int nseg, int* out);
+
+/* The launch teal_decode_attention_split* makes for this shape (teal_amd/csrc/teal_attention.hip; host only, no device needed):
+ * out[0] = 1: the shape takes the grouped-query kernel (n_head / n_kv_head = 8 or 4 from its cache length on; never when
+ * `roped`, i.e. through teal_decode_attention_split_roped); out[1] = threads per workgroup; out[2] = dynamic LDS bytes of that
+ * launch at this nsplit; out[3] = the LDS limit it has to fit.  For the grouped kernel that is what a device grants after
+ * teal_init(): above it the launch falls back to the per-query-head kernel.  Otherwise it is 64 KiB, and the launch
+ * refuses a share above it (TEAL_ERR_SHAPE).  The query itself reports either case through out[2] > out[3].
+ * TEAL_ERR_ARG: out == NULL; TEAL_ERR_SHAPE: the arguments the launch refuses (head_dim not 64 / 128, n_head not a positive
+ * multiple of n_kv_head, max_seq < 1, nsplit outside 1..64). */
+int teal_decode_attention_split_plan(int n_head, int n_kv_head, int head_dim, int max_seq, int nsplit, int roped, int* out);
 
 #ifdef __cplusplus
 }

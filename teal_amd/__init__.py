@@ -3,7 +3,7 @@
 Layout:
   csrc/                   hand-written HIP for gfx950 behind the C ABI of include/teal_hip.h:
                           teal_gemv_kernel.h (sparse GEMV template), teal_gemv_w{16,8}_{f16,bf16}.hip (instantiations),
-                          teal_attention.hip (decode attention + sampler), teal_kernels.hip (host logic + GEMV ABI)
+                          teal_attention.hip (decode attention), teal_sampler.hip (fused top-k sampler), teal_kernels.hip (host logic + GEMV ABI)
   quantize.py             int8 weight-only quantiser / module (feeds the int8 sparse GEMV)
   hf.py, calibrate.py     HF-transformers plugin surface; calibration producers
   _lib.py                 hipcc build + ctypes loader of libteal_hip.so (no CPU fallback)

@@ -17,16 +17,16 @@ import sys
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 CSRC = os.path.join(_PKG, "csrc")
-# translation units: host logic + GEMV ABI, attention + sampler, and the GEMV kernel instantiations split by
+# translation units: host logic + GEMV ABI, decode attention, the sampler, and the GEMV kernel instantiations split by
 # (weight width, activation dtype) so that they compile in parallel
-SOURCES = ("teal_kernels.hip", "teal_attention.hip", "teal_gemv_w16_f16.hip", "teal_gemv_w16_bf16.hip",
+SOURCES = ("teal_kernels.hip", "teal_attention.hip", "teal_sampler.hip", "teal_gemv_w16_f16.hip", "teal_gemv_w16_bf16.hip",
            "teal_gemv_w8_f16.hip", "teal_gemv_w8_bf16.hip", "teal_gemv_fast_f16.hip", "teal_gemv_fast_bf16.hip", "teal_gemv_int4.hip",
            "teal_gemv_fast_w8_f16.hip", "teal_gemv_fast_w8_bf16.hip", "teal_comparators.hip", "teal_prefill.hip",
            "teal_speculative.hip", "teal_batched.hip", "teal_prefix.hip")
 # translation units whose kernels take their hot arguments as scalar parameters: the command processor preloads the
 # first 11 dwords into SGPRs at wave launch (no scalar-cache miss before the first activation load)
 PRELOAD = {"teal_gemv_fast_f16.hip": 12, "teal_gemv_fast_bf16.hip": 12, "teal_gemv_fast_w8_f16.hip": 12,
-           "teal_gemv_fast_w8_bf16.hip": 12, "teal_attention.hip": 12}
+           "teal_gemv_fast_w8_bf16.hip": 12, "teal_attention.hip": 12, "teal_sampler.hip": 12}
 # No packed-fp32 instruction (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32) in any kernel of the library (round 6).  Measured on
 # MI355X: while ANOTHER process's skinny rocBLAS / hipBLASLt GEMM (Tensile MT64x32x256 / MT32x16x256, a 24-token F.linear) shares
 # the GPU, the LOW half of v_pk_fma_f32 results is dropped now and then for a whole row group — every decode step next to such a
@@ -54,13 +54,14 @@ LIB_PATH = os.path.join(_PKG, "libteal_hip.so")  # the in-tree PRODUCT library: 
 DIAG_LIB_PATH = os.path.join(_PKG, "libteal_hip_diag.so")
 # TEAL_LIB_PATH: load() opens another build of the library (same C ABI) instead — same-box A/B of two builds.  build() never
 # writes there (an override pointing at an older build must not be overwritten by the current tree), and symbols that build
-# lacks are tolerated (OPTIONAL_WITH_OVERRIDE).
+# lacks are tolerated (OPTIONAL_WITH_OVERRIDE): their callers fail when they reach them.  The engines reach
+# teal_decode_attention_split_plan in their constructor, so an engine cannot be built on a library older than that query.
 LIB_OVERRIDE = os.environ.get("TEAL_LIB_PATH") or None
 OPTIONAL_WITH_OVERRIDE = ("teal_decode_attention_split_roped", "teal_prefill_gemm", "teal_prefill_resid_norm", "teal_prefill_attention",
                           "teal_verify_attention_ws_bytes", "teal_verify_attention", "teal_spec_accept_scratch_bytes", "teal_spec_accept",
                           "teal_batched_sparse_gemm", "teal_batched_round_rows", "teal_batched_decode_attention_ws_bytes",
                           "teal_batched_decode_attention", "teal_batched_sparse_gemm_slots", "teal_batched_decode_attention_slots",
-                          "teal_batched_retire", "teal_sample_topk_slot", "teal_kv_copy_rows")
+                          "teal_batched_retire", "teal_sample_topk_slot", "teal_kv_copy_rows", "teal_decode_attention_split_plan")
 
 # every symbol include/teal_hip.h declares
 EXPORTS = (
@@ -73,7 +74,7 @@ EXPORTS = (
     "teal_verify_attention_ws_bytes", "teal_verify_attention", "teal_spec_accept_scratch_bytes", "teal_spec_accept",
     "teal_batched_sparse_gemm", "teal_batched_round_rows", "teal_batched_decode_attention_ws_bytes", "teal_batched_decode_attention",
     "teal_batched_sparse_gemm_slots", "teal_batched_decode_attention_slots", "teal_batched_retire", "teal_sample_topk_slot",
-    "teal_kv_copy_rows",
+    "teal_kv_copy_rows", "teal_decode_attention_split_plan",
 )
 
 # what libteal_hip_diag.so exports on top (include/teal_hip.h, #ifdef TEAL_DIAGNOSTICS); libteal_hip.so must export NONE of them
@@ -196,6 +197,8 @@ def _open(path: str, diag: bool) -> ctypes.CDLL:
         L.teal_decode_attention_split_roped.argtypes = [vp, vp, vp, vp, vp, vp, cf, ci, ci, ci, ci, ci, vp, sz, ci, vp, sz, vp]
     L.teal_decode_attention.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
     L.teal_get_config.argtypes = [ci, ci, ci, ctypes.POINTER(ci)]
+    if hasattr(L, "teal_decode_attention_split_plan"):
+        L.teal_decode_attention_split_plan.argtypes = [ci, ci, ci, ci, ci, ci, ctypes.POINTER(ci)]
     if hasattr(L, "teal_prefill_gemm"):
         L.teal_prefill_gemm.argtypes = [vp, vp, ci, ci, vp, ci, ci, vp, sz, ci, ci, ci, ctypes.POINTER(ci), vp]  # (teal_prefill_in_t*, ...)
         L.teal_prefill_resid_norm.argtypes = [vp, vp, ci, vp, vp, ci, vp, cf, ci, vp, vp, vp, vp, ci, vp]

@@ -298,7 +298,7 @@ __device__ __forceinline__ int lane_rank(unsigned long long mask) {
                                      __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
-// ---- the fused sampler's random stream and top-k selection (teal_attention.hip: sample_*; teal_speculative.hip: the accept
+// ---- the fused sampler's random stream and top-k selection (teal_sampler.hip: sample_*; teal_speculative.hip: the accept
 //      kernel draws from the same stream and keeps the same top-k set) ----
 __device__ __forceinline__ uint32_t order_key16(uint32_t b, bool bf16) {
     (void)bf16;  // fp16 and bf16 share sign-magnitude ordering

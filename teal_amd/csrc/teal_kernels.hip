@@ -4,7 +4,8 @@
 //
 //   teal_gemv_kernel.h          the sparse GEMV kernel template (the hot kernel; design notes there)
 //   teal_gemv_w*_*.hip          its instantiations, one translation unit per (weight width, dtype)
-//   teal_attention.hip          decode attention + fused sampler and their entry points
+//   teal_attention.hip          decode attention, its launch plan and entry points
+//   teal_sampler.hip            fused top-k sampler and its entry points
 //
 // Replaces (reference tree FasterDecoding/TEAL @ 2024-10-22):
 //   kernels/sparse_gemv.py:87-142   splitk_sparse_gemv (host wrapper, autotune, grid)  -> run_gemv

@@ -14,8 +14,8 @@ separate kernel):
   5. down    [x = silu(gate) * up] -> mask(tau_down) -> GEMV                                -> fp32 slabs
   lm_head    [h = resid + round(sum down-slabs); x = RMSNorm(h) * w] -> dense GEMV           -> logits
 
-All through the C ABI (teal_fused_gemv / teal_decode_attention); PyTorch only owns the buffers and
-the stream.  The rounding points are those of the reference's fp16/bf16 tensors, so logits agree
+All through the C ABI (teal_fused_gemv / teal_decode_attention_split_ws / _split_roped); PyTorch only owns
+the buffers and the stream.  The rounding points are those of the reference's fp16/bf16 tensors, so logits agree
 with the unfused module path to fp16 rounding (tests/test_engine.py).
 """
 from __future__ import annotations
@@ -140,6 +140,43 @@ class DecodeEngine:
             return "model is not on a HIP device"
         return None
 
+    @staticmethod
+    def attention_choice(n_head: int, n_kv: int, hd: int, max_seq: int, quantised: bool, att_split: int = 0):
+        """(att_split, att_fused_merge, rope_epilogue) of a decode step over this rank's heads; needs the library, no device.
+        Attention is flash-decoding: 4 or 8 workgroups per head write split-KV partials that the wo launch merges in its
+        prologue (no extra launch); very long contexts / wide models: up to 16 splits + a merge launch.  att_split > 0
+        overrides the split count (benchmark A/B)."""
+        L, out = _lib.load(), (ctypes.c_int * 4)()
+
+        def plan(nsplit):  # (grouped-query kernel?, does its LDS at nsplit fit the limit?)
+            _lib.check(L.teal_decode_attention_split_plan(n_head, n_kv, hd, max_seq, nsplit, 0, out), "teal_decode_attention_split_plan")
+            return out[0] == 1, out[2] <= out[3]
+
+        qdim = n_head * hd
+        grouped = plan(1)[0]  # (a property of the shape, whatever the split count)
+        if att_split:
+            ns = int(att_split)
+        elif grouped:
+            # grouped-query kernel (decode_attention_gqa_kernel): one workgroup per (KV head, split) reads each K/V row once
+            # for the whole group; ~one workgroup per CU, more splits if the scores of a share would not fit its LDS limit;
+            # merged by the merge launch
+            ns = min(64, max(8, 256 // n_kv))
+            while ns < 64 and not plan(ns)[1]:
+                ns *= 2
+        elif max_seq <= 1024:
+            ns = 4
+        elif max_seq <= 4096 and qdim <= 8192:
+            ns = 8
+        elif max_seq <= 2048:
+            ns = 4
+        else:
+            ns = min(16, max(2, (256 + n_head - 1) // n_head, (max_seq + 2047) // 2048))
+        fused_merge = (ns == 4 and qdim <= 16384) or (ns == 8 and qdim <= 8192)
+        # RoPE + KV-cache append in the epilogue of the wqkv launch (TEAL_OUT_QKV_ROPE: -1.3 % per token on Llama-2-7B @ 50 %,
+        # profiles/r04_layer_experiments.txt) wherever that launch runs without split-K (the library reports which way it
+        # went) and the per-query-head attention kernel follows (the grouped-query kernel of long contexts rotates itself)
+        return ns, fused_merge, not quantised and not grouped
+
     def __init__(self, model: Transformer, thresholds: List[Dict[str, float]], pair: Optional[bool] = None,
                  att_split: int = 0, reduce_presummed: Optional[bool] = None):
         why = DecodeEngine.supports(model)
@@ -228,35 +265,9 @@ class DecodeEngine:
         self.rope = model.freqs_cis.contiguous()
         assert self.rope.dtype == dt and self.rope.shape[1:] == (hd // 2, 2)
         self.max_seq = model.max_seq_length
-        # attention (flash-decoding): 4 or 8 workgroups per head write split-KV partials that the wo launch
-        # merges in its prologue (no extra launch); very long contexts / wide models: up to 16 splits + a
-        # merge launch.  att_split > 0 overrides (benchmark A/B).
-        rep = cfg.n_head // cfg.n_local_heads
-        if att_split:
-            self.att_split = int(att_split)
-        elif (rep == 8 and self.max_seq >= 2048) or (rep == 4 and self.max_seq >= 4096):
-            # grouped-query kernel (teal_attention.hip: decode_attention_gqa_kernel): one workgroup per (KV head, split)
-            # reads each K/V row once for the whole group; ~one workgroup per CU, more splits if the scores of a share
-            # would not fit the LDS budget (kGqaMaxLds); merged by the merge launch (or by wo at 4 / 8 splits)
-            ns = min(64, max(8, 256 // cfg.n_local_heads))
-            while ns < 64 and self._gqa_lds_bytes(rep, hd, self.max_seq, ns) > 128 * 1024:
-                ns *= 2
-            self.att_split = ns
-        elif self.max_seq <= 1024:
-            self.att_split = 4
-        elif self.max_seq <= 4096 and qdim <= 8192:
-            self.att_split = 8
-        elif self.max_seq <= 2048:
-            self.att_split = 4
-        else:
-            self.att_split = min(16, max(2, (256 + cfg.n_head - 1) // cfg.n_head, (self.max_seq + 2047) // 2048))
-        self.att_fused_merge = (self.att_split == 4 and qdim <= 16384) or (self.att_split == 8 and qdim <= 8192)
-        # RoPE + KV-cache append in the epilogue of the wqkv launch (TEAL_OUT_QKV_ROPE: -1.3 % per token on Llama-2-7B @ 50 %,
-        # profiles/r04_layer_experiments.txt) wherever that launch runs without split-K (the library reports which way it
-        # went) and the per-query-head attention kernel follows (the grouped-query kernel of long contexts rotates itself)
-        gqa_kernel = (rep == 8 and self.max_seq >= 2048) or (rep == 4 and self.max_seq >= 4096)
-        self.rope_epilogue = bool(self.att_split) and not (self.int8 or self.int4) and not gqa_kernel
-        self.att_ws = e(cfg.n_head * max(1, self.att_split) * (hd + 2), dtype=torch.float32)
+        self.att_split, self.att_fused_merge, self.rope_epilogue = DecodeEngine.attention_choice(
+            cfg.n_head, cfg.n_local_heads, hd, self.max_seq, self.int8 or self.int4, att_split)
+        self.att_ws = e(cfg.n_head * self.att_split * (hd + 2), dtype=torch.float32)
         self.eps = float(cfg.norm_eps)
         self.n_wo = ctypes.c_int(0)
         self.n_down = ctypes.c_int(0)
@@ -310,7 +321,7 @@ class DecodeEngine:
                        seg(at.wqkv, qdim + kv, kv, th["v"], self.qkv.data_ptr() + 2 * (qdim + kv))]
             # split attention: the projection writes fp32 slabs that the attention launch sums itself, so a narrow
             # (GQA) wqkv is row-sliced over all CUs without a reduce launch in between
-            k1_out = _out(k1_segs, TEAL_OUT_SLABS, self.s_qkv) if self.att_split else _out(k1_segs, TEAL_OUT_ROUNDED)
+            k1_out = _out(k1_segs, TEAL_OUT_SLABS, self.s_qkv)
             if self.rope_epilogue:
                 kc0, vc0 = at.kv_cache.k_cache, at.kv_cache.v_cache
                 k1_out.mode = TEAL_OUT_QKV_ROPE  # y[0] = rotated q; falls back to the slabs when the launch needs split-K
@@ -397,18 +408,9 @@ class DecodeEngine:
             hook("after", "head", -1)
         return self.logits if logits_out is None else logits_out
 
-    @staticmethod
-    def _gqa_lds_bytes(rep: int, hd: int, max_seq: int, nsplit: int) -> int:
-        """LDS of the grouped-query attention launch (mirrors attention_split_impl in teal_attention.hip)."""
-        nw = 8
-        step = nw * (64 // (hd // 8))
-        local = (((max_seq + step - 1) // step + nsplit - 1) // nsplit) * step
-        return ((rep + 2) * (hd // 2) + 2 * rep * nw + rep * max(local, nw * hd)) * 4
-
     def _layer(self, i: int, tok_ptr: int, pos_ptr: int, hook=None, only=None):
         """The five launches of layer i (module docstring).  `only` (measurements: stage_times): launch just these stages, on
         whatever the buffers hold from the last full step."""
-        cfg = self.cfg
         k1_in, k1_out, kc, vc, k3_in, k3_out, k4_in, k4_out, k5_in, k5_out, tau_o = self.stages[i]
         cb = hook if hook else (lambda *a: None)
         if only is not None:
@@ -420,31 +422,10 @@ class DecodeEngine:
         if self.rope_epilogue:
             k1_out.rope_pos = pos_ptr
         cb("before", "qkv", i)
-        self._gemv(k1_in, k1_out, self.dim, self.n_qkv if self.att_split else None)
+        self._gemv(k1_in, k1_out, self.dim, self.n_qkv)
         cb("after", "qkv", i)
-        ymask = self.y_mask.data_ptr() if self.pair else None
         cb("before", "attn", i)
-        if self.att_split and self.rope_epilogue and self.n_qkv.value == 0:
-            # the projection's epilogue rotated q (self.qkv[:dim]) and appended the token's k / v rows
-            rc = self.L.teal_decode_attention_split_roped(self.qkv.data_ptr(), pos_ptr, kc.data_ptr(), vc.data_ptr(),
-                                                          None if self.att_fused_merge else self.y_attn.data_ptr(), ymask, tau_o,
-                                                          cfg.n_head, cfg.n_local_heads, cfg.head_dim, self.max_seq,
-                                                          self.att_split, self.att_ws.data_ptr(), self.att_ws.numel() * 4,
-                                                          self.code, self.ws.data_ptr(), self.ws.numel() * 4, self._stream)
-        elif self.att_split:
-            # (with y requested — long contexts / grouped-query shapes — a merge launch follows the split launch)
-            rc = self.L.teal_decode_attention_split_ws(None, self.s_qkv.data_ptr(), self.n_qkv.value, self.rope.data_ptr(), pos_ptr,
-                                                       kc.data_ptr(), vc.data_ptr(),
-                                                       None if self.att_fused_merge else self.y_attn.data_ptr(), ymask, tau_o,
-                                                       cfg.n_head, cfg.n_local_heads, cfg.head_dim, self.max_seq,
-                                                       self.att_split, self.att_ws.data_ptr(), self.att_ws.numel() * 4,
-                                                       self.code, self.ws.data_ptr(), self.ws.numel() * 4, self._stream)
-        else:
-            rc = self.L.teal_decode_attention_masked(self.qkv.data_ptr(), self.rope.data_ptr(), pos_ptr, kc.data_ptr(), vc.data_ptr(),
-                                                     self.y_attn.data_ptr(), ymask, tau_o, cfg.n_head, cfg.n_local_heads,
-                                                     cfg.head_dim, self.max_seq, self.code, self._stream)
-        if rc != 0:
-            _lib.check(rc, "teal_decode_attention")
+        self._attention(i, pos_ptr)
         cb("after", "attn", i)
         cb("before", "wo", i)
         self._gemv(k3_in, k3_out, self.qdim, self.n_wo)
@@ -461,8 +442,25 @@ class DecodeEngine:
             self._reduce_slabs("down")
         cb("after", "down", i)
 
+    def _attention(self, i: int, pos_ptr: int):
+        """Layer i's split attention launch.  Merged by wo (att_fused_merge): partials only; else y, and y's keep masks for a
+        paired wo, are requested and a merge launch follows the split launch (long contexts / grouped-query shapes)."""
+        cfg, (_, _, kc, vc, *_, tau_o) = self.cfg, self.stages[i]
+        y, ymask = None, None
+        if not self.att_fused_merge:
+            y, ymask = self.y_attn.data_ptr(), (self.y_mask.data_ptr() if self.pair else None)
+        tail = (y, ymask, tau_o, cfg.n_head, cfg.n_local_heads, cfg.head_dim, self.max_seq, self.att_split, self.att_ws.data_ptr(),
+                self.att_ws.numel() * 4, self.code, self.ws.data_ptr(), self.ws.numel() * 4, self._stream)
+        if self.rope_epilogue and self.n_qkv.value == 0:
+            # the projection's epilogue rotated q (self.qkv[:dim]) and appended the token's k / v rows
+            rc = self.L.teal_decode_attention_split_roped(self.qkv.data_ptr(), pos_ptr, kc.data_ptr(), vc.data_ptr(), *tail)
+        else:
+            rc = self.L.teal_decode_attention_split_ws(None, self.s_qkv.data_ptr(), self.n_qkv.value, self.rope.data_ptr(), pos_ptr,
+                                                       kc.data_ptr(), vc.data_ptr(), *tail)
+        if rc != 0:
+            _lib.check(rc, "teal_decode_attention_split")
+
     def _layer_only(self, i: int, tok_ptr: int, pos_ptr: int, only):
-        cfg = self.cfg
         k1_in, k1_out, kc, vc, k3_in, k3_out, k4_in, k4_out, k5_in, k5_out, tau_o = self.stages[i]
         if "qkv" in only:
             if i == 0:
@@ -471,21 +469,10 @@ class DecodeEngine:
                 k1_in.nslabs = self.n_down.value
             if self.rope_epilogue:
                 k1_out.rope_pos = pos_ptr
-            self._gemv(k1_in, k1_out, self.dim, self.n_qkv if self.att_split else None)
+            self._gemv(k1_in, k1_out, self.dim, self.n_qkv)
         if "attn" in only:
-            assert self.att_split and self.att_fused_merge, "stage timing covers the split attention merged by wo"
-            if self.rope_epilogue and self.n_qkv.value == 0:
-                rc = self.L.teal_decode_attention_split_roped(self.qkv.data_ptr(), pos_ptr, kc.data_ptr(), vc.data_ptr(), None, None, tau_o,
-                                                              cfg.n_head, cfg.n_local_heads, cfg.head_dim, self.max_seq, self.att_split,
-                                                              self.att_ws.data_ptr(), self.att_ws.numel() * 4, self.code, self.ws.data_ptr(),
-                                                              self.ws.numel() * 4, self._stream)
-            else:
-                rc = self.L.teal_decode_attention_split_ws(None, self.s_qkv.data_ptr(), self.n_qkv.value, self.rope.data_ptr(), pos_ptr,
-                                                           kc.data_ptr(), vc.data_ptr(), None, None, tau_o, cfg.n_head, cfg.n_local_heads,
-                                                           cfg.head_dim, self.max_seq, self.att_split, self.att_ws.data_ptr(),
-                                                           self.att_ws.numel() * 4, self.code, self.ws.data_ptr(), self.ws.numel() * 4, self._stream)
-            if rc != 0:
-                _lib.check(rc, "teal_decode_attention")
+            assert self.att_fused_merge, "stage timing covers the split attention merged by wo"
+            self._attention(i, pos_ptr)
         if "wo" in only:
             self._gemv(k3_in, k3_out, self.qdim, self.n_wo)
         if "gate_up" in only:

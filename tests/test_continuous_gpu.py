@@ -1,4 +1,4 @@
-"""GPU: continuous batching (the slot entry points of teal_batched.hip / teal_attention.hip, SlotDecodeEngine, ContinuousBatcher).
+"""GPU: continuous batching (the slot entry points of teal_batched.hip / teal_sampler.hip, SlotDecodeEngine, ContinuousBatcher).
 
   1. teal_batched_sparse_gemm_slots with inactive slots = teal_batched_sparse_gemm of the compacted batch, bit for bit, with the
      same kept counts; inactive slab columns exactly 0; NaN / Inf in the inactive hand-over changes no bit;

@@ -1,6 +1,6 @@
 """CPU: continuous batching (teal_batched.hip's slot entry points, teal_amd/gpt_fast/continuous.py) — what needs no GPU.
 
-  * the slot kernels (teal_batched.hip, and the slot-predicated sampler in teal_attention.hip) build for gfx950 with no scratch
+  * the slot kernels (teal_batched.hip, and the slot-predicated sampler in teal_sampler.hip) build for gfx950 with no scratch
     and no VGPR spills, and the new entry points are exported and declared;
   * ContinuousBatcher against a fake engine that restates the device rule (retire on budget / EOS, per-request draws):
     FIFO admission, slot reuse, min(budget, up to EOS) tokens per request, refill="all", refusals;
@@ -39,7 +39,7 @@ def test_slot_kernels_do_not_spill_to_scratch(tmp_path):
     slot = {n: v for n, v in res.items() if "ELb1EEEv" in n or "retire" in n}  # the SLOTS = true instantiations and the retire launch
     assert len(slot) >= 24 + 4 + 2 + 1, sorted(slot)
     assert all(v == (0, 0) for v in slot.values()), {n: v for n, v in slot.items() if v != (0, 0)}
-    res = _resources(tmp_path, "teal_attention.hip")
+    res = _resources(tmp_path, "teal_sampler.hip")
     samp = {n: v for n, v in res.items() if "slot_kernel" in n}
     assert len(samp) == 8, sorted(samp)
     # (the 16-vectors-per-thread window sampler — Llama-3's vocabulary — spills in its plain form already, 1024 threads leave it

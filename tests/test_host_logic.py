@@ -338,22 +338,63 @@ def test_weight_images_keep_rows_on_128_byte_lines():
         assert ((N + ROW_PAD) * 2) % 128 == 0 and (N + 128) % 128 == 0 and (N + INT4_ROW_PAD_BYTES) % 128 == 0, N
 
 
+# (att_split, att_fused_merge, rope_epilogue) of DecodeEngine for 16-bit weights, by (n_head, n_kv, head_dim), at SPLIT_CHOICE_SEQS:
+# what the engine chose before the launch plan moved into the library (its own restatement of the launcher's thresholds
+# and LDS formula), recorded from that code.  int8 / int4 weights: rope_epilogue 0, the rest equal.
+SPLIT_CHOICE_SEQS = (64, 1024, 1025, 2047, 2048, 4095, 4096, 4097, 8192, 16384, 32768, 131072)
+SPLIT_CHOICE = {
+    (32, 32, 128): [(4, 1, 1), (4, 1, 1), (8, 1, 1), (8, 1, 1), (8, 1, 1), (8, 1, 1), (8, 1, 1), (8, 1, 1), (8, 1, 1), (8, 1, 1), (16, 0, 1), (16, 0, 1)],
+    (32, 8, 128): [(4, 1, 1), (4, 1, 1), (8, 1, 1), (8, 1, 1), (8, 1, 1), (8, 1, 1), (32, 0, 0), (32, 0, 0), (32, 0, 0), (32, 0, 0), (32, 0, 0), (32, 0, 0)],
+    (40, 40, 128): [(4, 1, 1), (4, 1, 1), (8, 1, 1), (8, 1, 1), (8, 1, 1), (8, 1, 1), (8, 1, 1), (7, 0, 1), (7, 0, 1), (8, 1, 1), (16, 0, 1), (16, 0, 1)],
+    (64, 8, 128): [(4, 1, 1), (4, 1, 1), (8, 1, 1), (8, 1, 1), (32, 0, 0), (32, 0, 0), (32, 0, 0), (32, 0, 0), (32, 0, 0), (32, 0, 0), (32, 0, 0), (64, 0, 0)],
+    (8, 1, 128): [(4, 1, 1), (4, 1, 1), (8, 1, 1), (8, 1, 1), (64, 0, 0), (64, 0, 0), (64, 0, 0), (64, 0, 0), (64, 0, 0), (64, 0, 0), (64, 0, 0), (64, 0, 0)],
+    (8, 2, 64): [(4, 1, 1), (4, 1, 1), (8, 1, 1), (8, 1, 1), (8, 1, 1), (8, 1, 1), (64, 0, 0), (64, 0, 0), (64, 0, 0), (64, 0, 0), (64, 0, 0), (64, 0, 0)],
+    (16, 2, 64): [(4, 1, 1), (4, 1, 1), (8, 1, 1), (8, 1, 1), (64, 0, 0), (64, 0, 0), (64, 0, 0), (64, 0, 0), (64, 0, 0), (64, 0, 0), (64, 0, 0), (64, 0, 0)],
+}
+
+
 def test_engine_grouped_query_split_choice_mirrors_the_launcher():
-    """engine.py picks the split count of the grouped-query attention launch from the same LDS formula and limits as
-    attention_split_impl (teal_attention.hip); a drift would silently fall back to the per-query-head kernel."""
-    import re
+    """The split attention launch is decided in one place, the library (teal_decode_attention_split_plan reports what
+    attention_split_impl launches from); DecodeEngine sizes its split count by that query.  Part one: the query's numbers.
+    Part two: the engine's choice over shapes and cache lengths, against the recorded table."""
+    import ctypes
+    from teal_amd import _lib
     from teal_amd.gpt_fast.engine import DecodeEngine
-    src = open(os.path.join(ROOT, "teal_amd", "csrc", "teal_attention.hip")).read()
-    assert re.search(r"kGqaMinSeq\s*=\s*4096;", src) and re.search(r"kGqaMinSeq8\s*=\s*2048;", src)
-    assert re.search(r"kGqaMaxLds\s*=\s*128\s*\*\s*1024;", src)
-    eng_src = open(os.path.join(ROOT, "teal_amd", "gpt_fast", "engine.py")).read()
-    assert "(rep == 8 and self.max_seq >= 2048) or (rep == 4 and self.max_seq >= 4096)" in eng_src and "> 128 * 1024" in eng_src
-    f = DecodeEngine._gqa_lds_bytes
+    _lib.build()
+    L, out = _lib.load(), (ctypes.c_int * 4)()
+
+    def plan(n_head, n_kv, hd, max_seq, nsplit, roped=0):
+        out[:] = [-1] * 4
+        assert L.teal_decode_attention_split_plan(n_head, n_kv, hd, max_seq, nsplit, roped, out) == 0
+        return list(out)
+
     # Llama-2-70B shapes: 8 query heads per KV head, head_dim 128, 16 k positions, 32 splits -> 512 rows per share
-    assert f(8, 128, 16384, 32) == ((8 + 2) * 64 + 2 * 8 * 8 + 8 * max(512, 8 * 128)) * 4
+    assert plan(64, 8, 128, 16384, 32) == [1, 512, ((8 + 2) * 64 + 2 * 8 * 8 + 8 * max(512, 8 * 128)) * 4, 131072]
+    assert plan(8, 2, 64, 4096, 8) == [1, 512, ((4 + 2) * 32 + 2 * 4 * 8 + 4 * max(512, 8 * 64)) * 4, 131072]
     # a share's scores grow with the cache length and shrink with the split count
-    assert f(8, 128, 131072, 32) > 128 * 1024 >= f(8, 128, 131072, 64)
-    assert f(4, 64, 4096, 8) == ((4 + 2) * 32 + 2 * 4 * 8 + 4 * max(512, 8 * 64)) * 4
+    assert plan(64, 8, 128, 131072, 32)[2] > 131072 >= plan(64, 8, 128, 131072, 64)[2]
+    # which shapes take the grouped-query kernel: 8 heads per KV head from 2048 positions, 4 from 4096, no others, never roped
+    assert [plan(64, 8, 128, m, 32)[0] for m in (2047, 2048)] == [0, 1] and [plan(32, 8, 128, m, 32)[0] for m in (4095, 4096)] == [0, 1]
+    for n_head in (8, 16, 40):  # 1, 2, 5 heads per KV head
+        assert plan(n_head, 8, 128, 131072, 64)[0] == 0
+    assert plan(64, 8, 128, 16384, 32, roped=1)[0] == 0 and plan(32, 8, 128, 16384, 32, roped=1)[0] == 0
+    # the per-query-head kernel: 16 waves for shares above 128 rows, 4 below; {q, k, v, reductions, per-wave o, scores} in 64 KiB
+    assert plan(32, 32, 128, 4096, 8) == [0, 1024, (3 * 128 + 2 * 16 + 16 * 128 + 512) * 4, 65536]
+    assert plan(32, 32, 64, 512, 4) == [0, 256, (3 * 64 + 2 * 4 + 4 * 64 + 128) * 4, 65536]
+    # the arguments the launch refuses
+    assert L.teal_decode_attention_split_plan(64, 8, 128, 4096, 8, 0, None) == -1  # TEAL_ERR_ARG
+    for bad in ((64, 8, 96, 4096, 8), (64, 7, 128, 4096, 8), (0, 8, 128, 4096, 8), (64, 0, 128, 4096, 8), (64, 8, 128, 0, 8),
+                (64, 8, 128, 4096, 0), (64, 8, 128, 4096, 65)):
+        assert L.teal_decode_attention_split_plan(*bad, 0, out) == -3, bad  # TEAL_ERR_SHAPE
+
+    for (n_head, n_kv, hd), row in SPLIT_CHOICE.items():
+        assert len(row) == len(SPLIT_CHOICE_SEQS)
+        for max_seq, (ns, fused, rope) in zip(SPLIT_CHOICE_SEQS, row):
+            assert DecodeEngine.attention_choice(n_head, n_kv, hd, max_seq, False) == (ns, bool(fused), bool(rope)), (n_head, n_kv, hd, max_seq)
+            assert DecodeEngine.attention_choice(n_head, n_kv, hd, max_seq, True) == (ns, bool(fused), False), (n_head, n_kv, hd, max_seq)
+    # an override replaces the split count only
+    assert DecodeEngine.attention_choice(32, 32, 128, 4096, False, 16) == (16, False, True)
+    assert DecodeEngine.attention_choice(64, 8, 128, 4096, False, 8) == (8, True, False)
 
 
 def test_measurement_scripts_compile():
