@@ -493,6 +493,42 @@ int teal_sample_topk_slot(const void* logits, int vocab, int dtype, int top_k, f
                           int32_t* pos_inout, int32_t* history, int history_len, void* ws, size_t ws_bytes, const int32_t* active, int slot,
                           void* stream);
 
+/* ---- token log-probabilities, teal_amd/csrc/teal_logprob.hip ---------------------------------------------------------------
+ * For a row of `vocab` 16-bit logits l and a token t:  lp(t) = (l[t] - m) - log sum_v exp(l[v] - m),  m = max_v l[v],  in fp32
+ * (expf / logf).  The MODEL's distribution: temperature 1, no top-k filter, whatever the sampler was told.  A logit of -inf
+ * contributes 0; NaN logits, +inf logits and a row that is all -inf are outside the contract; a token outside 0 .. vocab-1 gives
+ * NaN.  One workgroup per row, no workspace: a row's results depend only on that row's logits and token (not on B, the slot or
+ * the other rows) and replays are bit-identical.
+ * Both: vocab a multiple of 8 in 8..131072 (else TEAL_ERR_SHAPE); null required pointers TEAL_ERR_ARG; a row base (or, B > 1, a
+ * stride) off 16 bytes TEAL_ERR_ALIGN; every check comes before any HIP call. */
+
+/* One launch after the B samplers of a step (before teal_batched_retire).  Row r < B serves slot slot0 + r.
+ *   c = rng_state[r][1]   (uint64 [B][2]: the draw counter the sampler has just bumped)
+ *   i = c - 1
+ *   t = tokens[r]
+ * If 0 <= i < lp_len:
+ *   lp[r * lp_len + i] = lp(t)
+ *   if top_n > 0: top_ids / top_lp[(r * lp_len + i) * top_n + j], j < top_n, are the ids and logprobs of the top_n largest logits
+ *     of the row, by descending logit, equal logits (-0 = +0) by ascending id.
+ * Otherwise nothing is written.
+ * active != NULL: a row whose bit (slot0 + r) of active[0] (device int32) is clear writes nothing.
+ * logits_stride is in elements.  TEAL_ERR_ARG also: top_n outside 0..8 (top_ids / top_lp required when > 0), B outside 1..8,
+ * slot0 < 0 or slot0 + B > 32, lp_len <= 0. */
+int teal_token_logprobs(const void* logits, size_t logits_stride, int vocab, int dtype, int B, const int32_t* tokens,
+                        const void* rng_state, float* lp, int lp_len, int top_n, int32_t* top_ids, float* top_lp,
+                        const int32_t* active, int slot0, void* stream);
+/* Teacher forcing: takes the sampler's place in a scoring loop (one graph replay = one position).
+ *   p = pos_inout[0]
+ *   j = p + 1
+ * If 0 <= j < n_targets:
+ *   t = targets[j]
+ *   lp[j] = lp(t) from `logits`
+ *   token_out[0] = t
+ *   pos_inout[0] = j
+ * Otherwise nothing changes, so replaying past the end is harmless. */
+int teal_score_step(const void* logits, int vocab, int dtype, const int32_t* targets, int n_targets, int32_t* token_out,
+                    int32_t* pos_inout, float* lp, void* stream);
+
 /* ---- shared prompt prefixes of continuous batching, teal_amd/csrc/teal_prefix.hip ------------------------------------
  * A prefix is a token sequence whose K / V rows (every layer) are computed once and kept in a device store; a request that names
  * it is admitted by copying those rows into its slot's caches and running a prompt pass over its own tokens only. */

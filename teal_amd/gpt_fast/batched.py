@@ -25,6 +25,7 @@ import torch
 from .. import _lib, runtime
 from ..kernels.sparse_gemv import BATCH_MAX, batched_segs
 from ..monkeypatch import UP_SHIFT_BYTES, to_column_major
+from . import logprobs as LP
 from .model import Transformer
 from .prefill import IN_NORM, IN_SILU_MUL, IN_XT, MAX_T, PrefillEngine, PrefillIn
 from .speculative import VerifyPass
@@ -122,6 +123,7 @@ class BatchedDecodeEngine:
         self._seed = 1234
         self._graph = None
         self._graph_key = None
+        self._lp: Optional[LP.LogprobBuffers] = None  # set_logprobs
         kvw = self.kv
         self._segs = [{
             "qkv": batched_segs([self.dim, self.dim + kvw, self.nqkv], [t["q"], t["k"], t["v"]]),
@@ -205,6 +207,30 @@ class BatchedDecodeEngine:
                                             self.history[b].data_ptr(), self.history.shape[1], self.ws.data_ptr(), self.ws.numel() * 4, st)
             if rc != 0:
                 _lib.check(rc, "teal_sample_topk (batched)")
+        if self._lp is not None:
+            self._lp.launch(self.logits, V, V, self.code, self.B, self.tok_buf, self.rng_state, st=st)
+
+    # ---- token log-probabilities (logprobs.py): one launch behind the B samplers, only when switched on ----------------------
+    def set_logprobs(self, n: Optional[int]):
+        """None: off (the default; the step's launches are exactly those without this feature).  0: every token a step draws gets
+        its logprob under the model's own distribution (temperature 1, no top-k filter); 1..8: and the ids and logprobs of that
+        many most likely tokens.  Entry i of sequence b belongs to history[b, i].  Drops the captured graph."""
+        n = LP.check_setting(n)
+        self._lp = None if n is None else LP.LogprobBuffers(self.B, self.history.shape[1], n, self.history.device)
+        self._graph = None
+
+    def _logprobs(self) -> LP.LogprobBuffers:
+        if self._lp is None:
+            raise RuntimeError("logprobs are off (set_logprobs)")
+        return self._lp
+
+    def read_logprobs(self, n: int):
+        """(lp [B, n], top_ids [B, n, top_n], top_lp [B, n, top_n]) of the tokens history[:, :n] — decode_n's"""
+        return self._logprobs().read(slice(None), 0, n)
+
+    def _loop_state(self):
+        """what the captured step carries from replay to replay (the capture's warm-up step is undone on these)"""
+        return [self.tok_buf, self.pos_buf, self.rng_state, self.history] + (list(self._lp.tensors()) if self._lp is not None else [])
 
     def _self_step(self, temperature, top_k):
         self._step()
@@ -213,10 +239,10 @@ class BatchedDecodeEngine:
     def capture(self, temperature: float = 0.8, top_k: Optional[int] = 200):
         """hipGraph of one step for all B sequences: the forward pass and B sampler launches (each sequence's token, position and
         draw counter stay on the device).  The warm-up step's state is put back."""
-        key = (float(temperature), int(top_k or 0))
+        key = (float(temperature), int(top_k or 0), None if self._lp is None else self._lp.top_n)
         if self._graph is not None and self._graph_key == key:
             return self._graph
-        state = (self.tok_buf.clone(), self.pos_buf.clone(), self.rng_state.clone(), self.history.clone())
+        state = [t.clone() for t in self._loop_state()]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -233,7 +259,7 @@ class BatchedDecodeEngine:
         return g
 
     def _restore(self, state):
-        for dst, src in zip((self.tok_buf, self.pos_buf, self.rng_state, self.history), state):
+        for dst, src in zip(self._loop_state(), state):
             dst.copy_(src)
 
     def manual_seed(self, seed: int):
@@ -449,6 +475,9 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         st = runtime.stream_ptr()
         for b in range(self.B):
             self._sample_slot(b, self.logits[b], temperature, top_k, st)
+        if self._lp is not None:  # predicated on the active word the samplers saw (retire clears bits behind it)
+            V = self.cfg.vocab_size
+            self._lp.launch(self.logits, V, V, self.code, self.B, self.tok_buf, self.rng_state, active=self._active, st=st)
         self._retire((1 << self.B) - 1, True, st)
 
     def capture(self, temperature: float = 0.8, top_k: Optional[int] = 200):
@@ -592,6 +621,9 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         self.slot_state[SLOT_ACTIVE:SLOT_ACTIVE + 1].bitwise_or_(1 << s)
         st = runtime.stream_ptr()
         self._sample_slot(s, logits, temperature, top_k, st)
+        if self._lp is not None:  # the request's first token: entry 0 of its row
+            self._lp.launch(logits, 0, self.cfg.vocab_size, self.code, 1, self.tok_buf[s:], self.rng_state[s], row0=s,
+                            active=self._active, st=st)
         self._retire(1 << s, False, st)
 
     # ---- the batcher's view ------------------------------------------------------------------------------------------------
@@ -614,6 +646,12 @@ class SlotDecodeEngine(BatchedDecodeEngine):
 
     def read_history(self, slot: int, n: int) -> List[int]:
         return self.history[slot, :n].tolist()
+
+    def read_logprobs(self, slot: int, n: int):
+        """(lp, top_ids, top_lp) of the tokens read_history(slot, n) returns, as lists: n floats, n lists of top_n ids, n lists of
+        top_n floats"""
+        lp, ids, tlp = self._logprobs().read(slot, 0, n)
+        return lp.tolist(), ids.tolist(), tlp.tolist()
 
     def union_kept(self) -> Dict[str, float]:
         """per projection: the mean over layers and over the bursts whose last step had an active slot of the fraction of rows

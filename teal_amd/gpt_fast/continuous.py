@@ -155,10 +155,14 @@ class ContinuousBatcher:
     temperature, top_k), run_steps(k, temperature, top_k, use_graph), read_state() (the slot state words, one copy),
     read_history(slot, n) and union_kept().  `prefixes` (id -> tokens): the engine also offers has_prefix(id),
     register_prefix(id, tokens) and admit(..., prefix=id); run() registers every prefix the engine does not hold yet before its
-    first admission, and only requests that name a prefix are admitted with `prefix=`."""
+    first admission, and only requests that name a prefix are admitted with `prefix=`.  `logprobs` (None: off; 0: each token's
+    logprob under the model's own distribution — temperature 1, no top-k filter; 1..8: and that many most likely alternates): the
+    engine also offers set_logprobs(n), called once before the first admission, and read_logprobs(slot, n) -> (lp, top_ids,
+    top_lp) lists aligned with read_history(slot, n); the result gains "logprobs" and, for n > 0, "top_logprobs"."""
 
     def __init__(self, engine, sync_every: int = 8, refill: str = "free", temperature: float = 0.8, top_k: Optional[int] = 200,
-                 seed: int = 1234, use_graph: bool = True, prefixes: Optional[Dict[str, List[int]]] = None):
+                 seed: int = 1234, use_graph: bool = True, prefixes: Optional[Dict[str, List[int]]] = None,
+                 logprobs: Optional[int] = None):
         if refill not in REFILL:
             raise ValueError(f"refill must be one of {REFILL}")
         if int(sync_every) < 1:
@@ -166,6 +170,9 @@ class ContinuousBatcher:
         self.eng, self.K, self.refill = engine, int(sync_every), refill
         self.temperature, self.top_k, self.seed, self.use_graph = temperature, top_k, int(seed), use_graph
         self.prefixes = {k: [int(t) for t in v] for k, v in (prefixes or {}).items()}
+        if logprobs is not None and (isinstance(logprobs, bool) or not isinstance(logprobs, int) or not 0 <= logprobs <= 8):
+            raise ValueError("logprobs must be None or an integer in 0..8")
+        self.logprobs, self._logprobs_set = logprobs, False
 
     def _clock(self):
         try:
@@ -194,7 +201,12 @@ class ContinuousBatcher:
         for name, toks in self.prefixes.items():  # once per prefix, before the first admission (the engine is idle)
             if not eng.has_prefix(name):
                 eng.register_prefix(name, toks)
+        if self.logprobs is not None and not self._logprobs_set:  # once: it drops the engine's captured step
+            eng.set_logprobs(self.logprobs)
+            self._logprobs_set = True
         pending = deque(range(len(requests)))
+        lps: List[Optional[List[float]]] = [None] * len(requests)
+        tops: List[Optional[List]] = [None] * len(requests)
         slot_req: List[Optional[int]] = [None] * B
         admitted_at = [0] * B
         out: List[Optional[List[int]]] = [None] * len(requests)
@@ -229,6 +241,10 @@ class ContinuousBatcher:
                 if r is None or (state[SLOT_ACTIVE] >> s) & 1:
                     continue
                 out[r] = eng.read_history(s, state[SLOT_PRODUCED + s])
+                if self.logprobs is not None:
+                    lp, ids, tlp = eng.read_logprobs(s, state[SLOT_PRODUCED + s])
+                    lps[r] = [float(v) for v in lp]
+                    tops[r] = [[(int(i), float(v)) for i, v in zip(ii, vv)] for ii, vv in zip(ids, tlp)]
                 slot_steps += state[SLOT_FINISH + s] - admitted_at[s]
                 slot_req[s] = None
         c1 = self._clock()
@@ -238,7 +254,13 @@ class ContinuousBatcher:
         wall_dev = self._seconds(c0, c1)
         t_admit = sum(self._seconds(a, b) for a, b in admit_spans)
         useful = sum(len(o) for o in out)
+        extra = {}
+        if self.logprobs is not None:
+            extra["logprobs"] = lps
+            if self.logprobs > 0:
+                extra["top_logprobs"] = tops
         return {
+            **extra,
             "tokens": out, "slots": slots_used, "steps": steps, "admissions": admissions, "wall_s": wall,
             "admission_s": t_admit, "admission_share": t_admit / wall_dev if wall_dev > 0 else 0.0,
             "mean_active_slots": slot_steps / steps if steps else 0.0, "useful_tokens": useful,

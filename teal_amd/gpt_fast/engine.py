@@ -27,6 +27,7 @@ from typing import Dict, List, Optional
 import torch
 
 from .. import _lib, runtime
+from . import logprobs as LP
 from ..monkeypatch import UP_SHIFT_BYTES, to_column_major
 from .model import Transformer
 
@@ -279,6 +280,8 @@ class DecodeEngine:
         self.pos_buf = torch.zeros(1, dtype=torch.int32, device=dev)      # loop-carried position
         self.history = torch.zeros(max(8, model.max_seq_length), dtype=torch.int32, device=dev)
         self._graph, self._graph_key, self._graphs = None, None, {}
+        self._lp: Optional[LP.LogprobBuffers] = None  # set_logprobs
+        self._score_targets = self._score_lp = None   # score
         self._build(thresholds)
 
     # ---- static launch descriptors (pointers never change: hipGraph-capture friendly) -------------
@@ -650,6 +653,11 @@ class DecodeEngine:
                         "up": k4_out.tau[1], "down": k5_out.tau[0]})
         return out
 
+    def set_thresholds(self, ths: List[Dict[str, float]]):
+        """new launch descriptors from `ths`; the captured graphs (which hold the old ones) are dropped"""
+        self._build(ths)
+        self._graph = None
+
     @torch.no_grad()
     def kept_fractions(self, idx: torch.Tensor, input_pos: torch.Tensor) -> Dict[str, float]:
         """Achieved kept fraction of every projection's input on the decode activations of one step (mean over layers)."""
@@ -702,8 +710,7 @@ class DecodeEngine:
                 for p, site in self.SITE.items():
                     s = float(sparsities[p][i])
                     ths[i][p] = -1.0 if s <= 0 else float(torch.quantile(cat[site], s))
-            self._build(ths)
-            self._graph = None
+            self.set_thresholds(ths)
         return ths
 
     @torch.no_grad()
@@ -742,14 +749,40 @@ class DecodeEngine:
     def _self_step(self, temperature, top_k):
         logits = self(self.tok_buf, self.pos_buf)
         self.sample_fused(logits, temperature, top_k, feed=True)
+        if self._lp is not None:
+            self._record_logprobs(logits, self.tok_buf)
 
-    def capture_loop(self, temperature: float, top_k: Optional[int], tokens: int = 1):
-        """hipGraph of `tokens` consecutive decode steps (token, position and RNG counter stay on the device between them, so
-        a graph can span any number of tokens; each replay costs one host launch and one graph boundary on the GPU)."""
+    # ---- token log-probabilities (logprobs.py): one more launch behind the sampler, only when switched on -------------------
+    def set_logprobs(self, n: Optional[int]):
+        """None: off (the default; the step's launches are exactly those without this feature).  0: every token the fused sampler
+        draws gets its logprob under the model's own distribution (temperature 1, no top-k filter); 1..8: and the ids and logprobs
+        of that many most likely tokens.  Entry i belongs to history[i] (read_logprobs).  Drops the captured graphs."""
+        n = LP.check_setting(n)
+        if n is not None and self.reduce is not None:
+            raise NotImplementedError("logprobs are not available under tensor parallelism: this rank's lm_head holds a slice of "
+                                      "the vocabulary, and the logprob launch reads whole rows")
+        self._lp = None if n is None else LP.LogprobBuffers(1, self.history.numel(), n, self.history.device)
+        self._graph = None
+
+    def _record_logprobs(self, logits: torch.Tensor, token: torch.Tensor):
+        self._lp.launch(logits, 0, self.cfg.vocab_size, self.code, 1, token, self.rng_state)
+
+    def read_logprobs(self, drawn: int, n: int):
+        """(lp [n], top_ids [n, top_n], top_lp [n, top_n]) of the tokens history[drawn : drawn + n] — decode_n(..., drawn=drawn)'s"""
+        if self._lp is None:
+            raise RuntimeError("logprobs are off (set_logprobs)")
+        return self._lp.read(0, drawn, n)
+
+    def _loop_state(self):
+        """what a captured step carries from replay to replay (a capture's warm-up step is undone on these)"""
+        return [self.tok_buf, self.pos_buf, self.rng_state] + (list(self._lp.tensors()) if self._lp is not None else []) + \
+               ([self._score_lp] if self._score_lp is not None else [])
+
+    def _capture(self, key, step):
+        """hipGraph of step(), cached under `key` until the thresholds or the logprob setting change"""
         if self.reduce is not None and not getattr(self.reduce, "capturable", False):
             raise RuntimeError("this tensor-parallel engine's all-reduce cannot be captured into a hipGraph (gloo / host-staged); "
                                "decode eagerly (use_graph=False) or run the ranks over RCCL")
-        key = (float(temperature), int(top_k or 0), int(tokens))
         if self._graph is not None and self._graph_key == key:
             return self._graph
         if self._graph is None:
@@ -757,23 +790,37 @@ class DecodeEngine:
         if key in self._graphs:
             self._graph, self._graph_key = self._graphs[key], key
             return self._graph
-        state = (self.tok_buf.clone(), self.pos_buf.clone(), self.rng_state.clone())
+        bufs = self._loop_state()
+        state = [b.clone() for b in bufs]
+
+        def restore():
+            for b, v in zip(bufs, state):
+                b.copy_(v)
+
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):  # warm-up outside capture (KV rows it writes are rewritten by the real run)
-            self._self_step(temperature, top_k)
+            step()
         torch.cuda.current_stream().wait_stream(s)
-        self.tok_buf.copy_(state[0]); self.pos_buf.copy_(state[1]); self.rng_state.copy_(state[2])
+        restore()
         g = torch.cuda.CUDAGraph()
         try:
             with runtime.graph_capture(g):
-                for _ in range(int(tokens)):
-                    self._self_step(temperature, top_k)
+                step()
         finally:  # (also when the capture fails — decode_n then decodes a sharded model eagerly from the same state)
-            self.tok_buf.copy_(state[0]); self.pos_buf.copy_(state[1]); self.rng_state.copy_(state[2])
+            restore()
         self._graphs[key] = g
         self._graph, self._graph_key = g, key
         return g
+
+    def capture_loop(self, temperature: float, top_k: Optional[int], tokens: int = 1):
+        """hipGraph of `tokens` consecutive decode steps (token, position and RNG counter stay on the device between them, so
+        a graph can span any number of tokens; each replay costs one host launch and one graph boundary on the GPU)."""
+        def steps():
+            for _ in range(int(tokens)):
+                self._self_step(temperature, top_k)
+
+        return self._capture((float(temperature), int(top_k or 0), int(tokens), None if self._lp is None else self._lp.top_n), steps)
 
     @torch.no_grad()
     def begin_sequence(self):
@@ -786,7 +833,10 @@ class DecodeEngine:
         the torch sampler of generate.sample takes ~10): opens the sample's random stream; follow with decode_n(..., drawn=1)"""
         assert logits_row.is_contiguous() and logits_row.numel() == self.cfg.vocab_size and logits_row.dtype == self.dtype
         self.begin_sequence()
-        return self.sample_fused(logits_row, temperature, top_k, feed=False)
+        tok = self.sample_fused(logits_row, temperature, top_k, feed=False)
+        if self._lp is not None:
+            self._record_logprobs(logits_row, tok)
+        return tok
 
     def decode_n(self, first_token: torch.Tensor, pos: int, n: int, temperature: float = 0.8,
                  top_k: Optional[int] = 200, use_graph: bool = True, drawn: int = 0) -> torch.Tensor:
@@ -821,6 +871,42 @@ class DecodeEngine:
             for _ in range(n):
                 self._self_step(temperature, top_k)
         return self.history[drawn:drawn + n].clone()  # (the sampler files a token under its draw counter)
+
+    # ---- teacher-forced scoring: the decode step with teal_score_step in the sampler's place --------------------------------
+    def _score_step(self):
+        logits = self(self.tok_buf, self.pos_buf)
+        rc = self.L.teal_score_step(logits.data_ptr(), self.cfg.vocab_size, self.code, self._score_targets.data_ptr(),
+                                    self._score_targets.numel(), self.tok_buf.data_ptr(), self.pos_buf.data_ptr(),
+                                    self._score_lp.data_ptr(), runtime.stream_ptr())
+        if rc != 0:
+            _lib.check(rc, "teal_score_step")
+
+    @torch.no_grad()
+    def score(self, tokens, use_graph: bool = True) -> torch.Tensor:
+        """fp32 [T - 1]: entry j - 1 = log p(tokens[j] | tokens[:j]) under the model's own distribution (temperature 1, no top-k
+        filter), j = 1 .. T-1.  Teacher forcing from an empty cache: position 0 is fed tokens[0] and EVERY position runs the
+        ordinary decode step at the engine's thresholds (one hipGraph replay per position); T - 1 <= max_seq positions."""
+        toks = torch.as_tensor(tokens).view(-1)
+        T = int(toks.numel())
+        if T < 2 or T - 1 > self.max_seq:
+            raise ValueError(f"score: {T} tokens (need 2 .. {self.max_seq + 1}: positions 0 .. T-2 must fit the cache of {self.max_seq} rows)")
+        if self._score_targets is None:
+            dev = self.history.device
+            self._score_targets = torch.zeros(self.max_seq + 1, dtype=torch.int32, device=dev)
+            self._score_lp = torch.zeros(self.max_seq + 1, dtype=torch.float32, device=dev)
+        self._score_targets[:T].copy_(toks.to(torch.int32))
+        self.tok_buf.copy_(self._score_targets[:1].view(1, 1))
+        self.pos_buf.fill_(0)
+        if self.reduce is not None and not getattr(self.reduce, "capturable", False):
+            use_graph = False  # host-staged all-reduce (gloo): the step cannot live in a hipGraph
+        if use_graph:
+            g = self._capture(("score",), self._score_step)
+            for _ in range(T - 1):
+                g.replay()
+        else:
+            for _ in range(T - 1):
+                self._score_step()
+        return self._score_lp[1:T].clone()
 
     # nn.Module-ish surface so GraphedDecoder can drive either a Transformer or an engine
     @property

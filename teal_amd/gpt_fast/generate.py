@@ -645,6 +645,31 @@ def check_batched_args(args) -> int:
     return B
 
 
+def check_logprobs_args(args) -> Optional[int]:
+    """--logprobs: None (off), 0 (each generated token's logprob) or 1..8 (and that many most likely alternates); every refusal
+    is raised here, before anything is loaded.  The logprobs come from a launch inside the fused engines' step, so the flag
+    needs an engine path: --compile / --engine (one sequence or --batch_size) or --requests."""
+    n = getattr(args, "logprobs", None)
+    if n is None:
+        return None
+    if not 0 <= int(n) <= 8:
+        raise SystemExit(f"--logprobs must be in 0..8 (alternates per token), got {n}")
+    if getattr(args, "draft_checkpoint_path", None) is not None or getattr(args, "self_speculate", False):
+        raise SystemExit("--logprobs does not combine with speculative decoding")
+    if int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1"))) > 1:
+        raise SystemExit("--logprobs does not run under tensor parallelism (a rank's lm_head holds a slice of the vocabulary)")
+    if getattr(args, "dense", False) or (not args.synthetic and args.hist_path is None):
+        raise SystemExit("--logprobs needs TEAL thresholds (--hist_path, or --synthetic): the fused engines run patched models only")
+    if getattr(args, "requests", None) is None and (getattr(args, "no_engine", False) or not (args.compile or args.engine)):
+        raise SystemExit("--logprobs needs a fused engine (--compile or --engine, without --no_engine, or --requests): the module "
+                         "path returns token ids only")
+    return int(n)
+
+
+def _mean_logprob_line(lps) -> str:
+    return f"    mean logprob {sum(lps) / max(1, len(lps)):.4f} over {len(lps)} tokens (model distribution, temperature 1)"
+
+
 @torch.no_grad()
 def run_batched(args, model: Transformer, thresholds, prompts: torch.Tensor, tokenizer, use_engine: bool) -> Dict:
     """prompts [B, T]: a dense prompt pass through the module path at batch B, then max_new_tokens - 1 steps through
@@ -663,7 +688,12 @@ def run_batched(args, model: Transformer, thresholds, prompts: torch.Tensor, tok
             eng = BatchedDecodeEngine(model, thresholds, B)
         else:
             print(f"batched engine not used: {why}")
-    tps, seqs = [], []
+    n_lp = getattr(args, "logprobs", None)
+    if n_lp is not None:
+        if eng is None:
+            raise SystemExit("--logprobs: the batched engine cannot run this model, and the module path returns token ids only")
+        eng.set_logprobs(n_lp)
+    tps, seqs, lps, tops = [], [], [], []
     for i in range(-1 if args.compile else 0, args.num_samples):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -689,9 +719,15 @@ def run_batched(args, model: Transformer, thresholds, prompts: torch.Tensor, tok
             continue
         tps.append(B * n_new / t)
         seqs.append(seq.tolist())
+        if n_lp is not None:  # of the tokens the engine drew: seq[:, T + 1:] (the first comes from the prompt pass's torch sampler)
+            lp, ids, tlp = eng.read_logprobs(n_new - 1)
+            lps.append(lp.tolist())
+            tops.append([[list(zip(a, b_)) for a, b_ in zip(ii, vv)] for ii, vv in zip(ids.tolist(), tlp.tolist())])
         for b in range(B):
             text = tokenizer.decode(seq[b].tolist()) if tokenizer is not None else seq[b, T:].tolist()
             print(f"[sample {i + 1}, sequence {b}] {text}")
+            if n_lp is not None and tokenizer is not None:
+                print(_mean_logprob_line(lps[-1][b]))
         print(f"Time for inference {i + 1}: {t:.02f} sec total, {tps[-1]:.02f} tokens/sec aggregate, "
               f"{tps[-1] / B:.02f} tokens/sec per sequence (batch {B})")
     print("==========")
@@ -699,7 +735,9 @@ def run_batched(args, model: Transformer, thresholds, prompts: torch.Tensor, tok
     print(f"Average tokens/sec: {mean:.2f} aggregate, {mean / B:.2f} per sequence")
     print(f"Memory used: {torch.cuda.max_memory_reserved() / 1e9:.02f} GB")
     return {"tokens_per_sec": tps, "mean_tokens_per_sec": mean, "mean_tokens_per_sec_per_sequence": mean / B, "batch_size": B,
-            "thresholds": thresholds, "decoder": type(eng).__name__ if eng is not None else "module", "sequences": seqs}
+            "thresholds": thresholds, "decoder": type(eng).__name__ if eng is not None else "module", "sequences": seqs,
+            **({"logprobs": lps, "logprob_offset": T + 1} if n_lp is not None else {}),
+            **({"top_logprobs": tops} if n_lp else {})}
 
 
 # ------------------------------------------------------------------------------------------------
@@ -751,7 +789,7 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer) -> Dict:
         raise SystemExit(f"--requests: the batched engine cannot run this model: {why}")
     eng = SlotDecodeEngine(model, thresholds, B)
     batcher = ContinuousBatcher(eng, sync_every=args.sync_every, temperature=args.temperature, top_k=args.top_k, seed=1234,
-                                use_graph=bool(args.compile), prefixes=prefixes)
+                                use_graph=bool(args.compile), prefixes=prefixes, logprobs=getattr(args, "logprobs", None))
     try:
         for name, toks in prefixes.items():  # once, before the warm-up run
             eng.register_prefix(name, toks)
@@ -768,6 +806,8 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer) -> Dict:
     for i, toks in enumerate(res["tokens"]):
         text = tokenizer.decode(prefixes.get(reqs[i].prefix, []) + reqs[i].tokens + toks) if tokenizer is not None else toks
         print(f"[request {i}, slot {res['slots'][i]}] {text}")
+        if "logprobs" in res and tokenizer is not None:
+            print(_mean_logprob_line(res["logprobs"][i]))
     tps = res["useful_tokens_per_sec"]
     print(f"{len(reqs)} requests, {res['useful_tokens']} useful tokens in {res['wall_s']:.2f} s: {tps:.2f} tokens/sec; "
           f"{res['steps']} steps, {res['mean_active_slots']:.2f} active slots of {B} on average, "
@@ -780,7 +820,8 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer) -> Dict:
             "decoder": type(batcher).__name__, "sequences": res["tokens"], "steps": res["steps"], "admissions": res["admissions"],
             "admission_share": res["admission_share"], "mean_active_slots": res["mean_active_slots"], "union_kept": res["union_kept"],
             "sync_every": res["sync_every"], "prefix_admissions": res["prefix_admissions"],
-            "prefix_rows_reused": res["prefix_rows_reused"], "prefix_paths": res["prefix_paths"]}
+            "prefix_rows_reused": res["prefix_rows_reused"], "prefix_paths": res["prefix_paths"],
+            **{k: res[k] for k in ("logprobs", "top_logprobs") if k in res}}
 
 
 def sample_batch(logits: torch.Tensor, temperature: float, top_k: Optional[int]) -> torch.Tensor:
@@ -793,6 +834,7 @@ def main(args) -> Dict:
     assert "cuda" in device, "the sparse decode path is GPU-only (HIP kernels, no CPU fallback)"
     spec = check_speculative_args(args)  # before anything is loaded
     batch = check_batched_args(args)
+    n_lp = check_logprobs_args(args)
     if getattr(args, "prefixes", None) is not None and getattr(args, "requests", None) is None:
         raise SystemExit("--prefixes names shared prefixes of continuous batching: it needs --requests")
     if getattr(args, "requests", None) is not None:
@@ -875,6 +917,8 @@ def main(args) -> Dict:
         assert thresholds is not None, "--engine needs thresholds (--hist_path or --synthetic)"
         decoder = EngineDecoder(model, thresholds, use_graph, args.temperature, args.top_k)
         relayout_for_engine(model)
+    if n_lp is not None and not use_engine:
+        raise SystemExit("--logprobs: the fused engine cannot run this model, and the module path returns token ids only")
     # --compile captures the prompt pass as well (one hipGraph per prompt length; the reference compiles `prefill` only under
     # --compile_prefill, generate.py:423-425 — its Inductor compile takes minutes, a capture here takes milliseconds, and the
     # eager pass is ~400 launches = nine decode steps' worth for a 6-token prompt).  The prefill stays DENSE
@@ -886,7 +930,7 @@ def main(args) -> Dict:
         # the decode step's weight images, dense); longer prompts, quantised or sharded models: the pass above
         from teal_amd.gpt_fast.prefill import FusedPrefill
         prefill = FusedPrefill(model, graph=use_graph, fallback=prefill)
-    tps, seqs = [], []
+    tps, seqs, lps, tops, lp_offsets = [], [], [], [], []
     start = -1 if args.compile else 0
     for i in range(start, args.num_samples):
         if getattr(args, "interactive", False) and i >= 0:
@@ -900,6 +944,11 @@ def main(args) -> Dict:
             prof = torch.profiler.profile()
         t0 = time.perf_counter()
         with prof:
+            if n_lp is not None:
+                # (the engine is built on the caches generate() is about to set up — the same sizes — and rebuilt when they move)
+                model.setup_caches(max_batch_size=1, max_seq_length=min(prompt.size(0) + args.max_new_tokens, model.config.block_size))
+                if decoder.model._lp is None:
+                    decoder.model.set_logprobs(n_lp)
             y = generate(model, prompt, args.max_new_tokens, decoder, temperature=args.temperature, top_k=args.top_k,
                          prefill=prefill)
         torch.cuda.synchronize()
@@ -914,6 +963,15 @@ def main(args) -> Dict:
         seqs.append(y.tolist())
         if tokenizer is not None:
             print(tokenizer.decode(y.tolist()))
+        if n_lp is not None:  # of the tokens the fused sampler drew: the last `drawn` of y (all the new ones on the usual path)
+            eng = decoder.model
+            drawn = int(eng.rng_state[1].item())
+            lp, ids, tlp = eng.read_logprobs(0, drawn)
+            lps.append(lp.tolist())
+            tops.append([list(zip(a, b_)) for a, b_ in zip(ids.tolist(), tlp.tolist())])
+            lp_offsets.append(y.size(0) - drawn)
+            if tokenizer is not None:
+                print(_mean_logprob_line(lps[-1]))
         print(f"Time for inference {i + 1}: {t:.02f} sec total, {tps[-1]:.02f} tokens/sec")
         print(f"Bandwidth achieved: {model_size * tps[-1] / 1e9:.02f} GB/s (dense parameter bytes x tok/s, as the reference reports)")
     print("==========")
@@ -928,7 +986,8 @@ def main(args) -> Dict:
     print(f"Memory used: {torch.cuda.max_memory_reserved() / 1e9:.02f} GB")
     pre_name = None if prefill is None else type(prefill).__name__ + (f":{prefill.used}" if getattr(prefill, "used", None) else "")
     return {"tokens_per_sec": tps, "mean_tokens_per_sec": mean, "thresholds": thresholds, "decoder": type(decoder).__name__,
-            "sequences": seqs, "prefill": pre_name}
+            "sequences": seqs, "prefill": pre_name,
+            **({"logprobs": lps, "logprob_offset": lp_offsets} if n_lp is not None else {}), **({"top_logprobs": tops} if n_lp else {})}
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -981,6 +1040,9 @@ def build_parser() -> argparse.ArgumentParser:
                    "\"prefix\": \"sys\" gives only its own suffix and reuses the prefix's K / V rows, computed once")
     p.add_argument("--eos_id", type=int, default=None, help="with --requests: a request also ends right after this token id (off "
                    "by default: budgets alone end requests)")
+    p.add_argument("--logprobs", type=int, default=None, help="return each generated token's log-probability under the model's own "
+                   "distribution (temperature 1, no top-k filter) and the N most likely alternates (0..8; 0: the token's only); "
+                   "engine paths only: --compile / --engine, --batch_size, --requests")
     p.add_argument("--sync_every", type=int, default=8, help="with --requests: steps per burst between two looks at the slot state")
     return p
 
