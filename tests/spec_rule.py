@@ -26,6 +26,7 @@ def uniform(h):
 
 def order_key16(bits):
     b = bits.astype(np.uint32)
+    b = np.where(b == 0x8000, 0, b)  # -0.0 keys as +0.0 (teal_common.h)
     return np.where(b & 0x8000, (~b) & 0xFFFF, b | 0x8000)
 
 

@@ -192,18 +192,36 @@ def test_fused_sampler_topk_and_distribution():
             out.append(int(tok.item()))
         return out
 
-    assert draw(3, 50, 1e-6) == [int(logits.float().argmax())] * 3      # T -> 0: argmax
+    import sampler_rule
+    bits = logits.view(torch.int16).cpu().numpy().view(np.uint16)
+
+    def same_as_model(got, top_k, temp, ctr0):
+        """the host model's tokens for the same counters (tests/sampler_rule.py); an open draw may be its runner-up"""
+        mt, mr, mo = sampler_rule.draws(bits, False, top_k, temp, 77, ctr0, len(got))
+        got = np.array(got)
+        assert mo.mean() <= 0.01 and ((got == mt) | (mo & (got == mr))).all(), (top_k, temp, np.flatnonzero(got != mt)[:8].tolist())
+        return mt, int(mo.sum())
+
+    argmax3 = draw(3, 50, 1e-6)
+    assert argmax3 == [int(logits.float().argmax())] * 3                # T -> 0: argmax
     assert int(state[1]) == 3                                            # counter bumped per draw
+    same_as_model(argmax3, 50, 1e-6, 0)
     k = 8
     top = set(torch.topk(logits.float(), k).indices.tolist())
     draws = draw(400, k, 1.0)
+    model_tokens, n_open = same_as_model(draws, k, 1.0, 3)
     assert set(draws) <= top and len(set(draws)) >= 4                    # only top-k, and it does vary
     # empirical frequencies ~ softmax over the top-k
     idx = torch.topk(logits.float(), k).indices
     p = torch.softmax(logits.float()[idx], dim=0).cpu().numpy()
     freq = np.array([draws.count(int(i)) for i in idx]) / len(draws)
     assert np.abs(freq - p).max() < 0.08
-    assert len(set(draw(200, 0, 1.0))) > 20                              # no filter: wide support
+    # ... and are exactly the frequency table the model gives for counters 3 .. 402 (up to the draws it calls open)
+    model_freq = np.array([(model_tokens == int(i)).sum() for i in idx]) / len(draws)
+    assert np.abs(freq - model_freq).max() <= n_open / len(draws)
+    wide = draw(200, 0, 1.0)
+    assert len(set(wide)) > 20                                           # no filter: wide support
+    same_as_model(wide, 0, 1.0, 403)
 
 
 def test_engine_device_resident_loop_matches_stepwise():

@@ -134,6 +134,11 @@ def _sample_ref(L, logits, V, code, top_k, temperature, seed, dim):
     _lib.check(L.teal_sample_topk_ws(logits.data_ptr(), V, code, top_k, temperature, rng.data_ptr(), tok.data_ptr(), pos.data_ptr(), None, 0,
                                      ws.data_ptr(), ws.numel() * 4, runtime.stream_ptr()), "sampler")
     torch.cuda.synchronize()
+    import numpy as np
+    import sampler_rule
+    bits = logits.view(torch.int16).cpu().numpy().view(np.uint16)
+    token, runner_up, is_open = sampler_rule.draw(bits, logits.dtype == torch.bfloat16, top_k, temperature, seed, 0)
+    assert int(tok.item()) == token or (is_open and int(tok.item()) == runner_up)  # the host model of the draw (tests/sampler_rule.py)
     return int(tok.item())
 
 
