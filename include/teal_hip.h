@@ -340,7 +340,9 @@ int teal_sample_topk_ws(const void* logits, int vocab, int dtype, int top_k, flo
  * the decode step's own weight images.  Every hand-over is TRANSPOSED, [feature][R] with R = 8 for T <= 8 and R = 16 for
  * 9 <= T <= 16 (every call of one pass takes the same T, hence the same R; "[..][8]" below reads "[..][R]"): the tokens of a
  * feature in one or two 16-byte words (16-bit activations: xt, ht, yt) or R / 4 of them (fp32 slabs [slice][feature][R]); token
- * slots >= T of the 16-bit vectors are written as zero, of the slabs left untouched (consumers ignore them).  1 <= T <= 16.
+ * slots >= T of the 16-bit vectors are written as zero; of the slabs, which are written in token pairs, slot T of an odd T is zero (a
+ * TEAL_PREFILL_IN_XT launch takes xt's slot T as given: zero from every producer here) and slots >= 2 * ceil(T / 2) are left
+ * untouched (consumers ignore them).  1 <= T <= 16.
  * Floating-point results: fp32 sums, the rounding points of the module path's 16-bit tensors. */
 
 /* What a GEMM launch builds its activations from (every workgroup builds the rows of its own slice, once, while staging them) */
@@ -434,8 +436,10 @@ typedef struct teal_batched_segs {
 } teal_batched_segs_t;
 
 /* slabs[slice][n][8] (fp32) = sum over the slice's rows m that sequence b keeps under its column's segment threshold of
- * W^T[m][n] * x_b[m], b < B <= 8 (slots >= B zero); inputs, weights and the slab contract as teal_prefill_gemm (Z, n0, n1 multiples
- * of 256).  Every weight row that some sequence keeps (the union) is read once; no other row is loaded.  counts (optional, int32
+ * W^T[m][n] * x_b[m], b < B <= 8; inputs, weights and the slab contract as teal_prefill_gemm (Z, n0, n1 multiples of 256).  Slots are
+ * written in pairs: slots B .. 2 * ceil(B / 2) - 1 are exactly zero whatever the hand-over holds there, slots >= 2 * ceil(B / 2) and
+ * the slabs of slices >= *split_out are left untouched (every consumer reads slots < B only; tests/test_exact_gemm_gpu.py pins
+ * this).  Every weight row that some sequence keeps (the union) is read once; no other row is loaded.  counts (optional, int32
  * [16][3][9]): slice k's row counts under segment s — counts[k][s][b] rows kept by sequence b, counts[k][s][8] rows of the union —
  * written for slices k < *split_out (sum them over k; entries of absent segments are not written). */
 int teal_batched_sparse_gemm(const teal_prefill_in_t* in, const teal_batched_segs_t* segs, const void* w0T, int ld0, int n0, const void* w1T,
