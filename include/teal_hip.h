@@ -533,6 +533,30 @@ int teal_token_logprobs(const void* logits, size_t logits_stride, int vocab, int
 int teal_score_step(const void* logits, int vocab, int dtype, const int32_t* targets, int n_targets, int32_t* token_out,
                     int32_t* pos_inout, float* lp, void* stream);
 
+/* ---- per-request logit processors, teal_amd/csrc/teal_logit_adjust.hip -----------------------------------------------------
+ * One launch between a step's logits and its samplers: repetition, frequency and presence penalty and a logit bias, per row.
+ * For element v of row r, with w = state[r][v] (bit 31: v occurs in the request's prompt; low 31 bits n: how often v was
+ * generated), {theta, alpha_p, alpha_f, reserved} = params[r] and b = bias[r] (or no bias):
+ *   x = float(logits[r][v])
+ *   if w != 0:   x = x > 0 ? x / theta : x * theta
+ *   if n > 0:    x = x - alpha_f * float(n);  x = x - alpha_p
+ *   if bias:     x = x + float(b[v])
+ *   out[r][v] = round-to-nearest-even(min(max(x, -MAXF), MAXF)),  MAXF = the dtype's largest finite value
+ * every operation a separately rounded fp32 operation (no fused multiply-add).  `out` never holds an infinity: a logit of -inf
+ * leaves as -MAXF.  NaN logits are outside the contract.  theta = 1, alphas 0, no bias: out equals logits as values (with a bias
+ * row, -0 leaves as +0).
+ * count_token != 0: before element t = tokens[r] is adjusted, the count of state[r][t] goes up by one (it stays at 2^31 - 1); a
+ * token outside 0 .. vocab-1 counts nothing.  No other state word is written; no atomics, no workspace: replays are bit-identical.
+ * Row r < B serves slot slot0 + r.  active != NULL: a row whose bit (slot0 + r) of active[0] (device int32) is clear changes
+ * nothing — no count, its `out` row untouched.  state: int32 [B][vocab]; params: fp32 [B][4]; bias: [B][vocab] of the dtype, or
+ * NULL; strides in elements.  `out` must not overlap `logits` (the logprob launch goes on reading the raw rows): TEAL_ERR_ARG.
+ * vocab a multiple of 8 in 8..131072 (else TEAL_ERR_SHAPE); B outside 1..8, slot0 < 0, slot0 + B > 32 or a null required pointer
+ * TEAL_ERR_ARG; TEAL_ERR_DTYPE; a row base (or, B > 1, a stride) off 16 bytes TEAL_ERR_ALIGN; every check comes before any HIP
+ * call. */
+int teal_logit_adjust(const void* logits, size_t logits_stride, int vocab, int dtype, int B, const int32_t* tokens, int count_token,
+                      int32_t* state, const float* params, const void* bias, void* out, size_t out_stride, const int32_t* active,
+                      int slot0, void* stream);
+
 /* ---- shared prompt prefixes of continuous batching, teal_amd/csrc/teal_prefix.hip ------------------------------------
  * A prefix is a token sequence whose K / V rows (every layer) are computed once and kept in a device store; a request that names
  * it is admitted by copying those rows into its slot's caches and running a prompt pass over its own tokens only. */

@@ -25,6 +25,7 @@ import torch
 from .. import _lib, runtime
 from ..kernels.sparse_gemv import BATCH_MAX, batched_segs
 from ..monkeypatch import UP_SHIFT_BYTES, to_column_major
+from . import logit_processors as PR
 from . import logprobs as LP
 from .model import Transformer
 from .prefill import IN_NORM, IN_SILU_MUL, IN_XT, MAX_T, PrefillEngine, PrefillIn
@@ -124,6 +125,7 @@ class BatchedDecodeEngine:
         self._graph = None
         self._graph_key = None
         self._lp: Optional[LP.LogprobBuffers] = None  # set_logprobs
+        self._proc: Optional[PR.LogitProcessors] = None  # set_logit_processors
         kvw = self.kv
         self._segs = [{
             "qkv": batched_segs([self.dim, self.dim + kvw, self.nqkv], [t["q"], t["k"], t["v"]]),
@@ -201,8 +203,12 @@ class BatchedDecodeEngine:
     # ---- sampling and the device-resident loop ----------------------------------------------------
     def _sample(self, temperature: float, top_k: Optional[int]):
         st, V = runtime.stream_ptr(), self.cfg.vocab_size
+        src = self.logits
+        if self._proc is not None:  # tok_buf still holds the tokens this step was fed: each sequence's latest
+            self._proc.launch(self.logits, V, self.B, self.tok_buf, True, st=st)
+            src = self._proc.adj
         for b in range(self.B):
-            rc = self.L.teal_sample_topk_ws(self.logits[b].data_ptr(), V, self.code, int(top_k or 0), float(temperature),
+            rc = self.L.teal_sample_topk_ws(src[b].data_ptr(), V, self.code, int(top_k or 0), float(temperature),
                                             self.rng_state[b].data_ptr(), self.tok_buf[b:].data_ptr(), self.pos_buf[b:].data_ptr(),
                                             self.history[b].data_ptr(), self.history.shape[1], self.ws.data_ptr(), self.ws.numel() * 4, st)
             if rc != 0:
@@ -219,6 +225,33 @@ class BatchedDecodeEngine:
         self._lp = None if n is None else LP.LogprobBuffers(self.B, self.history.shape[1], n, self.history.device)
         self._graph = None
 
+    # ---- per-request logit processors (logit_processors.py): one launch in front of the B samplers, only when switched on ----
+    def set_logit_processors(self, on: bool):
+        """off (the default): the step's launches are exactly those without this feature.  on: every step adjusts its logits by
+        each sequence's repetition / presence / frequency penalty and logit bias (set_slot_processors; identity until set) into a
+        buffer of their own, which the samplers read; logprobs and `logits` stay the model's.  Drops the captured graph."""
+        V = self.cfg.vocab_size
+        self._proc = PR.LogitProcessors(self.B, V, self.dtype, self.logits.device) if on else None
+        self._graph = None
+
+    def _processors(self) -> PR.LogitProcessors:
+        if self._proc is None:
+            raise RuntimeError("logit processors are off (set_logit_processors)")
+        return self._proc
+
+    def set_slot_processors(self, slot: int, prompt_tokens, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+                            frequency_penalty: float = 0.0, logit_bias: Optional[Dict] = None):
+        """sequence `slot` starts over: nothing generated yet, `prompt_tokens` marked as its prompt, and these controls from its
+        next draw on.  ValueError with the reason: repetition_penalty not finite and > 0, a penalty not finite, a bias id outside
+        the vocabulary or a bias value not finite."""
+        self._processors().set_row(slot, prompt_tokens, repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
+
+    # the processors' buffers (None while they are off): what the samplers read, the state table, the parameter and bias rows
+    adj_logits = property(lambda self: None if self._proc is None else self._proc.adj)
+    lp_state = property(lambda self: None if self._proc is None else self._proc.state)
+    lp_params = property(lambda self: None if self._proc is None else self._proc.params)
+    lp_bias = property(lambda self: None if self._proc is None else self._proc.bias)
+
     def _logprobs(self) -> LP.LogprobBuffers:
         if self._lp is None:
             raise RuntimeError("logprobs are off (set_logprobs)")
@@ -230,7 +263,8 @@ class BatchedDecodeEngine:
 
     def _loop_state(self):
         """what the captured step carries from replay to replay (the capture's warm-up step is undone on these)"""
-        return [self.tok_buf, self.pos_buf, self.rng_state, self.history] + (list(self._lp.tensors()) if self._lp is not None else [])
+        return [self.tok_buf, self.pos_buf, self.rng_state, self.history] + (list(self._lp.tensors()) if self._lp is not None else []) + \
+               (list(self._proc.loop_tensors()) if self._proc is not None else [])
 
     def _self_step(self, temperature, top_k):
         self._step()
@@ -239,7 +273,7 @@ class BatchedDecodeEngine:
     def capture(self, temperature: float = 0.8, top_k: Optional[int] = 200):
         """hipGraph of one step for all B sequences: the forward pass and B sampler launches (each sequence's token, position and
         draw counter stay on the device).  The warm-up step's state is put back."""
-        key = (float(temperature), int(top_k or 0), None if self._lp is None else self._lp.top_n)
+        key = (float(temperature), int(top_k or 0), None if self._lp is None else self._lp.top_n, self._proc is not None)
         if self._graph is not None and self._graph_key == key:
             return self._graph
         state = [t.clone() for t in self._loop_state()]
@@ -267,10 +301,16 @@ class BatchedDecodeEngine:
 
     @torch.no_grad()
     def decode_n(self, first_tokens: torch.Tensor, pos, n: int, temperature: float = 0.8, top_k: Optional[int] = 200,
-                 use_graph: bool = True) -> torch.Tensor:
+                 use_graph: bool = True, prompt_tokens=None) -> torch.Tensor:
         """n steps from first_tokens [B] at positions pos (int or [B]); returns the sampled tokens [B, n] (one read-back at the
-        end).  Sequence b draws from its own stream (seed + b)."""
+        end).  Sequence b draws from its own stream (seed + b).  prompt_tokens (B sequences of ids; with logit processors on):
+        each sequence's processor state starts over with these as its prompt — first_tokens are then counted as generated by
+        the first step, like every token a step is fed."""
         B = self.B
+        if prompt_tokens is not None and self._proc is not None:
+            assert len(prompt_tokens) == B
+            for b in range(B):
+                self._proc.reset(b, prompt_tokens[b])
         pos_t = torch.as_tensor(pos).to(torch.int32).reshape(-1).cpu()
         pos_t = pos_t.expand(B) if pos_t.numel() == 1 else pos_t
         assert int(pos_t.max()) + n <= self.max_seq and n <= self.history.shape[1]
@@ -400,8 +440,8 @@ class _Prefix:
     """one registered prefix: its K / V rows [2 L][n_kv][P][hd] (K, V of layer 0, K, V of layer 1, ...), the device table of the 2 L
     tensors' addresses and the position of a suffix's first token as a device int32"""
 
-    def __init__(self, rows: int, store: torch.Tensor):
-        self.rows, self.store = rows, store
+    def __init__(self, rows: int, store: torch.Tensor, tokens=()):
+        self.rows, self.store, self.tokens = rows, store, [int(t) for t in tokens]  # (tokens: a request's prompt bits cover them)
         self.table = torch.tensor([store[t].data_ptr() for t in range(store.shape[0])], dtype=torch.int64).to(store.device)
         self.pos = torch.tensor([rows], dtype=torch.int32).to(store.device)
 
@@ -472,9 +512,12 @@ class SlotDecodeEngine(BatchedDecodeEngine):
             _lib.check(rc, "teal_batched_retire")
 
     def _sample(self, temperature: float, top_k: Optional[int]):
-        st = runtime.stream_ptr()
+        st, src = runtime.stream_ptr(), self.logits
+        if self._proc is not None:  # tok_buf still holds the tokens this step was fed; an inactive slot counts nothing
+            self._proc.launch(self.logits, self.cfg.vocab_size, self.B, self.tok_buf, True, active=self._active, st=st)
+            src = self._proc.adj
         for b in range(self.B):
-            self._sample_slot(b, self.logits[b], temperature, top_k, st)
+            self._sample_slot(b, src[b], temperature, top_k, st)
         if self._lp is not None:  # predicated on the active word the samplers saw (retire clears bits behind it)
             V = self.cfg.vocab_size
             self._lp.launch(self.logits, V, V, self.code, self.B, self.tok_buf, self.rng_state, active=self._active, st=st)
@@ -549,7 +592,7 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         finally:
             self.admit_paths = counted
         store = torch.empty(2 * len(self.model.layers), self.cfg.n_local_heads, P, self.hd, device=self.logits.device, dtype=self.dtype)
-        pf = _Prefix(P, store)
+        pf = _Prefix(P, store, toks.tolist())
         self._copy_rows(self._slot_tables[0], pf.table, P, self.max_seq, P)
         self._prefixes[name] = pf
         return P
@@ -591,12 +634,16 @@ class SlotDecodeEngine(BatchedDecodeEngine):
 
     @torch.no_grad()
     def admit(self, slot: int, tokens, budget: int, eos_id: Optional[int], seed: int, temperature: float = 0.8,
-              top_k: Optional[int] = 200, prefix: Optional[str] = None):
+              top_k: Optional[int] = 200, prefix: Optional[str] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+              frequency_penalty: float = 0.0, logit_bias: Optional[Dict] = None):
         """Request -> slot `slot` (free): the dense prompt pass into that slot's caches, the first token drawn from the last row's
         logits (draw 0 of the stream `seed`), the slot's token, position, history, rng state, budget and EOS set on the device and
         its bit set.  A request whose first token ends it (budget 1, EOS) is switched off again by the same retire rule.
         `prefix`: a registered prefix of P rows — `tokens` are the request's own suffix; the store's rows 0 .. P-1 are copied into
-        the slot and only the suffix is run, at positions P .. P+T-1: the request is served as prompt = prefix + suffix."""
+        the slot and only the suffix is run, at positions P .. P+T-1: the request is served as prompt = prefix + suffix.
+        repetition_penalty / presence_penalty / frequency_penalty / logit_bias: the request's logit processors (they need
+        set_logit_processors(True); its prompt tokens — prefix + suffix — are marked, and every token it draws, the first
+        included, passes through them)."""
         s, B = int(slot), self.B
         prompt = torch.as_tensor(tokens, dtype=torch.int32).view(-1).to(self.logits.device)
         T = int(prompt.numel())
@@ -611,6 +658,11 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         if T < 1 or P + T >= self.max_seq or int(budget) < 1:
             raise ValueError(f"request of {T} prompt tokens" + (f" on a prefix of {P}" if pf is not None else "") +
                              f" and budget {budget} does not fit a cache of {self.max_seq} rows")
+        controls = PR.check_controls(self.cfg.vocab_size, repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
+        if self._proc is None and not PR.is_identity(controls):
+            raise RuntimeError("logit processors are off (set_logit_processors)")
+        if self._proc is not None:  # (every admission: the slot's last request left its counts and its parameters)
+            self._proc.set_row(s, (pf.tokens if pf is not None else []) + prompt.tolist(), **controls)
         logits = self._prompt_pass(s, prompt) if pf is None else self._suffix_pass(s, pf, prompt)
         self.admit_logits = logits  # (the last admission's, for tests and reports: valid until the next one)
         self.rng_state[s].copy_(torch.tensor([int(seed), 0], dtype=torch.int64), non_blocking=False)
@@ -619,8 +671,11 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         for j, off in enumerate((SLOT_BUDGET, SLOT_PRODUCED, SLOT_EOS, SLOT_FINISH)):
             self.slot_state[off + s:off + s + 1].copy_(upd[j:j + 1])
         self.slot_state[SLOT_ACTIVE:SLOT_ACTIVE + 1].bitwise_or_(1 << s)
-        st = runtime.stream_ptr()
-        self._sample_slot(s, logits, temperature, top_k, st)
+        st, src = runtime.stream_ptr(), logits
+        if self._proc is not None:  # the first draw: nothing generated yet, so nothing is counted
+            self._proc.launch(logits, 0, 1, self.tok_buf[s:], False, row0=s, active=self._active, st=st)
+            src = self._proc.adj[s]
+        self._sample_slot(s, src, temperature, top_k, st)
         if self._lp is not None:  # the request's first token: entry 0 of its row
             self._lp.launch(logits, 0, self.cfg.vocab_size, self.code, 1, self.tok_buf[s:], self.rng_state[s], row0=s,
                             active=self._active, st=st)

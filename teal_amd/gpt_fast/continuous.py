@@ -19,12 +19,14 @@ not depend on what happened to be cached when it was admitted.
 from __future__ import annotations
 
 import json
+import math
 import time
 from collections import deque
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
 
 from .batched import SLOT_ACTIVE, SLOT_FINISH, SLOT_PRODUCED, SLOT_STEP
+from .logit_processors import fp32
 
 REFILL = ("free", "all")
 
@@ -36,10 +38,55 @@ class Request:
     eos_id: Optional[int] = None
     seed: Optional[int] = None  # its random stream; None: the batcher's seed + its index
     prefix: Optional[str] = None  # a shared prefix's id: `tokens` are the suffix after its rows
+    # logit processors (None: the batcher's default).  In order of application: a positive logit of every prompt or generated token is
+    # divided by repetition_penalty, any other multiplied; frequency_penalty times the count of its generations and presence_penalty
+    # (once) are subtracted from a generated token's logit; logit_bias {"<id>": value} is added
+    repetition_penalty: Optional[float] = None
+    presence_penalty: Optional[float] = None
+    frequency_penalty: Optional[float] = None
+    logit_bias: Optional[Dict[str, float]] = None
+
+    def controls(self, defaults: Optional[Dict] = None) -> Dict:
+        """the controls that differ from "off" — the keyword arguments of the engine's admit; {}: the request asks for none"""
+        d = defaults or {}
+        out = {}
+        for name, off in (("repetition_penalty", 1.0), ("presence_penalty", 0.0), ("frequency_penalty", 0.0)):
+            v = getattr(self, name)
+            v = d.get(name, off) if v is None else v
+            if float(v) != off:
+                out[name] = float(v)
+        if self.logit_bias:
+            out["logit_bias"] = dict(self.logit_bias)
+        return out
 
 
 def _token_list(toks) -> bool:
     return isinstance(toks, list) and bool(toks) and all(isinstance(t, int) and not isinstance(t, bool) and t >= 0 for t in toks)
+
+
+def _number(v) -> bool:
+    """a finite number, also as the fp32 value the engine's parameter row holds"""
+    return isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) and math.isfinite(fp32(v))
+
+
+def parse_controls(d: dict, where: str) -> Dict:
+    """the logit-processor fields of one request object, validated; only those present"""
+    out = {}
+    if "repetition_penalty" in d:
+        if not _number(d["repetition_penalty"]) or fp32(d["repetition_penalty"]) <= 0:
+            raise ValueError(f"{where}: \"repetition_penalty\" must be a finite number > 0 (1: off)")
+        out["repetition_penalty"] = float(d["repetition_penalty"])
+    for name in ("presence_penalty", "frequency_penalty"):
+        if name in d:
+            if not _number(d[name]):
+                raise ValueError(f"{where}: \"{name}\" must be a finite number")
+            out[name] = float(d[name])
+    if "logit_bias" in d:
+        b = d["logit_bias"]
+        if not isinstance(b, dict) or not all(isinstance(k, str) and k.isdigit() and _number(v) for k, v in b.items()):
+            raise ValueError(f"{where}: \"logit_bias\" must be an object of token ids and finite numbers, {{\"<id>\": value}}")
+        out["logit_bias"] = {k: float(v) for k, v in b.items()}
+    return out
 
 
 def parse_prefixes(lines: Sequence[str], tokenizer=None) -> Dict[str, List[int]]:
@@ -95,7 +142,8 @@ def parse_requests(lines: Sequence[str], default_max_new_tokens: int, tokenizer=
     """JSON Lines, one request per line: {"tokens": [...]} or {"prompt": "..."} (needs a tokenizer; BOS prepended as generate.py
     does), with an optional "max_new_tokens" (default: `default_max_new_tokens`).  Blank lines are skipped.  A line may carry
     "prefix": an id of `prefixes`; its tokens / prompt are then the suffix, and a prompt is encoded WITHOUT a BOS (the prefix
-    holds it)."""
+    holds it).  A line may carry its own logit processors: "repetition_penalty" (> 0), "presence_penalty", "frequency_penalty"
+    and "logit_bias" ({"<id>": value})."""
     out = []
     for i, line in enumerate(lines):
         if not line.strip():
@@ -122,7 +170,7 @@ def parse_requests(lines: Sequence[str], default_max_new_tokens: int, tokenizer=
         n = d.get("max_new_tokens", default_max_new_tokens)
         if not isinstance(n, int) or n < 1:
             raise ValueError(f"request line {i + 1}: \"max_new_tokens\" must be a positive integer")
-        out.append(Request([int(t) for t in toks], n, eos_id, prefix=pid))
+        out.append(Request([int(t) for t in toks], n, eos_id, prefix=pid, **parse_controls(d, f"request line {i + 1}")))
     if not out:
         raise ValueError("no requests")
     return out
@@ -158,11 +206,16 @@ class ContinuousBatcher:
     first admission, and only requests that name a prefix are admitted with `prefix=`.  `logprobs` (None: off; 0: each token's
     logprob under the model's own distribution — temperature 1, no top-k filter; 1..8: and that many most likely alternates): the
     engine also offers set_logprobs(n), called once before the first admission, and read_logprobs(slot, n) -> (lp, top_ids,
-    top_lp) lists aligned with read_history(slot, n); the result gains "logprobs" and, for n > 0, "top_logprobs"."""
+    top_lp) lists aligned with read_history(slot, n); the result gains "logprobs" and, for n > 0, "top_logprobs".
+    Logit processors: `repetition_penalty`, `presence_penalty` and `frequency_penalty` here are the defaults of requests that set
+    none of their own.  When any request (or a default) asks for a processor the engine also offers set_logit_processors(True),
+    called once before the first admission, and admit(..., repetition_penalty=, presence_penalty=, frequency_penalty=,
+    logit_bias=); only requests that ask for one are admitted with those keywords."""
 
     def __init__(self, engine, sync_every: int = 8, refill: str = "free", temperature: float = 0.8, top_k: Optional[int] = 200,
                  seed: int = 1234, use_graph: bool = True, prefixes: Optional[Dict[str, List[int]]] = None,
-                 logprobs: Optional[int] = None):
+                 logprobs: Optional[int] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+                 frequency_penalty: float = 0.0):
         if refill not in REFILL:
             raise ValueError(f"refill must be one of {REFILL}")
         if int(sync_every) < 1:
@@ -173,6 +226,9 @@ class ContinuousBatcher:
         if logprobs is not None and (isinstance(logprobs, bool) or not isinstance(logprobs, int) or not 0 <= logprobs <= 8):
             raise ValueError("logprobs must be None or an integer in 0..8")
         self.logprobs, self._logprobs_set = logprobs, False
+        self.defaults = parse_controls({"repetition_penalty": repetition_penalty, "presence_penalty": presence_penalty,
+                                        "frequency_penalty": frequency_penalty}, "ContinuousBatcher")
+        self._processors_set = False
 
     def _clock(self):
         try:
@@ -204,6 +260,10 @@ class ContinuousBatcher:
         if self.logprobs is not None and not self._logprobs_set:  # once: it drops the engine's captured step
             eng.set_logprobs(self.logprobs)
             self._logprobs_set = True
+        controls = [r.controls(self.defaults) if hasattr(r, "controls") else {} for r in requests]
+        if any(controls) and not self._processors_set:  # once: it drops the engine's captured step
+            eng.set_logit_processors(True)
+            self._processors_set = True
         pending = deque(range(len(requests)))
         lps: List[Optional[List[float]]] = [None] * len(requests)
         tops: List[Optional[List]] = [None] * len(requests)
@@ -226,6 +286,7 @@ class ContinuousBatcher:
                     r = pending.popleft()
                     q = requests[r]
                     kw = {"prefix": q.prefix} if plen[r] else {}
+                    kw.update(controls[r])
                     eng.admit(s, q.tokens, q.max_new_tokens, q.eos_id, self.seed + r if q.seed is None else q.seed, self.temperature,
                               self.top_k, **kw)
                     prefix_admissions += 1 if plen[r] else 0

@@ -27,6 +27,7 @@ from typing import Dict, List, Optional
 import torch
 
 from .. import _lib, runtime
+from . import logit_processors as PR
 from . import logprobs as LP
 from ..monkeypatch import UP_SHIFT_BYTES, to_column_major
 from .model import Transformer
@@ -281,6 +282,7 @@ class DecodeEngine:
         self.history = torch.zeros(max(8, model.max_seq_length), dtype=torch.int32, device=dev)
         self._graph, self._graph_key, self._graphs = None, None, {}
         self._lp: Optional[LP.LogprobBuffers] = None  # set_logprobs
+        self._proc: Optional[PR.LogitProcessors] = None  # set_logit_processors
         self._score_targets = self._score_lp = None   # score
         self._build(thresholds)
 
@@ -748,9 +750,42 @@ class DecodeEngine:
     # ---- device-resident decode loop: one hipGraph replay == one token, no host-side glue ---------
     def _self_step(self, temperature, top_k):
         logits = self(self.tok_buf, self.pos_buf)
-        self.sample_fused(logits, temperature, top_k, feed=True)
+        self.sample_fused(self._adjusted(logits, True), temperature, top_k, feed=True)
         if self._lp is not None:
             self._record_logprobs(logits, self.tok_buf)
+
+    # ---- per-request logit processors (logit_processors.py): one more launch in front of the sampler, only when switched on --
+    def set_logit_processors(self, on: bool):
+        """off (the default): the step's launches are exactly those without this feature.  on: the fused sampler draws from the
+        step's logits adjusted by the sequence's repetition / presence / frequency penalty and logit bias (set_slot_processors;
+        identity until set), kept in a buffer of their own; logprobs and `logits` stay the model's.  Drops the captured graphs."""
+        if on and self.reduce is not None:
+            raise NotImplementedError("logit processors are not available under tensor parallelism: this rank's lm_head holds a "
+                                      "slice of the vocabulary, and the processor launch reads whole rows")
+        self._proc = PR.LogitProcessors(1, self.cfg.vocab_size, self.dtype, self.history.device) if on else None
+        self._graph = None
+
+    def set_slot_processors(self, slot: int, prompt_tokens, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+                            frequency_penalty: float = 0.0, logit_bias: Optional[Dict] = None):
+        """the sequence (slot 0) starts over: nothing generated yet, `prompt_tokens` marked as its prompt, and these controls from
+        its next draw on.  ValueError with the reason for a control out of range."""
+        if self._proc is None:
+            raise RuntimeError("logit processors are off (set_logit_processors)")
+        self._proc.set_row(slot, prompt_tokens, repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
+
+    # the processors' buffers (None while they are off): what the samplers read, the state table, the parameter and bias rows
+    adj_logits = property(lambda self: None if self._proc is None else self._proc.adj)
+    lp_state = property(lambda self: None if self._proc is None else self._proc.state)
+    lp_params = property(lambda self: None if self._proc is None else self._proc.params)
+    lp_bias = property(lambda self: None if self._proc is None else self._proc.bias)
+
+    def _adjusted(self, logits: torch.Tensor, count_token: bool) -> torch.Tensor:
+        """the row the sampler reads: `logits` itself, or (processors on) their adjusted copy; count_token: the token in tok_buf —
+        the one this step was fed, the sequence's latest — is counted as generated first"""
+        if self._proc is None:
+            return logits
+        self._proc.launch(logits, 0, 1, self.tok_buf, count_token)
+        return self._proc.adj[0]
 
     # ---- token log-probabilities (logprobs.py): one more launch behind the sampler, only when switched on -------------------
     def set_logprobs(self, n: Optional[int]):
@@ -776,6 +811,7 @@ class DecodeEngine:
     def _loop_state(self):
         """what a captured step carries from replay to replay (a capture's warm-up step is undone on these)"""
         return [self.tok_buf, self.pos_buf, self.rng_state] + (list(self._lp.tensors()) if self._lp is not None else []) + \
+               (list(self._proc.loop_tensors()) if self._proc is not None else []) + \
                ([self._score_lp] if self._score_lp is not None else [])
 
     def _capture(self, key, step):
@@ -820,7 +856,8 @@ class DecodeEngine:
             for _ in range(int(tokens)):
                 self._self_step(temperature, top_k)
 
-        return self._capture((float(temperature), int(top_k or 0), int(tokens), None if self._lp is None else self._lp.top_n), steps)
+        return self._capture((float(temperature), int(top_k or 0), int(tokens), None if self._lp is None else self._lp.top_n,
+                              self._proc is not None), steps)
 
     @torch.no_grad()
     def begin_sequence(self):
@@ -833,16 +870,21 @@ class DecodeEngine:
         the torch sampler of generate.sample takes ~10): opens the sample's random stream; follow with decode_n(..., drawn=1)"""
         assert logits_row.is_contiguous() and logits_row.numel() == self.cfg.vocab_size and logits_row.dtype == self.dtype
         self.begin_sequence()
-        tok = self.sample_fused(logits_row, temperature, top_k, feed=False)
+        tok = self.sample_fused(self._adjusted(logits_row, False), temperature, top_k, feed=False)
         if self._lp is not None:
             self._record_logprobs(logits_row, tok)
         return tok
 
     def decode_n(self, first_token: torch.Tensor, pos: int, n: int, temperature: float = 0.8,
-                 top_k: Optional[int] = 200, use_graph: bool = True, drawn: int = 0) -> torch.Tensor:
+                 top_k: Optional[int] = 200, use_graph: bool = True, drawn: int = 0, prompt_tokens=None) -> torch.Tensor:
         """n decode steps starting from `first_token` at position `pos`; returns the n sampled tokens.  drawn: tokens already
-        drawn from this sample's random stream (sample_first: 1) — the loop continues it instead of opening a new one."""
+        drawn from this sample's random stream (sample_first: 1) — the loop continues it instead of opening a new one.
+        prompt_tokens (with logit processors on): the processor state starts over with these as the prompt — first_token is then
+        counted as generated by the first step, like every token a step is fed; None leaves the state as it stands (after
+        set_slot_processors and sample_first)."""
         assert n + drawn <= self.history.numel() and pos + n <= self.max_seq
+        if prompt_tokens is not None and self._proc is not None:
+            self._proc.reset(0, prompt_tokens)
         self.tok_buf.copy_(first_token.view(1, 1))
         self.pos_buf.fill_(pos)
         if not drawn:

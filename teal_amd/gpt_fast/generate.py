@@ -434,8 +434,10 @@ def relayout_for_engine(model: Transformer) -> None:
 
 @torch.no_grad()
 def generate(model: Transformer, prompt: torch.Tensor, max_new_tokens: int, decoder: GraphedDecoder,
-             temperature: float = 0.8, top_k: Optional[int] = 200, prefill: Optional[GraphedPrefill] = None) -> torch.Tensor:
-    """prefill (seq > 1: ops fall back to dense matmul) then max_new_tokens-1 decode steps."""
+             temperature: float = 0.8, top_k: Optional[int] = 200, prefill: Optional[GraphedPrefill] = None,
+             processors: Optional[Dict] = None) -> torch.Tensor:
+    """prefill (seq > 1: ops fall back to dense matmul) then max_new_tokens-1 decode steps.  processors (the fused engine only):
+    repetition_penalty / presence_penalty / frequency_penalty / logit_bias of this sample, applied to every draw."""
     T = prompt.size(0)
     T_new = T + max_new_tokens
     dev = prompt.device
@@ -444,6 +446,12 @@ def generate(model: Transformer, prompt: torch.Tensor, max_new_tokens: int, deco
     seq[:T] = prompt
     logits = prefill(prompt) if prefill is not None else model(prompt.view(1, -1), torch.arange(0, T, device=dev))
     eng = decoder.model if hasattr(decoder.model, "decode_n") else None
+    if processors:
+        if eng is None or logits.dtype != eng.dtype or logits.shape[-1] != eng.cfg.vocab_size:
+            raise ValueError("logit processors need the fused engine's sampler for every draw")
+        if eng.adj_logits is None:
+            eng.set_logit_processors(True)
+        eng.set_slot_processors(0, prompt.tolist(), **processors)
     if eng is not None and logits.dtype == eng.dtype and logits.shape[-1] == eng.cfg.vocab_size:
         # HIP engine: the token after the prompt comes from the same fused sampler as every later one (gpt-fast/generate.py:
         # 49-66 is ONE function for both), and the whole loop stays on the device
@@ -666,6 +674,33 @@ def check_logprobs_args(args) -> Optional[int]:
     return int(n)
 
 
+def check_processor_args(args) -> Dict:
+    """--repetition_penalty / --presence_penalty / --frequency_penalty: the controls that are switched on ({}: none); every
+    refusal is raised here, before anything is loaded.  The processors are a launch in front of the fused engines' samplers, so
+    the flags need an engine path: --compile / --engine (one sequence or --batch_size) or --requests, where they are the
+    defaults of requests that carry none of their own."""
+    from teal_amd.gpt_fast.continuous import parse_controls
+    given = {k: getattr(args, k, None) for k in ("repetition_penalty", "presence_penalty", "frequency_penalty")}
+    try:
+        c = parse_controls({k: v for k, v in given.items() if v is not None}, "generate")
+    except ValueError as e:
+        raise SystemExit(str(e).replace('generate: "', "--").replace('" must', " must"))
+    c = {k: v for k, v in c.items() if v != (1.0 if k == "repetition_penalty" else 0.0)}
+    if not c:
+        return {}
+    flags = "--repetition_penalty / --presence_penalty / --frequency_penalty"
+    if getattr(args, "draft_checkpoint_path", None) is not None or getattr(args, "self_speculate", False):
+        raise SystemExit(f"{flags} do not combine with speculative decoding (the accept rule compares the models' own distributions)")
+    if int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1"))) > 1:
+        raise SystemExit(f"{flags} do not run under tensor parallelism (a rank's lm_head holds a slice of the vocabulary)")
+    if getattr(args, "dense", False) or (not args.synthetic and args.hist_path is None):
+        raise SystemExit(f"{flags} need TEAL thresholds (--hist_path, or --synthetic): the fused engines run patched models only")
+    if getattr(args, "requests", None) is None and (getattr(args, "no_engine", False) or not (args.compile or args.engine)):
+        raise SystemExit(f"{flags} need a fused engine (--compile or --engine, without --no_engine, or --requests): the module "
+                         "path samples from the raw logits")
+    return c
+
+
 def _mean_logprob_line(lps) -> str:
     return f"    mean logprob {sum(lps) / max(1, len(lps)):.4f} over {len(lps)} tokens (model distribution, temperature 1)"
 
@@ -693,6 +728,13 @@ def run_batched(args, model: Transformer, thresholds, prompts: torch.Tensor, tok
         if eng is None:
             raise SystemExit("--logprobs: the batched engine cannot run this model, and the module path returns token ids only")
         eng.set_logprobs(n_lp)
+    proc = check_processor_args(args)
+    if proc:  # the first token of each sequence comes from the prompt pass's torch sampler: the processors act from the second on
+        if eng is None:
+            raise SystemExit("logit processors: the batched engine cannot run this model, and the module path samples from the raw logits")
+        eng.set_logit_processors(True)
+        for b in range(B):
+            eng.set_slot_processors(b, prompts[b].tolist(), **proc)
     tps, seqs, lps, tops = [], [], [], []
     for i in range(-1 if args.compile else 0, args.num_samples):
         torch.cuda.synchronize()
@@ -705,7 +747,8 @@ def run_batched(args, model: Transformer, thresholds, prompts: torch.Tensor, tok
         if n_new > 1:
             if eng is not None:
                 eng.manual_seed(1234 + max(i, 0))
-                seq[:, T + 1:] = eng.decode_n(first, T, n_new - 1, args.temperature, args.top_k, use_graph=bool(args.compile)).long()
+                seq[:, T + 1:] = eng.decode_n(first, T, n_new - 1, args.temperature, args.top_k, use_graph=bool(args.compile),
+                                              prompt_tokens=prompts.tolist() if proc else None).long()
             else:
                 cur, pos = first.view(B, 1), torch.tensor([T], device=dev)
                 for j in range(n_new - 1):
@@ -789,7 +832,8 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer) -> Dict:
         raise SystemExit(f"--requests: the batched engine cannot run this model: {why}")
     eng = SlotDecodeEngine(model, thresholds, B)
     batcher = ContinuousBatcher(eng, sync_every=args.sync_every, temperature=args.temperature, top_k=args.top_k, seed=1234,
-                                use_graph=bool(args.compile), prefixes=prefixes, logprobs=getattr(args, "logprobs", None))
+                                use_graph=bool(args.compile), prefixes=prefixes, logprobs=getattr(args, "logprobs", None),
+                                **check_processor_args(args))
     try:
         for name, toks in prefixes.items():  # once, before the warm-up run
             eng.register_prefix(name, toks)
@@ -835,6 +879,7 @@ def main(args) -> Dict:
     spec = check_speculative_args(args)  # before anything is loaded
     batch = check_batched_args(args)
     n_lp = check_logprobs_args(args)
+    proc = check_processor_args(args)
     if getattr(args, "prefixes", None) is not None and getattr(args, "requests", None) is None:
         raise SystemExit("--prefixes names shared prefixes of continuous batching: it needs --requests")
     if getattr(args, "requests", None) is not None:
@@ -919,6 +964,8 @@ def main(args) -> Dict:
         relayout_for_engine(model)
     if n_lp is not None and not use_engine:
         raise SystemExit("--logprobs: the fused engine cannot run this model, and the module path returns token ids only")
+    if proc and not use_engine:
+        raise SystemExit("logit processors: the fused engine cannot run this model, and the module path samples from the raw logits")
     # --compile captures the prompt pass as well (one hipGraph per prompt length; the reference compiles `prefill` only under
     # --compile_prefill, generate.py:423-425 — its Inductor compile takes minutes, a capture here takes milliseconds, and the
     # eager pass is ~400 launches = nine decode steps' worth for a 6-token prompt).  The prefill stays DENSE
@@ -950,7 +997,7 @@ def main(args) -> Dict:
                 if decoder.model._lp is None:
                     decoder.model.set_logprobs(n_lp)
             y = generate(model, prompt, args.max_new_tokens, decoder, temperature=args.temperature, top_k=args.top_k,
-                         prefill=prefill)
+                         prefill=prefill, processors=proc or None)
         torch.cuda.synchronize()
         t = time.perf_counter() - t0
         if i == -1:
@@ -1043,6 +1090,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--logprobs", type=int, default=None, help="return each generated token's log-probability under the model's own "
                    "distribution (temperature 1, no top-k filter) and the N most likely alternates (0..8; 0: the token's only); "
                    "engine paths only: --compile / --engine, --batch_size, --requests")
+    p.add_argument("--repetition_penalty", type=float, default=None, help="logit processor (engine paths only, like --logprobs): the "
+                   "logit of every token of the prompt or generated so far is divided by this if positive, multiplied otherwise "
+                   "(> 0; 1: off).  With --requests: the default of requests that set none")
+    p.add_argument("--presence_penalty", type=float, default=None, help="logit processor: subtracted once from the logit of every "
+                   "token generated so far (0: off)")
+    p.add_argument("--frequency_penalty", type=float, default=None, help="logit processor: subtracted from a token's logit once per "
+                   "time it was generated so far (0: off)")
     p.add_argument("--sync_every", type=int, default=8, help="with --requests: steps per burst between two looks at the slot state")
     return p
 
