@@ -24,9 +24,8 @@ import torch
 
 from .. import _lib, runtime
 from ..kernels.sparse_gemv import BATCH_MAX, batched_segs
-from ..monkeypatch import UP_SHIFT_BYTES, to_column_major
 from . import logit_processors as PR
-from . import logprobs as LP
+from .engine_features import SamplerFeatures, _SlotCaches, dense_16bit_refusal, relayout
 from .model import Transformer
 from .prefill import IN_NORM, IN_SILU_MUL, IN_XT, MAX_T, PrefillEngine, PrefillIn
 from .speculative import VerifyPass
@@ -35,22 +34,19 @@ PROJ_LAUNCHES = (("qkv", ("q", "k", "v")), ("o", ("o",)), ("gateup", ("gate", "u
 NINF = float("-inf")
 
 
-class BatchedDecodeEngine:
+class BatchedDecodeEngine(SamplerFeatures):
     @staticmethod
     def supports(model: Transformer) -> Optional[str]:
         """None if the batched step can run `model` as it stands (batch = the caches' max_batch_size), else the reason."""
         cfg = model.config
         if int(getattr(model, "tp_world", 1)) > 1:
             return "tensor-parallel models are not batched (decode them one sequence at a time)"
-        lins = [lin for layer in model.layers for lin in (layer.attention.wqkv, layer.attention.wo, layer.feed_forward.w1,
-                                                         layer.feed_forward.w3, layer.feed_forward.w2)] + [model.output]
-        if any(hasattr(lin, "scales_and_zeros") or hasattr(lin, "scales") or lin.weight.dtype == torch.int8 for lin in lins):
-            return "quantised (int8 / int4) weights are not batched"
+        why = dense_16bit_refusal(
+            model, lambda lin: hasattr(lin, "scales_and_zeros") or hasattr(lin, "scales") or lin.weight.dtype == torch.int8,
+            "quantised (int8 / int4) weights are not batched")
+        if why is not None:
+            return why
         dt = model.output.weight.dtype
-        if dt not in (torch.float16, torch.bfloat16) or any(lin.weight.dtype != dt for lin in lins):
-            return f"weights are not uniformly fp16 / bf16: {dt}"
-        if not model.output.weight.is_cuda:
-            return "model is not on a HIP device"
         inter = model.layers[0].feed_forward.w1.out_features
         qd, kv = cfg.n_head * cfg.head_dim, cfg.n_local_heads * cfg.head_dim
         if (cfg.head_dim not in (64, 128) or cfg.dim != qd or cfg.dim % 256 or cfg.dim > 16384 or inter % 256 or inter > 65536
@@ -84,13 +80,11 @@ class BatchedDecodeEngine:
         self.L = _lib.load()
         runtime.init()
         self.model, self.cfg, self.B = model, model.config, B
+        self._feature_rows = B
         cfg = self.cfg
         dev, dt = model.output.weight.device, model.output.weight.dtype
         self.dtype, self.code = dt, runtime.dtype_code(dt)
-        for layer in model.layers:  # the decode step's layout (idempotent)
-            for lin in (layer.attention.wqkv, layer.attention.wo, layer.feed_forward.w1, layer.feed_forward.w3, layer.feed_forward.w2):
-                to_column_major(lin, shift_bytes=UP_SHIFT_BYTES if lin is layer.feed_forward.w3 else 0)
-        to_column_major(model.output)
+        relayout(model)
         self.ths = [dict(t) for t in thresholds]
         self.dim, self.hd = cfg.dim, cfg.head_dim
         self.kv = cfg.n_local_heads * cfg.head_dim
@@ -124,8 +118,6 @@ class BatchedDecodeEngine:
         self._seed = 1234
         self._graph = None
         self._graph_key = None
-        self._lp: Optional[LP.LogprobBuffers] = None  # set_logprobs
-        self._proc: Optional[PR.LogitProcessors] = None  # set_logit_processors
         kvw = self.kv
         self._segs = [{
             "qkv": batched_segs([self.dim, self.dim + kvw, self.nqkv], [t["q"], t["k"], t["v"]]),
@@ -216,55 +208,13 @@ class BatchedDecodeEngine:
         if self._lp is not None:
             self._lp.launch(self.logits, V, V, self.code, self.B, self.tok_buf, self.rng_state, st=st)
 
-    # ---- token log-probabilities (logprobs.py): one launch behind the B samplers, only when switched on ----------------------
-    def set_logprobs(self, n: Optional[int]):
-        """None: off (the default; the step's launches are exactly those without this feature).  0: every token a step draws gets
-        its logprob under the model's own distribution (temperature 1, no top-k filter); 1..8: and the ids and logprobs of that
-        many most likely tokens.  Entry i of sequence b belongs to history[b, i].  Drops the captured graph."""
-        n = LP.check_setting(n)
-        self._lp = None if n is None else LP.LogprobBuffers(self.B, self.history.shape[1], n, self.history.device)
-        self._graph = None
-
-    # ---- per-request logit processors (logit_processors.py): one launch in front of the B samplers, only when switched on ----
-    def set_logit_processors(self, on: bool):
-        """off (the default): the step's launches are exactly those without this feature.  on: every step adjusts its logits by
-        each sequence's repetition / presence / frequency penalty and logit bias (set_slot_processors; identity until set) into a
-        buffer of their own, which the samplers read; logprobs and `logits` stay the model's.  Drops the captured graph."""
-        V = self.cfg.vocab_size
-        self._proc = PR.LogitProcessors(self.B, V, self.dtype, self.logits.device) if on else None
-        self._graph = None
-
-    def _processors(self) -> PR.LogitProcessors:
-        if self._proc is None:
-            raise RuntimeError("logit processors are off (set_logit_processors)")
-        return self._proc
-
-    def set_slot_processors(self, slot: int, prompt_tokens, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-                            frequency_penalty: float = 0.0, logit_bias: Optional[Dict] = None):
-        """sequence `slot` starts over: nothing generated yet, `prompt_tokens` marked as its prompt, and these controls from its
-        next draw on.  ValueError with the reason: repetition_penalty not finite and > 0, a penalty not finite, a bias id outside
-        the vocabulary or a bias value not finite."""
-        self._processors().set_row(slot, prompt_tokens, repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
-
-    # the processors' buffers (None while they are off): what the samplers read, the state table, the parameter and bias rows
-    adj_logits = property(lambda self: None if self._proc is None else self._proc.adj)
-    lp_state = property(lambda self: None if self._proc is None else self._proc.state)
-    lp_params = property(lambda self: None if self._proc is None else self._proc.params)
-    lp_bias = property(lambda self: None if self._proc is None else self._proc.bias)
-
-    def _logprobs(self) -> LP.LogprobBuffers:
-        if self._lp is None:
-            raise RuntimeError("logprobs are off (set_logprobs)")
-        return self._lp
-
     def read_logprobs(self, n: int):
         """(lp [B, n], top_ids [B, n, top_n], top_lp [B, n, top_n]) of the tokens history[:, :n] — decode_n's"""
         return self._logprobs().read(slice(None), 0, n)
 
     def _loop_state(self):
         """what the captured step carries from replay to replay (the capture's warm-up step is undone on these)"""
-        return [self.tok_buf, self.pos_buf, self.rng_state, self.history] + (list(self._lp.tensors()) if self._lp is not None else []) + \
-               (list(self._proc.loop_tensors()) if self._proc is not None else [])
+        return [self.tok_buf, self.pos_buf, self.rng_state, self.history] + self._feature_loop_state()
 
     def _self_step(self, temperature, top_k):
         self._step()
@@ -273,28 +223,12 @@ class BatchedDecodeEngine:
     def capture(self, temperature: float = 0.8, top_k: Optional[int] = 200):
         """hipGraph of one step for all B sequences: the forward pass and B sampler launches (each sequence's token, position and
         draw counter stay on the device).  The warm-up step's state is put back."""
-        key = (float(temperature), int(top_k or 0), None if self._lp is None else self._lp.top_n, self._proc is not None)
+        key = (float(temperature), int(top_k or 0)) + self._feature_key()
         if self._graph is not None and self._graph_key == key:
             return self._graph
-        state = [t.clone() for t in self._loop_state()]
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self._self_step(temperature, top_k)
-        torch.cuda.current_stream().wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        try:
-            self._restore(state)
-            with runtime.graph_capture(g):
-                self._self_step(temperature, top_k)
-        finally:
-            self._restore(state)
+        g, _ = runtime.capture_graph(lambda: self._self_step(temperature, top_k), self._loop_state())
         self._graph, self._graph_key = g, key
         return g
-
-    def _restore(self, state):
-        for dst, src in zip(self._loop_state(), state):
-            dst.copy_(src)
 
     def manual_seed(self, seed: int):
         self._seed = int(seed)
@@ -384,7 +318,7 @@ class _SlotCacheView(torch.nn.Module):
         return self.k_cache, self.v_cache
 
 
-class SlotPrefillEngine(PrefillEngine):
+class SlotPrefillEngine(_SlotCaches, PrefillEngine):
     """The HIP prompt pass (2..16 tokens) of one request into slot `slot` of batch-B caches: slot s of a contiguous
     [B, n_kv, max_seq, hd] cache is itself a contiguous [1, n_kv, max_seq, hd] cache, so the pass gets its base pointers."""
 
@@ -392,15 +326,8 @@ class SlotPrefillEngine(PrefillEngine):
     def supports(model: Transformer) -> Optional[str]:
         return PrefillEngine._supports(model, any_batch=True)
 
-    slot = 0
 
-    def _caches(self, at):
-        kc, vc = at.kv_cache.k_cache, at.kv_cache.v_cache
-        off = self.slot * kc[0].numel() * kc.element_size()
-        return kc.data_ptr() + off, vc.data_ptr() + off
-
-
-class SlotVerifyPass(VerifyPass):
+class SlotVerifyPass(_SlotCaches, VerifyPass):
     """The dense pass over T <= 16 tokens at positions p .. p+T-1 (VerifyPass: p on the device, attention against the rows already
     in the cache) into slot `slot` of batch-B caches — the suffix pass of a request admitted on a shared prefix."""
 
@@ -411,16 +338,9 @@ class SlotVerifyPass(VerifyPass):
             why = f"vocab_size {model.config.vocab_size} is not a multiple of 256 (the all-row lm_head GEMM's column contract)"
         return why
 
-    slot = 0
-
     def __init__(self, model: Transformer):
         super().__init__(model)
         self.rows = torch.zeros(8, 2 * model.config.vocab_size, device=self.lm_slabs.device, dtype=model.output.weight.dtype)
-
-    def _caches(self, at):
-        kc, vc = at.kv_cache.k_cache, at.kv_cache.v_cache
-        off = self.slot * kc[0].numel() * kc.element_size()
-        return kc.data_ptr() + off, vc.data_ptr() + off
 
     def last_logits(self, ns: int, T: int) -> torch.Tensor:
         """logits [vocab] of row T - 1 from the `ns` lm_head slabs run() left: summed in slice order, rounded once"""
@@ -523,12 +443,8 @@ class SlotDecodeEngine(BatchedDecodeEngine):
             self._lp.launch(self.logits, V, V, self.code, self.B, self.tok_buf, self.rng_state, active=self._active, st=st)
         self._retire((1 << self.B) - 1, True, st)
 
-    def capture(self, temperature: float = 0.8, top_k: Optional[int] = 200):
-        state = self.slot_state.clone()  # the warm-up step retires too
-        try:
-            return super().capture(temperature, top_k)
-        finally:
-            self.slot_state.copy_(state)
+    def _loop_state(self):
+        return super()._loop_state() + [self.slot_state]  # the warm-up step retires too
 
     # ---- admission ---------------------------------------------------------------------------------------------------------
     @torch.no_grad()

@@ -27,9 +27,7 @@ from typing import Dict, List, Optional
 import torch
 
 from .. import _lib, runtime
-from . import logit_processors as PR
-from . import logprobs as LP
-from ..monkeypatch import UP_SHIFT_BYTES, to_column_major
+from .engine_features import SamplerFeatures, model_linears, relayout
 from .model import Transformer
 
 TEAL_IN_PLAIN, TEAL_IN_RESID_NORM, TEAL_IN_SILU_MUL, TEAL_IN_MASKED, TEAL_IN_ATTN_MERGE = 0, 1, 2, 3, 4
@@ -80,7 +78,7 @@ def _out(segs, mode, slabs: Optional[torch.Tensor] = None) -> GemvOut:
     return o
 
 
-class DecodeEngine:
+class DecodeEngine(SamplerFeatures):
     """One-token decode of `model` at batch 1 through the fused HIP kernels.
 
     `thresholds[i]` = {"q","k","v","o","gate","up","down": tau} for layer i (what monkeypatch_layer
@@ -95,8 +93,7 @@ class DecodeEngine:
         teal_decode_attention* (head_dim 64 / 128, [1][n_kv][max_seq][hd] caches), the register-resident RMSNorm
         producer (dim <= 16384), 16-byte rows (multiples of 8 columns), Z <= 65536, one weight format for all linears."""
         cfg = model.config
-        lins = [lin for layer in model.layers for lin in (layer.attention.wqkv, layer.attention.wo, layer.feed_forward.w1,
-                                                         layer.feed_forward.w3, layer.feed_forward.w2)] + [model.output]
+        lins = model_linears(model)
         i4 = [hasattr(lin, "scales_and_zeros") for lin in lins]
         if any(i4):
             # int4 group-quantised projections (teal_amd/quantize.py) with a 16-bit lm_head, as quantize_model_int4 leaves them
@@ -190,8 +187,7 @@ class DecodeEngine:
         self.cfg, self.model = cfg, model
         dev = model.output.weight.device
         dt = model.output.scales.dtype if hasattr(model.output, "scales") else model.output.weight.dtype
-        lins = [lin for layer in model.layers for lin in (layer.attention.wqkv, layer.attention.wo, layer.feed_forward.w1,
-                                                         layer.feed_forward.w3, layer.feed_forward.w2)] + [model.output]
+        lins = model_linears(model)
         self.int4 = hasattr(lins[0], "scales_and_zeros")  # int4 group-quantised projections, 16-bit lm_head
         self.int8 = lins[0].weight.dtype == torch.int8    # int8 weight-only linears (teal_amd/quantize.py)
         self.dtype, self.code = dt, runtime.dtype_code(dt)
@@ -222,12 +218,7 @@ class DecodeEngine:
         if reduce_presummed is None:
             reduce_presummed = os.environ.get("TEAL_TP_PRESUM", "0") == "1"
         self.presum = bool(reduce_presummed)
-        for layer in model.layers:
-            for lin in (layer.attention.wqkv, layer.attention.wo, layer.feed_forward.w1, layer.feed_forward.w3,
-                        layer.feed_forward.w2):
-                if not self.int4:  # (an int4 linear holds the packed image of W^T already)
-                    to_column_major(lin, shift_bytes=UP_SHIFT_BYTES if lin is layer.feed_forward.w3 else 0)
-        to_column_major(model.output)
+        relayout(model)
         e = lambda *shape, dtype=dt: torch.zeros(*shape, device=dev, dtype=dtype)  # noqa: E731
         self.resid = [e(dim), e(dim)]
         self.qkv, self.y_attn, self.gu = e(self.nqkv), e(qdim), e(2 * inter)
@@ -281,8 +272,7 @@ class DecodeEngine:
         self.pos_buf = torch.zeros(1, dtype=torch.int32, device=dev)      # loop-carried position
         self.history = torch.zeros(max(8, model.max_seq_length), dtype=torch.int32, device=dev)
         self._graph, self._graph_key, self._graphs = None, None, {}
-        self._lp: Optional[LP.LogprobBuffers] = None  # set_logprobs
-        self._proc: Optional[PR.LogitProcessors] = None  # set_logit_processors
+        self._feature_rows = 1
         self._score_targets = self._score_lp = None   # score
         self._build(thresholds)
 
@@ -531,17 +521,10 @@ class DecodeEngine:
                 for i in range(len(self.stages)):
                     self._layer(i, tok_ptr, pos_ptr, only=only)
 
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                run()
-            torch.cuda.current_stream().wait_stream(s)
+            g, _ = runtime.capture_graph(run)
             torch.cuda.synchronize()
             if key != "layer":
                 out["bytes"][key] = stage_bytes(key)
-            g = torch.cuda.CUDAGraph()
-            with runtime.graph_capture(g):
-                run()
             for _ in range(3):
                 g.replay()
             torch.cuda.synchronize()
@@ -754,30 +737,12 @@ class DecodeEngine:
         if self._lp is not None:
             self._record_logprobs(logits, self.tok_buf)
 
-    # ---- per-request logit processors (logit_processors.py): one more launch in front of the sampler, only when switched on --
-    def set_logit_processors(self, on: bool):
-        """off (the default): the step's launches are exactly those without this feature.  on: the fused sampler draws from the
-        step's logits adjusted by the sequence's repetition / presence / frequency penalty and logit bias (set_slot_processors;
-        identity until set), kept in a buffer of their own; logprobs and `logits` stay the model's.  Drops the captured graphs."""
-        if on and self.reduce is not None:
-            raise NotImplementedError("logit processors are not available under tensor parallelism: this rank's lm_head holds a "
-                                      "slice of the vocabulary, and the processor launch reads whole rows")
-        self._proc = PR.LogitProcessors(1, self.cfg.vocab_size, self.dtype, self.history.device) if on else None
-        self._graph = None
-
-    def set_slot_processors(self, slot: int, prompt_tokens, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-                            frequency_penalty: float = 0.0, logit_bias: Optional[Dict] = None):
-        """the sequence (slot 0) starts over: nothing generated yet, `prompt_tokens` marked as its prompt, and these controls from
-        its next draw on.  ValueError with the reason for a control out of range."""
-        if self._proc is None:
-            raise RuntimeError("logit processors are off (set_logit_processors)")
-        self._proc.set_row(slot, prompt_tokens, repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
-
-    # the processors' buffers (None while they are off): what the samplers read, the state table, the parameter and bias rows
-    adj_logits = property(lambda self: None if self._proc is None else self._proc.adj)
-    lp_state = property(lambda self: None if self._proc is None else self._proc.state)
-    lp_params = property(lambda self: None if self._proc is None else self._proc.params)
-    lp_bias = property(lambda self: None if self._proc is None else self._proc.bias)
+    # ---- logit processors and token logprobs (SamplerFeatures): one more launch in front of / behind the sampler, when on -----
+    def _feature_refusal(self, what: str):
+        if self.reduce is not None:
+            launch = {"logprobs": "logprob", "logit processors": "processor"}[what]
+            raise NotImplementedError(f"{what} are not available under tensor parallelism: this rank's lm_head holds a slice of "
+                                      f"the vocabulary, and the {launch} launch reads whole rows")
 
     def _adjusted(self, logits: torch.Tensor, count_token: bool) -> torch.Tensor:
         """the row the sampler reads: `logits` itself, or (processors on) their adjusted copy; count_token: the token in tok_buf —
@@ -787,31 +752,16 @@ class DecodeEngine:
         self._proc.launch(logits, 0, 1, self.tok_buf, count_token)
         return self._proc.adj[0]
 
-    # ---- token log-probabilities (logprobs.py): one more launch behind the sampler, only when switched on -------------------
-    def set_logprobs(self, n: Optional[int]):
-        """None: off (the default; the step's launches are exactly those without this feature).  0: every token the fused sampler
-        draws gets its logprob under the model's own distribution (temperature 1, no top-k filter); 1..8: and the ids and logprobs
-        of that many most likely tokens.  Entry i belongs to history[i] (read_logprobs).  Drops the captured graphs."""
-        n = LP.check_setting(n)
-        if n is not None and self.reduce is not None:
-            raise NotImplementedError("logprobs are not available under tensor parallelism: this rank's lm_head holds a slice of "
-                                      "the vocabulary, and the logprob launch reads whole rows")
-        self._lp = None if n is None else LP.LogprobBuffers(1, self.history.numel(), n, self.history.device)
-        self._graph = None
-
     def _record_logprobs(self, logits: torch.Tensor, token: torch.Tensor):
         self._lp.launch(logits, 0, self.cfg.vocab_size, self.code, 1, token, self.rng_state)
 
     def read_logprobs(self, drawn: int, n: int):
         """(lp [n], top_ids [n, top_n], top_lp [n, top_n]) of the tokens history[drawn : drawn + n] — decode_n(..., drawn=drawn)'s"""
-        if self._lp is None:
-            raise RuntimeError("logprobs are off (set_logprobs)")
-        return self._lp.read(0, drawn, n)
+        return self._logprobs().read(0, drawn, n)
 
     def _loop_state(self):
         """what a captured step carries from replay to replay (a capture's warm-up step is undone on these)"""
-        return [self.tok_buf, self.pos_buf, self.rng_state] + (list(self._lp.tensors()) if self._lp is not None else []) + \
-               (list(self._proc.loop_tensors()) if self._proc is not None else []) + \
+        return [self.tok_buf, self.pos_buf, self.rng_state] + self._feature_loop_state() + \
                ([self._score_lp] if self._score_lp is not None else [])
 
     def _capture(self, key, step):
@@ -826,25 +776,8 @@ class DecodeEngine:
         if key in self._graphs:
             self._graph, self._graph_key = self._graphs[key], key
             return self._graph
-        bufs = self._loop_state()
-        state = [b.clone() for b in bufs]
-
-        def restore():
-            for b, v in zip(bufs, state):
-                b.copy_(v)
-
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):  # warm-up outside capture (KV rows it writes are rewritten by the real run)
-            step()
-        torch.cuda.current_stream().wait_stream(s)
-        restore()
-        g = torch.cuda.CUDAGraph()
-        try:
-            with runtime.graph_capture(g):
-                step()
-        finally:  # (also when the capture fails — decode_n then decodes a sharded model eagerly from the same state)
-            restore()
+        # (the state is put back also when the capture fails — decode_n then decodes a sharded model eagerly from the same state)
+        g, _ = runtime.capture_graph(step, self._loop_state())
         self._graphs[key] = g
         self._graph, self._graph_key = g, key
         return g
@@ -856,8 +789,7 @@ class DecodeEngine:
             for _ in range(int(tokens)):
                 self._self_step(temperature, top_k)
 
-        return self._capture((float(temperature), int(top_k or 0), int(tokens), None if self._lp is None else self._lp.top_n,
-                              self._proc is not None), steps)
+        return self._capture((float(temperature), int(top_k or 0), int(tokens)) + self._feature_key(), steps)
 
     @torch.no_grad()
     def begin_sequence(self):

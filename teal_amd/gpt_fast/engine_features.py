@@ -1,0 +1,140 @@
+"""What the fused engines share on the host side: the model's linears and the pointers a captured pass holds, the checks
+every dense-chain engine starts `supports` with, and the sampler-side features (token logprobs, logit processors) of the decode
+engines.  A new per-request feature of the sampler goes into `SamplerFeatures` once, plus each engine's `_sample`.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional
+
+import torch
+
+from ..monkeypatch import UP_SHIFT_BYTES, to_column_major
+from . import logit_processors as PR
+from . import logprobs as LP
+
+
+def block_linears(layer):
+    """the five projections of a block, in launch order"""
+    return (layer.attention.wqkv, layer.attention.wo, layer.feed_forward.w1, layer.feed_forward.w3, layer.feed_forward.w2)
+
+
+def model_linears(model):
+    """every block's projections, then the lm_head"""
+    return [lin for layer in model.layers for lin in block_linears(layer)] + [model.output]
+
+
+def relayout(model) -> None:
+    """every projection and the lm_head column-major, the decode step's layout (idempotent)"""
+    for layer in model.layers:
+        for lin in block_linears(layer):
+            if not hasattr(lin, "scales_and_zeros"):  # (an int4 image is packed column-gathered already)
+                to_column_major(lin, shift_bytes=UP_SHIFT_BYTES if lin is layer.feed_forward.w3 else 0)
+    to_column_major(model.output)
+
+
+def pointer_key(model, weights: bool = True, freqs: bool = True):
+    """everything a captured pass over `model` holds raw pointers to: a re-laid-out weight (to_column_major replaces the storage)
+    or a re-allocated KV cache changes it.  weights=False: the context length and the KV caches only."""
+    head = (model.max_seq_length,)
+    if weights:
+        head += (model.output.weight.data_ptr(), model.tok_embeddings.weight.data_ptr())
+        if freqs:
+            head += (model.freqs_cis.data_ptr(),)
+    per_layer = []
+    for layer in model.layers:
+        at, ff = layer.attention, layer.feed_forward
+        per_layer += [at.kv_cache.k_cache.data_ptr(), at.kv_cache.v_cache.data_ptr()]
+        if weights:
+            per_layer += [lin.weight.data_ptr() for lin in (at.wqkv, at.wo, ff.w1, ff.w2, ff.w3)]
+    return head + tuple(per_layer)
+
+
+def dense_16bit_refusal(model, quantised, quantised_why: str) -> Optional[str]:
+    """why a dense-chain engine (prompt pass, batched step) cannot take `model`'s weights as they stand, or None: `quantised(lin)`
+    marks a quantised linear (refused with `quantised_why`); the rest must be uniformly fp16 / bf16 and on the device"""
+    lins = model_linears(model)
+    if any(quantised(lin) for lin in lins):
+        return quantised_why
+    dt = model.output.weight.dtype
+    if dt not in (torch.float16, torch.bfloat16) or any(lin.weight.dtype != dt for lin in lins):
+        return f"weights are not uniformly fp16 / bf16: {dt}"
+    if not model.output.weight.is_cuda:
+        return "model is not on a HIP device"
+    return None
+
+
+class _SlotCaches:
+    """the K / V base pointers of slot `slot` of batch-B caches: slot s of a contiguous [B, n_kv, max_seq, hd] cache is itself a
+    contiguous [1, n_kv, max_seq, hd] cache"""
+
+    slot = 0
+
+    def _caches(self, at):
+        kc, vc = at.kv_cache.k_cache, at.kv_cache.v_cache
+        off = self.slot * kc[0].numel() * kc.element_size()
+        return kc.data_ptr() + off, vc.data_ptr() + off
+
+
+class SamplerFeatures:
+    """Token logprobs (logprobs.py: one launch behind the sampler) and per-request logit processors (logit_processors.py: one
+    launch in front of it), both off until switched on.  The host class provides `_feature_rows` (its sequences), `history`
+    (int32 [..., length]: a logprob row is as long), `cfg.vocab_size`, `dtype` and a `_graph` the setters drop."""
+
+    _lp: Optional[LP.LogprobBuffers] = None      # set_logprobs
+    _proc: Optional[PR.LogitProcessors] = None   # set_logit_processors
+
+    def _feature_refusal(self, what: str) -> None:
+        """raises if this engine cannot switch `what` ("logprobs" / "logit processors") on"""
+        return None
+
+    def set_logprobs(self, n: Optional[int]):
+        """None: off (the default; the step's launches are exactly those without this feature).  0: every token the fused sampler
+        draws gets its logprob under the model's own distribution (temperature 1, no top-k filter); 1..8: and the ids and logprobs
+        of that many most likely tokens.  Entry i of a sequence belongs to entry i of its history row (read_logprobs).  Drops the
+        captured graphs."""
+        n = LP.check_setting(n)
+        if n is not None:
+            self._feature_refusal("logprobs")
+        self._lp = None if n is None else LP.LogprobBuffers(self._feature_rows, self.history.shape[-1], n, self.history.device)
+        self._graph = None
+
+    def _logprobs(self) -> LP.LogprobBuffers:
+        if self._lp is None:
+            raise RuntimeError("logprobs are off (set_logprobs)")
+        return self._lp
+
+    def set_logit_processors(self, on: bool):
+        """off (the default): the step's launches are exactly those without this feature.  on: the fused sampler draws from the
+        step's logits adjusted by each sequence's repetition / presence / frequency penalty and logit bias (set_slot_processors;
+        identity until set), kept in a buffer of their own; logprobs and `logits` stay the model's.  Drops the captured graphs."""
+        if on:
+            self._feature_refusal("logit processors")
+        self._proc = PR.LogitProcessors(self._feature_rows, self.cfg.vocab_size, self.dtype, self.history.device) if on else None
+        self._graph = None
+
+    def _processors(self) -> PR.LogitProcessors:
+        if self._proc is None:
+            raise RuntimeError("logit processors are off (set_logit_processors)")
+        return self._proc
+
+    def set_slot_processors(self, slot: int, prompt_tokens, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+                            frequency_penalty: float = 0.0, logit_bias: Optional[Dict] = None):
+        """sequence `slot` starts over: nothing generated yet, `prompt_tokens` marked as its prompt, and these controls from its
+        next draw on.  ValueError with the reason: repetition_penalty not finite and > 0, a penalty not finite, a bias id outside
+        the vocabulary or a bias value not finite."""
+        self._processors().set_row(slot, prompt_tokens, repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
+
+    # the processors' buffers (None while they are off): what the samplers read, the state table, the parameter and bias rows
+    adj_logits = property(lambda self: None if self._proc is None else self._proc.adj)
+    lp_state = property(lambda self: None if self._proc is None else self._proc.state)
+    lp_params = property(lambda self: None if self._proc is None else self._proc.params)
+    lp_bias = property(lambda self: None if self._proc is None else self._proc.bias)
+
+    def _feature_loop_state(self):
+        """the features' share of what a captured step carries from replay to replay"""
+        return (list(self._lp.tensors()) if self._lp is not None else []) + \
+               (list(self._proc.loop_tensors()) if self._proc is not None else [])
+
+    def _feature_key(self):
+        """the features' share of a captured step's key"""
+        return (None if self._lp is None else self._lp.top_n, self._proc is not None)

@@ -39,6 +39,7 @@ if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
 from teal_amd import runtime  # noqa: E402
+from teal_amd.gpt_fast.engine_features import pointer_key, relayout  # noqa: E402
 from teal_amd.gpt_fast.model import ModelArgs, Transformer  # noqa: E402
 from teal_amd.monkeypatch import monkeypatch_layer  # noqa: E402
 from teal_amd.utils import PROJS, get_layer_greedy_sparsities  # noqa: E402
@@ -315,15 +316,7 @@ class GraphedDecoder:
             self.tok.copy_(cur_token.view(1, 1))
         if input_pos is not None:
             self.pos.copy_(input_pos)
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):  # warm-up outside capture: workspace + allocator pools
-            for _ in range(2):
-                self._step()
-        torch.cuda.current_stream().wait_stream(s)
-        self.graph = torch.cuda.CUDAGraph()
-        with runtime.graph_capture(self.graph):
-            self.out_tok = self._step()
+        self.graph, self.out_tok = runtime.capture_graph(self._step, warmups=2)  # (warm-ups: workspace + allocator pools)
 
     def __call__(self, cur_token: torch.Tensor, input_pos: torch.Tensor) -> torch.Tensor:
         self.tok.copy_(cur_token.view(1, 1))
@@ -354,25 +347,14 @@ class GraphedPrefill:
             return self.model(prompt.view(1, -1), torch.arange(0, T, device=prompt.device))
         # everything the captured launches hold raw pointers to: a re-laid-out weight (DecodeEngine / monkeypatch
         # to_column_major replace the storage) or a re-allocated KV cache forces a new capture
-        key = (T, self.model.max_seq_length, self.model.output.weight.data_ptr(), self.model.tok_embeddings.weight.data_ptr()) + tuple(
-            p for layer in self.model.layers for p in (layer.attention.kv_cache.k_cache.data_ptr(), layer.attention.kv_cache.v_cache.data_ptr(),
-                                                       layer.attention.wqkv.weight.data_ptr(), layer.attention.wo.weight.data_ptr(),
-                                                       layer.feed_forward.w1.weight.data_ptr(), layer.feed_forward.w2.weight.data_ptr(),
-                                                       layer.feed_forward.w3.weight.data_ptr()))
+        key = (T,) + pointer_key(self.model, freqs=False)
         if key not in self.graphs:
             dev = prompt.device
             toks = torch.zeros(1, T, dtype=torch.int, device=dev)
             pos = torch.arange(0, T, device=dev)
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                toks.copy_(prompt.view(1, -1))
-                self.model(toks, pos)  # warm-up outside capture (allocator pools, GEMM heuristics)
-            torch.cuda.current_stream().wait_stream(s)
-            g = torch.cuda.CUDAGraph()
-            try:
-                with runtime.graph_capture(g):
-                    logits = self.model(toks, pos)
+            toks.copy_(prompt.view(1, -1))
+            try:  # (the warm-up outside capture: allocator pools, GEMM heuristics)
+                g, logits = runtime.capture_graph(lambda: self.model(toks, pos))
             except Exception as e:  # noqa: BLE001
                 # a sharded model's pass holds one all-reduce per attention and per MLP (tp._reduce_hook): if the collective
                 # cannot be captured on this stack, run the pass op by op instead of aborting the run (no silent change for an
@@ -403,9 +385,7 @@ class EngineDecoder:
         self._engine, self._key = None, None
 
     def _cache_key(self):
-        m = self.torch_model
-        return (m.max_seq_length,) + tuple(p for layer in m.layers for p in (layer.attention.kv_cache.k_cache.data_ptr(),
-                                                                              layer.attention.kv_cache.v_cache.data_ptr()))
+        return pointer_key(self.torch_model, weights=False)
 
     @property
     def model(self):
@@ -424,12 +404,7 @@ class EngineDecoder:
 def relayout_for_engine(model: Transformer) -> None:
     """The fused engine re-lays every projection (and lm_head) out column-major when it is built — lazily, after the first
     prefill.  Do it up front so that a prefill graph never captures pointers to storage that is freed later."""
-    from teal_amd.monkeypatch import UP_SHIFT_BYTES, to_column_major
-    for layer in model.layers:
-        for lin in (layer.attention.wqkv, layer.attention.wo, layer.feed_forward.w1, layer.feed_forward.w3, layer.feed_forward.w2):
-            if not hasattr(lin, "scales_and_zeros"):  # (an int4 image is packed column-gathered already)
-                to_column_major(lin, shift_bytes=UP_SHIFT_BYTES if lin is layer.feed_forward.w3 else 0)
-    to_column_major(model.output)
+    relayout(model)
 
 
 @torch.no_grad()

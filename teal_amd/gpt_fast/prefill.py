@@ -25,7 +25,7 @@ from typing import Optional
 import torch
 
 from .. import _lib, runtime
-from ..monkeypatch import UP_SHIFT_BYTES, to_column_major
+from .engine_features import dense_16bit_refusal, pointer_key, relayout
 from .model import Transformer
 
 MAX_T = 16  # most tokens of a pass; the hand-over layout is [feature][8] for T <= 8 and [feature][16] for 9 <= T <= 16 (buffers sized for 16)
@@ -48,15 +48,11 @@ class PrefillEngine:
         cfg = model.config
         if int(getattr(model, "tp_world", 1)) > 1:
             return "tensor-parallel models prefill through the module path (its all-reduce hooks)"
-        lins = [lin for layer in model.layers for lin in (layer.attention.wqkv, layer.attention.wo, layer.feed_forward.w1,
-                                                         layer.feed_forward.w3, layer.feed_forward.w2)] + [model.output]
-        if any(hasattr(lin, "scales_and_zeros") or hasattr(lin, "scales") for lin in lins):
-            return "quantised weights prefill through the module path"
+        why = dense_16bit_refusal(model, lambda lin: hasattr(lin, "scales_and_zeros") or hasattr(lin, "scales"),
+                                  "quantised weights prefill through the module path")
+        if why is not None:
+            return why
         dt = model.output.weight.dtype
-        if dt not in (torch.float16, torch.bfloat16) or any(lin.weight.dtype != dt for lin in lins):
-            return f"weights are not uniformly fp16 / bf16: {dt}"
-        if not model.output.weight.is_cuda:
-            return "model is not on a HIP device"
         inter = model.layers[0].feed_forward.w1.out_features
         qd, kv = cfg.n_head * cfg.head_dim, cfg.n_local_heads * cfg.head_dim
         if cfg.head_dim not in (64, 128) or cfg.dim != qd or cfg.dim % 256 or cfg.dim > 16384 or inter % 256 or (qd + 2 * kv) % 256:
@@ -80,10 +76,7 @@ class PrefillEngine:
         self.model, cfg = model, model.config
         dev, dt = model.output.weight.device, model.output.weight.dtype
         self.code = runtime.dtype_code(dt)
-        for layer in model.layers:  # the decode step's layout (idempotent: monkeypatch_layer / DecodeEngine did it already)
-            for lin in (layer.attention.wqkv, layer.attention.wo, layer.feed_forward.w1, layer.feed_forward.w3, layer.feed_forward.w2):
-                to_column_major(lin, shift_bytes=UP_SHIFT_BYTES if lin is layer.feed_forward.w3 else 0)
-        to_column_major(model.output)
+        relayout(model)  # the decode step's layout (idempotent: monkeypatch_layer / DecodeEngine did it already)
         self.dim, self.hd = cfg.dim, cfg.head_dim
         self.kv = cfg.n_local_heads * cfg.head_dim
         self.nqkv = self.dim + 2 * self.kv
@@ -107,12 +100,7 @@ class PrefillEngine:
 
     def key(self):
         """everything the launches hold raw pointers to: a re-laid-out weight or a re-allocated KV cache needs a new engine"""
-        m = self.model
-        return (m.max_seq_length, m.output.weight.data_ptr(), m.tok_embeddings.weight.data_ptr(), m.freqs_cis.data_ptr()) + tuple(
-            p for layer in m.layers for p in (layer.attention.kv_cache.k_cache.data_ptr(), layer.attention.kv_cache.v_cache.data_ptr(),
-                                              layer.attention.wqkv.weight.data_ptr(), layer.attention.wo.weight.data_ptr(),
-                                              layer.feed_forward.w1.weight.data_ptr(), layer.feed_forward.w2.weight.data_ptr(),
-                                              layer.feed_forward.w3.weight.data_ptr()))
+        return pointer_key(self.model)
 
     def _caches(self, at):
         """the raw K / V cache pointers the pass writes rows 0 .. T-1 of"""
@@ -210,14 +198,7 @@ class FusedPrefill:
             return eng(prompt)
         if T not in self._graphs:
             static = prompt.clone()
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                eng(static)  # warm-up outside capture
-            torch.cuda.current_stream().wait_stream(s)
-            g = torch.cuda.CUDAGraph()
-            with runtime.graph_capture(g):
-                logits = eng(static)
+            g, logits = runtime.capture_graph(lambda: eng(static))
             self._graphs[T] = (g, static, logits)
         g, static, logits = self._graphs[T]
         static.copy_(prompt)

@@ -152,34 +152,13 @@ class SpeculativeDecoder:
         if rc != 0:
             _lib.check(rc, "teal_spec_accept")
 
-    def _state(self):
-        e = self.draft
-        return [t.clone() for t in (self.tokens, self.spec_pos, e.pos_buf, e.rng_state, self.out_len, self.n_acc, self.hist, self.out_seq)]
-
-    def _restore(self, s):
-        e = self.draft
-        for dst, src in zip((self.tokens, self.spec_pos, e.pos_buf, e.rng_state, self.out_len, self.n_acc, self.hist, self.out_seq), s):
-            dst.copy_(src)
-
     def capture(self):
         """one hipGraph of a whole round (warm-up outside capture; the state it advanced is put back)"""
-        if self._graph is not None:
-            return self._graph
-        state = self._state()
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self._launch_round()
-        torch.cuda.current_stream().wait_stream(s)
-        self._restore(state)
-        g = torch.cuda.CUDAGraph()
-        try:
-            with runtime.graph_capture(g):
-                self._launch_round()
-        finally:
-            self._restore(state)
-        self._graph = g
-        return g
+        if self._graph is None:
+            e = self.draft
+            self._graph, _ = runtime.capture_graph(self._launch_round, (self.tokens, self.spec_pos, e.pos_buf, e.rng_state, self.out_len,
+                                                                        self.n_acc, self.hist, self.out_seq))
+        return self._graph
 
     @torch.no_grad()
     def round(self) -> int:

@@ -56,6 +56,35 @@ def graph_capture(g: "torch.cuda.CUDAGraph", **kw):
     return torch.cuda.graph(g, **kw)
 
 
+def capture_graph(step, state=(), warmups: int = 1):
+    """(graph, value): step() captured into a hipGraph, and what the captured step() returned.  step() first runs `warmups`
+    times on a side stream outside capture (workspace, allocator pools; the KV rows it writes are rewritten by the real run).
+    `state`: the tensors step() carries from call to call — they are put back before the capturing run and again after it,
+    also when the capture raises (a caller that then goes on eagerly starts from the same state).  Without `state` nothing is
+    undone: what the warm-ups did stands (the capturing call itself is recorded, not executed)."""
+    state = list(state)
+    saved = [t.clone() for t in state]
+
+    def restore():
+        for t, v in zip(state, saved):
+            t.copy_(v)
+
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(warmups):
+            step()
+    torch.cuda.current_stream().wait_stream(s)
+    restore()
+    g = torch.cuda.CUDAGraph()
+    try:
+        with graph_capture(g):
+            value = step()
+    finally:
+        restore()
+    return g, value
+
+
 def stream_ptr() -> int:
     return torch.cuda.current_stream().cuda_stream
 
