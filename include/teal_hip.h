@@ -557,6 +557,42 @@ int teal_logit_adjust(const void* logits, size_t logits_stride, int vocab, int d
                       int32_t* state, const float* params, const void* bias, void* out, size_t out_stride, const int32_t* active,
                       int slot0, void* stream);
 
+/* ---- per-request sampling, teal_amd/csrc/teal_sample_rows.hip -----------------------------------------------------------------
+ * One launch in the place of a step's B teal_sample_topk* launches: row r < B (one workgroup each) draws a token from its row of
+ * `vocab` 16-bit logits under its own four 32-bit words params[r] = {fp32 temperature, int32 top_k, fp32 top_p, fp32 min_p}, read
+ * from device memory, so a captured launch serves any mix of settings.  The filters apply in this order:
+ *   1. temperature   inv = 1 / max(temperature, 1e-5);  mx = the row's largest logit;  t_i = fl(fl(x_i - mx) * inv)
+ *                    (fp32, one rounding per operation: what teal_sample_topk* compute).
+ *   2. top_k         0 < top_k < vocab: every logit not below the top_k-th largest VALUE stays, ties at the pivot included; any
+ *                    other top_k: no filter.  The surviving set is K1.  (teal_sample_topk*'s filter.)
+ *   3. top_p         over K1, with w_i = exp(t_i), Z = the sum of w over K1 and A(v) = the mass of the members of K1 whose value is
+ *                    strictly greater than v: a logit of value v stays iff A(v) < top_p * Z.  (The nucleus of the renormalised
+ *                    top-k set, decided by value: equal logits stay or go together, the maximum always stays.)  top_p >= 1: no
+ *                    filter, and no sum is formed.  top_p <= 0 or not finite is the caller's error.
+ *   4. min_p         a logit stays iff exp(t_i) >= min_p: its probability is at least min_p times the largest one's (renormalising
+ *                    does not change that ratio).  min_p == 0: no filter.  min_p outside [0, 1) is the caller's error.
+ *   5. the race      among the logits that pass all three: argmax_i expf(t_i) / -logf(u_i), u_i = ((hash3(seed, ctr, i) >> 8) + 0.5)
+ *                    / 2^24 — teal_sample_topk*'s fp32 expression and random stream, the smallest index winning exact ties; then
+ *                    tokens[r] = token, history[r][c] = token if c < history_len (c: the draw counter before), the draw counter
+ *                    goes up by one and pos[r] by one where `pos` is given.
+ * Every filter has the form "value >= threshold" and the maximum passes all of them: the kept sets are nested, and kept_out[r]
+ * (optional) — how many logits entered the race — identifies the set.  With top_p = 1 and min_p = 0 a row draws the very token
+ * teal_sample_topk_slot draws from the same logits, temperature, top_k and rng state (bit-equal scores).
+ * Rounding: the masses are summed as 64-bit fixed-point integers (trunc(expf(t_i) * 2^40)), A and Z are within about
+ * (E + 2) * 2^-24 * Z of exact for an expf good to E ulps, and top_p * Z is formed in fp64; a decision closer than 1e-5 * Z to a
+ * boundary (or, min_p, exp(t) within 1e-5 * min_p of min_p) may fall either way against exact arithmetic.  Integer sums do not
+ * depend on their order: a row's token and kept count depend only on that row's logits, parameters and rng state — not on B, the
+ * slot, the other rows or the replay.  NaN logits and a row that is all -inf are outside the contract.
+ * Row r serves slot slot0 + r.  active != NULL: a row whose bit (slot0 + r) of active[0] (device int32) is clear changes nothing.
+ * rng_state: uint64 [B][2] = {seed, draw counter}; tokens, pos (or NULL), kept_out (or NULL): int32 [B]; history: int32
+ * [B][history_len] or NULL; logits_stride in elements.
+ * vocab a multiple of 8 in 8..131072 (else TEAL_ERR_SHAPE); B outside 1..8, slot0 < 0, slot0 + B > 32, history_len < 0 with a
+ * history or a null required pointer TEAL_ERR_ARG; TEAL_ERR_DTYPE; a row base (or, B > 1, a stride) off 16 bytes TEAL_ERR_ALIGN;
+ * every check comes before any HIP call. */
+int teal_sample_rows(const void* logits, size_t logits_stride, int vocab, int dtype, int B, const void* params, void* rng_state,
+                     int32_t* tokens, int32_t* pos, int32_t* history, int history_len, int32_t* kept_out, const int32_t* active,
+                     int slot0, void* stream);
+
 /* ---- shared prompt prefixes of continuous batching, teal_amd/csrc/teal_prefix.hip ------------------------------------
  * A prefix is a token sequence whose K / V rows (every layer) are computed once and kept in a device store; a request that names
  * it is admitted by copying those rows into its slot's caches and running a prompt pass over its own tokens only. */

@@ -25,6 +25,7 @@ import torch
 from .. import _lib, runtime
 from ..kernels.sparse_gemv import BATCH_MAX, batched_segs
 from . import logit_processors as PR
+from . import sampling as SM
 from .engine_features import SamplerFeatures, _SlotCaches, dense_16bit_refusal, relayout
 from .model import Transformer
 from .prefill import IN_NORM, IN_SILU_MUL, IN_XT, MAX_T, PrefillEngine, PrefillIn
@@ -199,14 +200,30 @@ class BatchedDecodeEngine(SamplerFeatures):
         if self._proc is not None:  # tok_buf still holds the tokens this step was fed: each sequence's latest
             self._proc.launch(self.logits, V, self.B, self.tok_buf, True, st=st)
             src = self._proc.adj
-        for b in range(self.B):
-            rc = self.L.teal_sample_topk_ws(src[b].data_ptr(), V, self.code, int(top_k or 0), float(temperature),
-                                            self.rng_state[b].data_ptr(), self.tok_buf[b:].data_ptr(), self.pos_buf[b:].data_ptr(),
-                                            self.history[b].data_ptr(), self.history.shape[1], self.ws.data_ptr(), self.ws.numel() * 4, st)
-            if rc != 0:
-                _lib.check(rc, "teal_sample_topk (batched)")
+        if self._samp is not None:  # one launch, every sequence under its own row of settings
+            self._samp.launch(src, V, self.B, self.rng_state, self.tok_buf, self.pos_buf, self.history, self.history.shape[1], st=st)
+        else:
+            for b in range(self.B):
+                rc = self.L.teal_sample_topk_ws(src[b].data_ptr(), V, self.code, int(top_k or 0), float(temperature),
+                                                self.rng_state[b].data_ptr(), self.tok_buf[b:].data_ptr(), self.pos_buf[b:].data_ptr(),
+                                                self.history[b].data_ptr(), self.history.shape[1], self.ws.data_ptr(),
+                                                self.ws.numel() * 4, st)
+                if rc != 0:
+                    _lib.check(rc, "teal_sample_topk (batched)")
         if self._lp is not None:
             self._lp.launch(self.logits, V, V, self.code, self.B, self.tok_buf, self.rng_state, st=st)
+
+    @torch.no_grad()
+    def sample_first(self, logits_rows: torch.Tensor) -> torch.Tensor:
+        """per-request sampling on: the B tokens after the prompts, one sampling launch over the prompt pass's last-position logits
+        [B, vocab] under each sequence's own row of settings -> int32 [B].  Sequence b draws from a stream of its own, seed + B + b
+        (decode_n's streams are seed + b from draw 0); position, history and the decode streams do not move."""
+        rows = logits_rows.to(self.dtype).contiguous()
+        assert rows.shape == (self.B, self.cfg.vocab_size)
+        state = torch.tensor([[self._seed + self.B + b, 0] for b in range(self.B)], dtype=torch.int64).to(rows.device)
+        tok = torch.zeros(self.B, dtype=torch.int32, device=rows.device)
+        self._sampling().launch(rows, rows.shape[1], self.B, state, tok, None, None, 0)
+        return tok
 
     def read_logprobs(self, n: int):
         """(lp [B, n], top_ids [B, n, top_n], top_lp [B, n, top_n]) of the tokens history[:, :n] — decode_n's"""
@@ -223,7 +240,7 @@ class BatchedDecodeEngine(SamplerFeatures):
     def capture(self, temperature: float = 0.8, top_k: Optional[int] = 200):
         """hipGraph of one step for all B sequences: the forward pass and B sampler launches (each sequence's token, position and
         draw counter stay on the device).  The warm-up step's state is put back."""
-        key = (float(temperature), int(top_k or 0)) + self._feature_key()
+        key = self._step_key(temperature, top_k) + self._feature_key()
         if self._graph is not None and self._graph_key == key:
             return self._graph
         g, _ = runtime.capture_graph(lambda: self._self_step(temperature, top_k), self._loop_state())
@@ -436,8 +453,12 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         if self._proc is not None:  # tok_buf still holds the tokens this step was fed; an inactive slot counts nothing
             self._proc.launch(self.logits, self.cfg.vocab_size, self.B, self.tok_buf, True, active=self._active, st=st)
             src = self._proc.adj
-        for b in range(self.B):
-            self._sample_slot(b, src[b], temperature, top_k, st)
+        if self._samp is not None:  # one launch, every active slot under its own row of settings
+            self._samp.launch(src, self.cfg.vocab_size, self.B, self.rng_state, self.tok_buf, self.pos_buf, self.history,
+                              self.history.shape[1], active=self._active, st=st)
+        else:
+            for b in range(self.B):
+                self._sample_slot(b, src[b], temperature, top_k, st)
         if self._lp is not None:  # predicated on the active word the samplers saw (retire clears bits behind it)
             V = self.cfg.vocab_size
             self._lp.launch(self.logits, V, V, self.code, self.B, self.tok_buf, self.rng_state, active=self._active, st=st)
@@ -551,7 +572,7 @@ class SlotDecodeEngine(BatchedDecodeEngine):
     @torch.no_grad()
     def admit(self, slot: int, tokens, budget: int, eos_id: Optional[int], seed: int, temperature: float = 0.8,
               top_k: Optional[int] = 200, prefix: Optional[str] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-              frequency_penalty: float = 0.0, logit_bias: Optional[Dict] = None):
+              frequency_penalty: float = 0.0, logit_bias: Optional[Dict] = None, top_p: float = 1.0, min_p: float = 0.0):
         """Request -> slot `slot` (free): the dense prompt pass into that slot's caches, the first token drawn from the last row's
         logits (draw 0 of the stream `seed`), the slot's token, position, history, rng state, budget and EOS set on the device and
         its bit set.  A request whose first token ends it (budget 1, EOS) is switched off again by the same retire rule.
@@ -559,7 +580,10 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         the slot and only the suffix is run, at positions P .. P+T-1: the request is served as prompt = prefix + suffix.
         repetition_penalty / presence_penalty / frequency_penalty / logit_bias: the request's logit processors (they need
         set_logit_processors(True); its prompt tokens — prefix + suffix — are marked, and every token it draws, the first
-        included, passes through them)."""
+        included, passes through them).
+        top_p / min_p: nucleus and min-p sampling of this request (they need set_sampling_params(True)).  With per-request sampling
+        on, `temperature`, `top_k`, `top_p` and `min_p` are written into the slot's parameter row and hold for every draw of the
+        request; off, `temperature` and `top_k` are those of this first draw only (run_steps has its own)."""
         s, B = int(slot), self.B
         prompt = torch.as_tensor(tokens, dtype=torch.int32).view(-1).to(self.logits.device)
         T = int(prompt.numel())
@@ -577,6 +601,10 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         controls = PR.check_controls(self.cfg.vocab_size, repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
         if self._proc is None and not PR.is_identity(controls):
             raise RuntimeError("logit processors are off (set_logit_processors)")
+        if self._samp is not None:  # (every admission: the slot's last request left its settings)
+            self._samp.set_row(s, temperature, top_k, top_p, min_p)
+        elif SM.check_sampling(top_p=top_p, min_p=min_p)["top_p"] < 1.0 or min_p > 0.0:
+            raise RuntimeError("per-request sampling is off (set_sampling_params)")
         if self._proc is not None:  # (every admission: the slot's last request left its counts and its parameters)
             self._proc.set_row(s, (pf.tokens if pf is not None else []) + prompt.tolist(), **controls)
         logits = self._prompt_pass(s, prompt) if pf is None else self._suffix_pass(s, pf, prompt)
@@ -591,7 +619,11 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         if self._proc is not None:  # the first draw: nothing generated yet, so nothing is counted
             self._proc.launch(logits, 0, 1, self.tok_buf[s:], False, row0=s, active=self._active, st=st)
             src = self._proc.adj[s]
-        self._sample_slot(s, src, temperature, top_k, st)
+        if self._samp is not None:
+            self._samp.launch(src, 0, 1, self.rng_state[s], self.tok_buf[s:], self.pos_buf[s:], self.history[s], self.history.shape[1],
+                              row0=s, active=self._active, st=st)
+        else:
+            self._sample_slot(s, src, temperature, top_k, st)
         if self._lp is not None:  # the request's first token: entry 0 of its row
             self._lp.launch(logits, 0, self.cfg.vocab_size, self.code, 1, self.tok_buf[s:], self.rng_state[s], row0=s,
                             active=self._active, st=st)

@@ -29,6 +29,7 @@ from .batched import SLOT_ACTIVE, SLOT_FINISH, SLOT_PRODUCED, SLOT_STEP
 from .logit_processors import fp32
 
 REFILL = ("free", "all")
+SAMPLING = ("temperature", "top_k", "top_p", "min_p")
 
 
 @dataclass
@@ -45,6 +46,21 @@ class Request:
     presence_penalty: Optional[float] = None
     frequency_penalty: Optional[float] = None
     logit_bias: Optional[Dict[str, float]] = None
+    # sampling (None: the batcher's default).  In order of application: temperature, top_k (0: off), top_p over the renormalised
+    # top-k set (1: off), min_p relative to the most likely token (0: off)
+    temperature: Optional[float] = None
+    top_k: Optional[int] = None
+    top_p: Optional[float] = None
+    min_p: Optional[float] = None
+
+    def sampling(self, defaults: Dict) -> Dict:
+        """the request's four sampling settings, `defaults` (a dict of the four) where it sets none of its own"""
+        out = {}
+        for name in SAMPLING:
+            v = getattr(self, name)
+            out[name] = defaults[name] if v is None else v
+        out["top_k"] = int(out["top_k"] or 0)
+        return out
 
     def controls(self, defaults: Optional[Dict] = None) -> Dict:
         """the controls that differ from "off" — the keyword arguments of the engine's admit; {}: the request asks for none"""
@@ -86,6 +102,32 @@ def parse_controls(d: dict, where: str) -> Dict:
         if not isinstance(b, dict) or not all(isinstance(k, str) and k.isdigit() and _number(v) for k, v in b.items()):
             raise ValueError(f"{where}: \"logit_bias\" must be an object of token ids and finite numbers, {{\"<id>\": value}}")
         out["logit_bias"] = {k: float(v) for k, v in b.items()}
+    return out
+
+
+def parse_sampling(d: dict, where: str) -> Dict:
+    """the sampling fields and the seed of one request object, validated; only those present"""
+    out = {}
+    if "temperature" in d:
+        if not _number(d["temperature"]) or d["temperature"] < 0:
+            raise ValueError(f"{where}: \"temperature\" must be a finite number >= 0")
+        out["temperature"] = float(d["temperature"])
+    if "top_k" in d:
+        if not isinstance(d["top_k"], int) or isinstance(d["top_k"], bool) or not 0 <= d["top_k"] < 2 ** 31:
+            raise ValueError(f"{where}: \"top_k\" must be a non-negative integer (0: off)")
+        out["top_k"] = int(d["top_k"])
+    if "top_p" in d:
+        if not _number(d["top_p"]) or fp32(d["top_p"]) <= 0:
+            raise ValueError(f"{where}: \"top_p\" must be a finite number > 0 (1: off)")
+        out["top_p"] = float(d["top_p"])
+    if "min_p" in d:
+        if not _number(d["min_p"]) or d["min_p"] < 0 or fp32(d["min_p"]) >= 1:
+            raise ValueError(f"{where}: \"min_p\" must be a number in [0, 1) (0: off)")
+        out["min_p"] = float(d["min_p"])
+    if "seed" in d:
+        if not isinstance(d["seed"], int) or isinstance(d["seed"], bool) or not 0 <= d["seed"] < 2 ** 63:
+            raise ValueError(f"{where}: \"seed\" must be a non-negative integer below 2^63")
+        out["seed"] = int(d["seed"])
     return out
 
 
@@ -143,7 +185,8 @@ def parse_requests(lines: Sequence[str], default_max_new_tokens: int, tokenizer=
     does), with an optional "max_new_tokens" (default: `default_max_new_tokens`).  Blank lines are skipped.  A line may carry
     "prefix": an id of `prefixes`; its tokens / prompt are then the suffix, and a prompt is encoded WITHOUT a BOS (the prefix
     holds it).  A line may carry its own logit processors: "repetition_penalty" (> 0), "presence_penalty", "frequency_penalty"
-    and "logit_bias" ({"<id>": value})."""
+    and "logit_bias" ({"<id>": value}), its own sampling settings: "temperature" (>= 0), "top_k" (0: off), "top_p" (> 0; 1: off) and
+    "min_p" (in [0, 1); 0: off), and its own "seed"."""
     out = []
     for i, line in enumerate(lines):
         if not line.strip():
@@ -170,7 +213,8 @@ def parse_requests(lines: Sequence[str], default_max_new_tokens: int, tokenizer=
         n = d.get("max_new_tokens", default_max_new_tokens)
         if not isinstance(n, int) or n < 1:
             raise ValueError(f"request line {i + 1}: \"max_new_tokens\" must be a positive integer")
-        out.append(Request([int(t) for t in toks], n, eos_id, prefix=pid, **parse_controls(d, f"request line {i + 1}")))
+        out.append(Request([int(t) for t in toks], n, eos_id, prefix=pid, **parse_controls(d, f"request line {i + 1}"),
+                           **parse_sampling(d, f"request line {i + 1}")))
     if not out:
         raise ValueError("no requests")
     return out
@@ -210,12 +254,16 @@ class ContinuousBatcher:
     Logit processors: `repetition_penalty`, `presence_penalty` and `frequency_penalty` here are the defaults of requests that set
     none of their own.  When any request (or a default) asks for a processor the engine also offers set_logit_processors(True),
     called once before the first admission, and admit(..., repetition_penalty=, presence_penalty=, frequency_penalty=,
-    logit_bias=); only requests that ask for one are admitted with those keywords."""
+    logit_bias=); only requests that ask for one are admitted with those keywords.
+    Sampling: `temperature`, `top_k`, `top_p` and `min_p` here are the defaults of requests that set none of their own.  When a
+    default or some request differs from (temperature, top_k, 1, 0) the engine also offers set_sampling_params(True), called once
+    before the first admission, and admit(..., top_p=, min_p=); every request is then admitted with its own four settings, which
+    hold for all of its draws, and run_steps' temperature and top_k no longer matter.  Otherwise every call is today's."""
 
     def __init__(self, engine, sync_every: int = 8, refill: str = "free", temperature: float = 0.8, top_k: Optional[int] = 200,
                  seed: int = 1234, use_graph: bool = True, prefixes: Optional[Dict[str, List[int]]] = None,
                  logprobs: Optional[int] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-                 frequency_penalty: float = 0.0):
+                 frequency_penalty: float = 0.0, top_p: float = 1.0, min_p: float = 0.0):
         if refill not in REFILL:
             raise ValueError(f"refill must be one of {REFILL}")
         if int(sync_every) < 1:
@@ -229,6 +277,8 @@ class ContinuousBatcher:
         self.defaults = parse_controls({"repetition_penalty": repetition_penalty, "presence_penalty": presence_penalty,
                                         "frequency_penalty": frequency_penalty}, "ContinuousBatcher")
         self._processors_set = False
+        parse_sampling({"top_p": top_p, "min_p": min_p}, "ContinuousBatcher")
+        self.top_p, self.min_p, self._sampling_set = float(top_p), float(min_p), False
 
     def _clock(self):
         try:
@@ -264,6 +314,12 @@ class ContinuousBatcher:
         if any(controls) and not self._processors_set:  # once: it drops the engine's captured step
             eng.set_logit_processors(True)
             self._processors_set = True
+        base = {"temperature": self.temperature, "top_k": int(self.top_k or 0), "top_p": self.top_p, "min_p": self.min_p}
+        sampling = [r.sampling(base) if hasattr(r, "sampling") else dict(base) for r in requests]
+        plain = dict(base, top_p=1.0, min_p=0.0)  # what the fused top-k samplers serve: the batcher's two scalars
+        if any(s != plain for s in sampling) and not self._sampling_set:  # once: it drops the engine's captured step
+            eng.set_sampling_params(True)
+            self._sampling_set = True
         pending = deque(range(len(requests)))
         lps: List[Optional[List[float]]] = [None] * len(requests)
         tops: List[Optional[List]] = [None] * len(requests)
@@ -287,8 +343,11 @@ class ContinuousBatcher:
                     q = requests[r]
                     kw = {"prefix": q.prefix} if plen[r] else {}
                     kw.update(controls[r])
-                    eng.admit(s, q.tokens, q.max_new_tokens, q.eos_id, self.seed + r if q.seed is None else q.seed, self.temperature,
-                              self.top_k, **kw)
+                    T, k = self.temperature, self.top_k
+                    if self._sampling_set:
+                        T, k = sampling[r]["temperature"], sampling[r]["top_k"]
+                        kw.update(top_p=sampling[r]["top_p"], min_p=sampling[r]["min_p"])
+                    eng.admit(s, q.tokens, q.max_new_tokens, q.eos_id, self.seed + r if q.seed is None else q.seed, T, k, **kw)
                     prefix_admissions += 1 if plen[r] else 0
                     prefix_rows += plen[r]
                     slot_req[s], admitted_at[s], slots_used[r] = r, step0 + steps, s

@@ -717,6 +717,10 @@ class DecodeEngine(SamplerFeatures):
         feed=True also carries the loop state on the device: the token goes into the buffer the next
         step reads, the position is advanced and the token is appended to `history`."""
         tok_out = self.tok_buf if feed else self.token
+        if self._samp is not None:  # per-request sampling: the row of settings, not the two scalars
+            self._samp.launch(logits, 0, 1, self.rng_state, tok_out, self.pos_buf if feed else None, self.history if feed else None,
+                              self.history.numel())
+            return tok_out
         rc = self.L.teal_sample_topk_ws(logits.data_ptr(), self.cfg.vocab_size, self.code, int(top_k or 0), float(temperature),
                                         self.rng_state.data_ptr(), tok_out.data_ptr(),
                                         self.pos_buf.data_ptr() if feed else None,
@@ -738,9 +742,14 @@ class DecodeEngine(SamplerFeatures):
             self._record_logprobs(logits, self.tok_buf)
 
     # ---- logit processors and token logprobs (SamplerFeatures): one more launch in front of / behind the sampler, when on -----
+    speculating = False  # a SpeculativeDecoder drafts with this engine (set by it, cleared by its release())
+
     def _feature_refusal(self, what: str):
+        if what == "per-request sampling" and self.speculating:
+            raise NotImplementedError("per-request sampling is not available under speculative decoding: the accept rule compares "
+                                      "the draft's and the target's distributions under one temperature and top_k")
         if self.reduce is not None:
-            launch = {"logprobs": "logprob", "logit processors": "processor"}[what]
+            launch = {"logprobs": "logprob", "logit processors": "processor", "per-request sampling": "sampling"}[what]
             raise NotImplementedError(f"{what} are not available under tensor parallelism: this rank's lm_head holds a slice of "
                                       f"the vocabulary, and the {launch} launch reads whole rows")
 
@@ -789,7 +798,7 @@ class DecodeEngine(SamplerFeatures):
             for _ in range(int(tokens)):
                 self._self_step(temperature, top_k)
 
-        return self._capture((float(temperature), int(top_k or 0), int(tokens)) + self._feature_key(), steps)
+        return self._capture(self._step_key(temperature, top_k) + (int(tokens),) + self._feature_key(), steps)
 
     @torch.no_grad()
     def begin_sequence(self):

@@ -1,6 +1,6 @@
 """What the fused engines share on the host side: the model's linears and the pointers a captured pass holds, the checks
-every dense-chain engine starts `supports` with, and the sampler-side features (token logprobs, logit processors) of the decode
-engines.  A new per-request feature of the sampler goes into `SamplerFeatures` once, plus each engine's `_sample`.
+every dense-chain engine starts `supports` with, and the sampler-side features (token logprobs, logit processors, per-request
+sampling) of the decode engines.  A new per-request feature of the sampler goes into `SamplerFeatures` once, plus each engine's `_sample`.
 """
 from __future__ import annotations
 
@@ -11,6 +11,7 @@ import torch
 from ..monkeypatch import UP_SHIFT_BYTES, to_column_major
 from . import logit_processors as PR
 from . import logprobs as LP
+from . import sampling as SM
 
 
 def block_linears(layer):
@@ -76,15 +77,16 @@ class _SlotCaches:
 
 
 class SamplerFeatures:
-    """Token logprobs (logprobs.py: one launch behind the sampler) and per-request logit processors (logit_processors.py: one
-    launch in front of it), both off until switched on.  The host class provides `_feature_rows` (its sequences), `history`
+    """Token logprobs (logprobs.py: one launch behind the sampler), per-request logit processors (logit_processors.py: one
+    launch in front of it) and per-request sampling (sampling.py: one launch in the samplers' place), all off until switched on.  The host class provides `_feature_rows` (its sequences), `history`
     (int32 [..., length]: a logprob row is as long), `cfg.vocab_size`, `dtype` and a `_graph` the setters drop."""
 
     _lp: Optional[LP.LogprobBuffers] = None      # set_logprobs
     _proc: Optional[PR.LogitProcessors] = None   # set_logit_processors
+    _samp: Optional[SM.SamplingParams] = None    # set_sampling_params
 
     def _feature_refusal(self, what: str) -> None:
-        """raises if this engine cannot switch `what` ("logprobs" / "logit processors") on"""
+        """raises if this engine cannot switch `what` ("logprobs" / "logit processors" / "per-request sampling") on"""
         return None
 
     def set_logprobs(self, n: Optional[int]):
@@ -124,6 +126,36 @@ class SamplerFeatures:
         the vocabulary or a bias value not finite."""
         self._processors().set_row(slot, prompt_tokens, repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
 
+    def set_sampling_params(self, on: bool):
+        """off (the default): the step's launches are exactly those without this feature, one fused top-k sampler per sequence
+        under the temperature and top_k the step is given.  on: ONE launch draws every sequence's token under that sequence's own
+        temperature, top_k, top_p and min_p (set_slot_sampling; temperature 1 and no filter until set), read from device memory:
+        the step no longer depends on the temperature and top_k it is given, and one captured step serves any mix.  Drops the
+        captured graphs."""
+        if on:
+            self._feature_refusal("per-request sampling")
+        self._samp = SM.SamplingParams(self._feature_rows, self.cfg.vocab_size, self.dtype, self.history.device) if on else None
+        self._graph = None
+
+    def _sampling(self) -> SM.SamplingParams:
+        if self._samp is None:
+            raise RuntimeError("per-request sampling is off (set_sampling_params)")
+        return self._samp
+
+    def set_slot_sampling(self, slot: int, temperature: float, top_k: Optional[int], top_p: float = 1.0, min_p: float = 0.0):
+        """sequence `slot` draws under these settings from its next draw on.  ValueError with the reason: a setting not finite,
+        temperature < 0, top_k negative, top_p <= 0, min_p outside [0, 1)."""
+        self._sampling().set_row(slot, temperature, top_k, top_p, min_p)
+
+    # the sampling rows (None while the feature is off): the parameter words and each row's last kept count
+    sampling_params = property(lambda self: None if self._samp is None else self._samp.params)
+    sampling_kept = property(lambda self: None if self._samp is None else self._samp.kept)
+
+    def _step_key(self, temperature, top_k):
+        """the sampler's share of a captured step's key: the two scalars baked into the fused top-k sampler's launches, or —
+        per-request sampling on — nothing, the rows being read on the device"""
+        return (float(temperature), int(top_k or 0)) if self._samp is None else ("rows",)
+
     # the processors' buffers (None while they are off): what the samplers read, the state table, the parameter and bias rows
     adj_logits = property(lambda self: None if self._proc is None else self._proc.adj)
     lp_state = property(lambda self: None if self._proc is None else self._proc.state)
@@ -133,8 +165,9 @@ class SamplerFeatures:
     def _feature_loop_state(self):
         """the features' share of what a captured step carries from replay to replay"""
         return (list(self._lp.tensors()) if self._lp is not None else []) + \
-               (list(self._proc.loop_tensors()) if self._proc is not None else [])
+               (list(self._proc.loop_tensors()) if self._proc is not None else []) + \
+               (list(self._samp.loop_tensors()) if self._samp is not None else [])
 
     def _feature_key(self):
-        """the features' share of a captured step's key"""
-        return (None if self._lp is None else self._lp.top_n, self._proc is not None)
+        """the features' share of a captured step's key (per-request sampling adds its word only while it is on)"""
+        return (None if self._lp is None else self._lp.top_n, self._proc is not None) + (("sampling",) if self._samp is not None else ())

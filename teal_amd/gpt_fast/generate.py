@@ -410,9 +410,10 @@ def relayout_for_engine(model: Transformer) -> None:
 @torch.no_grad()
 def generate(model: Transformer, prompt: torch.Tensor, max_new_tokens: int, decoder: GraphedDecoder,
              temperature: float = 0.8, top_k: Optional[int] = 200, prefill: Optional[GraphedPrefill] = None,
-             processors: Optional[Dict] = None) -> torch.Tensor:
+             processors: Optional[Dict] = None, sampling: Optional[Dict] = None) -> torch.Tensor:
     """prefill (seq > 1: ops fall back to dense matmul) then max_new_tokens-1 decode steps.  processors (the fused engine only):
-    repetition_penalty / presence_penalty / frequency_penalty / logit_bias of this sample, applied to every draw."""
+    repetition_penalty / presence_penalty / frequency_penalty / logit_bias of this sample, applied to every draw.  sampling (the
+    fused engine only): top_p / min_p of this sample, next to the decoder's temperature and top_k, for every draw."""
     T = prompt.size(0)
     T_new = T + max_new_tokens
     dev = prompt.device
@@ -427,6 +428,12 @@ def generate(model: Transformer, prompt: torch.Tensor, max_new_tokens: int, deco
         if eng.adj_logits is None:
             eng.set_logit_processors(True)
         eng.set_slot_processors(0, prompt.tolist(), **processors)
+    if sampling:
+        if eng is None or logits.dtype != eng.dtype or logits.shape[-1] != eng.cfg.vocab_size:
+            raise ValueError("top_p / min_p need the fused engine's sampler for every draw")
+        if eng.sampling_params is None:
+            eng.set_sampling_params(True)
+        eng.set_slot_sampling(0, decoder.kw["temperature"], decoder.kw["top_k"], **sampling)
     if eng is not None and logits.dtype == eng.dtype and logits.shape[-1] == eng.cfg.vocab_size:
         # HIP engine: the token after the prompt comes from the same fused sampler as every later one (gpt-fast/generate.py:
         # 49-66 is ONE function for both), and the whole loop stays on the device
@@ -676,6 +683,34 @@ def check_processor_args(args) -> Dict:
     return c
 
 
+def check_sampling_args(args) -> Dict:
+    """--top_p / --min_p: {} when both are off, else {"top_p": ..., "min_p": ...}; every refusal is raised here, before anything is
+    loaded.  Nucleus and min-p sampling live in the fused engines' per-request sampling launch, so the flags need an engine path:
+    --compile / --engine (one sequence or --batch_size), where they are the setting of every row, or --requests, where they are
+    the defaults of requests that carry none of their own."""
+    from teal_amd.gpt_fast.sampling import check_sampling
+    c = {"top_p": 1.0 if getattr(args, "top_p", None) is None else args.top_p, "min_p": 0.0 if getattr(args, "min_p", None) is None else args.min_p}
+    for name, rule in (("top_p", "a finite number > 0 (1: off)"), ("min_p", "a number in [0, 1) (0: off)")):
+        try:
+            check_sampling(**{name: c[name]})
+        except ValueError:
+            raise SystemExit(f"--{name} must be {rule}, got {c[name]!r}") from None
+    if c["top_p"] >= 1.0 and c["min_p"] == 0.0:
+        return {}
+    flags = "--top_p / --min_p"
+    if getattr(args, "draft_checkpoint_path", None) is not None or getattr(args, "self_speculate", False):
+        raise SystemExit(f"{flags} do not combine with speculative decoding (the accept rule compares the models' distributions under "
+                         "one temperature and top_k)")
+    if int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1"))) > 1:
+        raise SystemExit(f"{flags} do not run under tensor parallelism (a rank's lm_head holds a slice of the vocabulary)")
+    if getattr(args, "dense", False) or (not args.synthetic and args.hist_path is None):
+        raise SystemExit(f"{flags} need TEAL thresholds (--hist_path, or --synthetic): the fused engines run patched models only")
+    if getattr(args, "requests", None) is None and (getattr(args, "no_engine", False) or not (args.compile or args.engine)):
+        raise SystemExit(f"{flags} need a fused engine (--compile or --engine, without --no_engine, or --requests): the module "
+                         "path's sampler knows temperature and top_k only")
+    return c
+
+
 def _mean_logprob_line(lps) -> str:
     return f"    mean logprob {sum(lps) / max(1, len(lps)):.4f} over {len(lps)} tokens (model distribution, temperature 1)"
 
@@ -710,6 +745,14 @@ def run_batched(args, model: Transformer, thresholds, prompts: torch.Tensor, tok
         eng.set_logit_processors(True)
         for b in range(B):
             eng.set_slot_processors(b, prompts[b].tolist(), **proc)
+    samp = check_sampling_args(args)
+    if samp:  # every draw under the flags: the first token of each sequence comes from the sampling launch too (sample_first)
+        if eng is None:
+            raise SystemExit("--top_p / --min_p: the batched engine cannot run this model, and the module path's sampler knows "
+                             "temperature and top_k only")
+        eng.set_sampling_params(True)
+        for b in range(B):
+            eng.set_slot_sampling(b, args.temperature, args.top_k, **samp)
     tps, seqs, lps, tops = [], [], [], []
     for i in range(-1 if args.compile else 0, args.num_samples):
         torch.cuda.synchronize()
@@ -717,7 +760,9 @@ def run_batched(args, model: Transformer, thresholds, prompts: torch.Tensor, tok
         seq = torch.empty(B, T + n_new, dtype=torch.int64, device=dev)
         seq[:, :T] = prompts
         logits = model(prompts.long(), torch.arange(0, T, device=dev))  # [B, T, V], dense (the ops' prefill path)
-        first = sample_batch(logits[:, -1], args.temperature, args.top_k)
+        if samp:
+            eng.manual_seed(1234 + max(i, 0))
+        first = eng.sample_first(logits[:, -1]).long() if samp else sample_batch(logits[:, -1], args.temperature, args.top_k)
         seq[:, T] = first
         if n_new > 1:
             if eng is not None:
@@ -808,7 +853,7 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer) -> Dict:
     eng = SlotDecodeEngine(model, thresholds, B)
     batcher = ContinuousBatcher(eng, sync_every=args.sync_every, temperature=args.temperature, top_k=args.top_k, seed=1234,
                                 use_graph=bool(args.compile), prefixes=prefixes, logprobs=getattr(args, "logprobs", None),
-                                **check_processor_args(args))
+                                **check_processor_args(args), **check_sampling_args(args))
     try:
         for name, toks in prefixes.items():  # once, before the warm-up run
             eng.register_prefix(name, toks)
@@ -855,6 +900,7 @@ def main(args) -> Dict:
     batch = check_batched_args(args)
     n_lp = check_logprobs_args(args)
     proc = check_processor_args(args)
+    samp = check_sampling_args(args)
     if getattr(args, "prefixes", None) is not None and getattr(args, "requests", None) is None:
         raise SystemExit("--prefixes names shared prefixes of continuous batching: it needs --requests")
     if getattr(args, "requests", None) is not None:
@@ -941,6 +987,9 @@ def main(args) -> Dict:
         raise SystemExit("--logprobs: the fused engine cannot run this model, and the module path returns token ids only")
     if proc and not use_engine:
         raise SystemExit("logit processors: the fused engine cannot run this model, and the module path samples from the raw logits")
+    if samp and not use_engine:
+        raise SystemExit("--top_p / --min_p: the fused engine cannot run this model, and the module path's sampler knows temperature "
+                         "and top_k only")
     # --compile captures the prompt pass as well (one hipGraph per prompt length; the reference compiles `prefill` only under
     # --compile_prefill, generate.py:423-425 — its Inductor compile takes minutes, a capture here takes milliseconds, and the
     # eager pass is ~400 launches = nine decode steps' worth for a 6-token prompt).  The prefill stays DENSE
@@ -972,7 +1021,7 @@ def main(args) -> Dict:
                 if decoder.model._lp is None:
                     decoder.model.set_logprobs(n_lp)
             y = generate(model, prompt, args.max_new_tokens, decoder, temperature=args.temperature, top_k=args.top_k,
-                         prefill=prefill, processors=proc or None)
+                         prefill=prefill, processors=proc or None, sampling=samp or None)
         torch.cuda.synchronize()
         t = time.perf_counter() - t0
         if i == -1:
@@ -1072,6 +1121,11 @@ def build_parser() -> argparse.ArgumentParser:
                    "token generated so far (0: off)")
     p.add_argument("--frequency_penalty", type=float, default=None, help="logit processor: subtracted from a token's logit once per "
                    "time it was generated so far (0: off)")
+    p.add_argument("--top_p", type=float, default=None, help="nucleus sampling (engine paths only, like --logprobs): after temperature "
+                   "and top_k, keep the most likely tokens until their share of the kept mass reaches this (> 0; 1: off).  With "
+                   "--requests: the default of requests that set none")
+    p.add_argument("--min_p", type=float, default=None, help="min-p sampling: after top_p, keep the tokens at least this likely "
+                   "relative to the most likely one (in [0, 1); 0: off)")
     p.add_argument("--sync_every", type=int, default=8, help="with --requests: steps per burst between two looks at the slot state")
     return p
 

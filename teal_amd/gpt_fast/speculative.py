@@ -106,6 +106,9 @@ class SpeculativeDecoder:
         V = verify.model.config.vocab_size
         if draft.cfg.vocab_size != V or draft.dtype != verify.model.output.weight.dtype:
             raise ValueError("speculative decoding: the draft and the target must share the vocabulary and the 16-bit dtype")
+        if draft.sampling_params is not None:
+            raise ValueError("speculative decoding: the draft engine has per-request sampling on (set_sampling_params(False) first)")
+        draft.speculating = True  # per-request sampling stays off on this engine (DecodeEngine._feature_refusal) until release()
         self.draft, self.verify, self.k, self.fill_in, self.graph = draft, verify, int(k), bool(fill_in), bool(graph)
         self.temperature, self.top_k = float(temperature), int(top_k or 0)
         self.L = draft.L
@@ -122,6 +125,12 @@ class SpeculativeDecoder:
         self.hist = torch.zeros(MAX_T, **i32)
         nb = int(self.L.teal_spec_accept_scratch_bytes(V, self.k))
         self.scratch = torch.zeros((nb + 3) // 4, device=dev, dtype=torch.float32)
+        self._graph = None
+
+    def release(self):
+        """the decoder lets its draft engine go: the engine may switch per-request sampling on again.  The decoder must not run
+        another round afterwards."""
+        self.draft.speculating = False
         self._graph = None
 
     def begin(self, first_token: torch.Tensor, pos: int):
