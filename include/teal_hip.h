@@ -593,6 +593,60 @@ int teal_sample_rows(const void* logits, size_t logits_stride, int vocab, int dt
                      int32_t* tokens, int32_t* pos, int32_t* history, int history_len, int32_t* kept_out, const int32_t* active,
                      int slot0, void* stream);
 
+/* ---- per-request stop conditions of continuous batching, teal_amd/csrc/teal_stop.hip ------------------------------------------
+ * The retire launch with stop ids, stop sequences, a minimum length and a finish reason.  It takes the place of the plain retire
+ * launch after a step's samplers (and after an admission's first draw) while an engine has the feature on: one launch for one.
+ * slot_state, tokens, pos, B, slot_mask, max_seq and count_step mean what they mean for the plain retire launch; the slot-state
+ * layout is untouched.
+ * history: int32 [B][history_stride]; entry c of row b is the token of draw c of the request now in slot b — the samplers write it
+ * before this launch, and a row restarts at 0 on admission.  stops: int32 [8][TEAL_STOP_WORDS], row b for slot b:
+ *   TEAL_STOP_MIN      min_new_tokens: no stop id, EOS id or stop sequence fires while fewer tokens than this are produced
+ *                      (<= 1: always armed)
+ *   TEAL_STOP_NIDS     stop ids in use, 0..16 (device data: a value above 16 is read as 16, one below 0 as 0)
+ *   TEAL_STOP_NSEQ     stop sequences in use, 0..8 (above 8 is read as 8, below 0 as 0)
+ *   TEAL_STOP_REASON   out: TEAL_FINISH_* — why the slot stopped.  The host writes TEAL_FINISH_RUNNING at admission
+ *   TEAL_STOP_MATCH    out: the token id for STOP_TOKEN, the sequence's index for STOP_SEQUENCE, -1 otherwise
+ *   words 5..7         reserved, never written
+ *   TEAL_STOP_IDS      + i, i < 16: the stop ids
+ *   TEAL_STOP_SEQLEN   + q, q < 8: the length of sequence q, 1..8 (any other value: the sequence never matches)
+ *   TEAL_STOP_SEQ      + 8 q + j: token j of sequence q
+ * The rule, for every slot b < B that is active and in slot_mask, with n = PRODUCED[b] before the launch, t = tokens[b], p = pos[b]:
+ *   BUDGET[b] -= 1;  PRODUCED[b] = n + 1
+ *   armed      = n + 1 >= MIN
+ *   hit_id     = armed and ((EOS[b] >= 0 and t == EOS[b]) or t == IDS[i] for some i < NIDS)
+ *   hit_seq q  = armed and q < NSEQ and len = SEQLEN[q] in 1..8 and len <= n + 1 and SEQ[q][len-1] == t
+ *                and SEQ[q][j] == history[b][n - len + 1 + j] for every j < len - 1
+ *   the slot stops when hit_id, some hit_seq, BUDGET <= 0 or p >= max_seq holds; the reason is the first of STOP_TOKEN,
+ *   STOP_SEQUENCE (the lowest q), LENGTH, CACHE that holds.  On a stop FINISH[b] = STEP, REASON and MATCH are written, the slot's
+ *   bit is cleared and pos[b] is pulled back to max_seq - 1 if it passed it.  count_step != 0: STEP += 1.
+ * A sequence is matched against tokens this request generated only: len <= n + 1 keeps every history index at 0 or above, and the
+ * prompt is never looked at.  A slot that is inactive or outside slot_mask changes nothing: no state word, no word of its stops
+ * row, no position.  With a slot's MIN, NIDS and NSEQ all 0, slot_state and pos leave bit-identical to the plain retire launch's.
+ * The caller's contract: n < history_stride for every slot served (the engines' rows hold max_seq + 1 entries); a history entry
+ * at or past history_stride is never read and counts as a mismatch.  A matched sequence of 8 tokens ends at entry n and starts at
+ * n - 7, hence history_stride >= 8.
+ * One workgroup, no atomics, no workspace; replays are bit-identical.
+ * TEAL_ERR_ARG: a null pointer, B outside 1..8, max_seq < 1, history_stride < 8; every check comes before any HIP call. */
+#define TEAL_STOP_MIN 0
+#define TEAL_STOP_NIDS 1
+#define TEAL_STOP_NSEQ 2
+#define TEAL_STOP_REASON 3
+#define TEAL_STOP_MATCH 4
+#define TEAL_STOP_IDS 8
+#define TEAL_STOP_SEQLEN 24
+#define TEAL_STOP_SEQ 32
+#define TEAL_STOP_WORDS 96
+#define TEAL_STOP_MAX_IDS 16
+#define TEAL_STOP_MAX_SEQS 8
+#define TEAL_STOP_MAX_SEQ_LEN 8
+#define TEAL_FINISH_RUNNING 0
+#define TEAL_FINISH_STOP_TOKEN 1
+#define TEAL_FINISH_STOP_SEQUENCE 2
+#define TEAL_FINISH_LENGTH 3
+#define TEAL_FINISH_CACHE 4
+int teal_batched_retire_stops(int32_t* slot_state, const int32_t* tokens, int32_t* pos, const int32_t* history, int history_stride,
+                              int32_t* stops, int B, int slot_mask, int max_seq, int count_step, void* stream);
+
 /* ---- shared prompt prefixes of continuous batching, teal_amd/csrc/teal_prefix.hip ------------------------------------
  * A prefix is a token sequence whose K / V rows (every layer) are computed once and kept in a device store; a request that names
  * it is admitted by copying those rows into its slot's caches and running a prompt pass over its own tokens only. */

@@ -26,6 +26,7 @@ from .. import _lib, runtime
 from ..kernels.sparse_gemv import BATCH_MAX, batched_segs
 from . import logit_processors as PR
 from . import sampling as SM
+from . import stopping as ST
 from .engine_features import SamplerFeatures, _SlotCaches, dense_16bit_refusal, relayout
 from .model import Transformer
 from .prefill import IN_NORM, IN_SILU_MUL, IN_XT, MAX_T, PrefillEngine, PrefillIn
@@ -387,7 +388,11 @@ class SlotDecodeEngine(BatchedDecodeEngine):
     """BatchedDecodeEngine whose B slots are switched on and off on the device (continuous batching).  One hipGraph replay is the
     forward pass through the `_slots` launches (an inactive slot adds nothing to the union and writes no cache row), B
     slot-predicated samplers and teal_batched_retire, which counts each active slot's token and switches the slot off on its EOS
-    id, its budget or the cache end.  `admit` puts one request into a free slot between replays."""
+    id, its budget or the cache end.  `admit` puts one request into a free slot between replays.  With stop conditions on
+    (set_stop_conditions) teal_batched_retire_stops takes the retire launch's place: stop ids, stop sequences, a minimum length
+    and a finish reason per request (stopping.py)."""
+
+    _stops: Optional[ST.StopConditions] = None   # set_stop_conditions
 
     def __init__(self, model: Transformer, thresholds: List[Dict[str, float]], batch: int):
         super().__init__(model, thresholds, batch)
@@ -443,6 +448,9 @@ class SlotDecodeEngine(BatchedDecodeEngine):
             _lib.check(rc, "teal_sample_topk_slot")
 
     def _retire(self, mask: int, count_step: bool, st):
+        if self._stops is not None:  # the same place in the step, one launch for one
+            self._stops.launch(self._active, self.tok_buf, self.pos_buf, self.history, self.B, mask, self.max_seq, count_step, st=st)
+            return
         rc = self.L.teal_batched_retire(self._active, self.tok_buf.data_ptr(), self.pos_buf.data_ptr(), self.B, mask, self.max_seq,
                                         int(count_step), st)
         if rc != 0:
@@ -465,7 +473,37 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         self._retire((1 << self.B) - 1, True, st)
 
     def _loop_state(self):
-        return super()._loop_state() + [self.slot_state]  # the warm-up step retires too
+        # the warm-up step retires too (and, with stop conditions on, writes a stopped slot's REASON and MATCH)
+        return super()._loop_state() + [self.slot_state] + (list(self._stops.loop_tensors()) if self._stops is not None else [])
+
+    def _feature_key(self):
+        return super()._feature_key() + (("stops",) if self._stops is not None else ())
+
+    # ---- stop conditions ---------------------------------------------------------------------------------------------------
+    def set_stop_conditions(self, on: bool):
+        """off (the default): every step and every admission issues exactly the launches it issues without this feature.  on:
+        teal_batched_retire_stops takes teal_batched_retire's place in the step and in admit's first draw — a slot also ends on
+        its request's stop ids and stop sequences, none of them (nor its EOS id) before its min_new_tokens, and read_finish tells
+        why it ended.  Allowed on an idle engine only (a running slot's row would be empty); drops the captured graphs."""
+        if int(self.slot_state[SLOT_ACTIVE].item()) != 0:
+            raise RuntimeError("set_stop_conditions needs an idle engine: a slot is active")
+        self._stops = ST.StopConditions(self.B, self.cfg.vocab_size, self.history.device) if on else None
+        self._graph = None
+
+    def _stop_conditions(self) -> ST.StopConditions:
+        if self._stops is None:
+            raise RuntimeError("stop conditions are off (set_stop_conditions)")
+        return self._stops
+
+    # the stop table int32 [8][TEAL_STOP_WORDS] (None while the feature is off)
+    stop_table = property(lambda self: None if self._stops is None else self._stops.table)
+
+    def read_finish(self, slot: int):
+        """(reason, match) of the request that last stopped in `slot`: "stop_token" (match: the token id), "stop_sequence" (match:
+        the sequence's index), "length" or "cache" (match: -1); (None, -1) while it runs"""
+        if not 0 <= int(slot) < self.B:
+            raise ValueError(f"slot {slot} outside 0..{self.B - 1}")
+        return self._stop_conditions().read()[int(slot)]
 
     # ---- admission ---------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -572,7 +610,8 @@ class SlotDecodeEngine(BatchedDecodeEngine):
     @torch.no_grad()
     def admit(self, slot: int, tokens, budget: int, eos_id: Optional[int], seed: int, temperature: float = 0.8,
               top_k: Optional[int] = 200, prefix: Optional[str] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-              frequency_penalty: float = 0.0, logit_bias: Optional[Dict] = None, top_p: float = 1.0, min_p: float = 0.0):
+              frequency_penalty: float = 0.0, logit_bias: Optional[Dict] = None, top_p: float = 1.0, min_p: float = 0.0,
+              stop_token_ids=(), stop_sequences=(), min_new_tokens: int = 0):
         """Request -> slot `slot` (free): the dense prompt pass into that slot's caches, the first token drawn from the last row's
         logits (draw 0 of the stream `seed`), the slot's token, position, history, rng state, budget and EOS set on the device and
         its bit set.  A request whose first token ends it (budget 1, EOS) is switched off again by the same retire rule.
@@ -583,7 +622,10 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         included, passes through them).
         top_p / min_p: nucleus and min-p sampling of this request (they need set_sampling_params(True)).  With per-request sampling
         on, `temperature`, `top_k`, `top_p` and `min_p` are written into the slot's parameter row and hold for every draw of the
-        request; off, `temperature` and `top_k` are those of this first draw only (run_steps has its own)."""
+        request; off, `temperature` and `top_k` are those of this first draw only (run_steps has its own).
+        stop_token_ids / stop_sequences / min_new_tokens: the request's stop conditions (they need set_stop_conditions(True)): up
+        to 16 ids, up to 8 sequences of up to 8 token ids, matched against the tokens it generates — never its prompt or prefix;
+        neither they nor `eos_id` end it before min_new_tokens tokens.  The stopping tokens stay in its output."""
         s, B = int(slot), self.B
         prompt = torch.as_tensor(tokens, dtype=torch.int32).view(-1).to(self.logits.device)
         T = int(prompt.numel())
@@ -601,10 +643,15 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         controls = PR.check_controls(self.cfg.vocab_size, repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
         if self._proc is None and not PR.is_identity(controls):
             raise RuntimeError("logit processors are off (set_logit_processors)")
+        stops = ST.check_stops(self.cfg.vocab_size, stop_token_ids, stop_sequences, min_new_tokens)
+        if self._stops is None and not ST.is_default(stops):
+            raise RuntimeError("stop conditions are off (set_stop_conditions)")
         if self._samp is not None:  # (every admission: the slot's last request left its settings)
             self._samp.set_row(s, temperature, top_k, top_p, min_p)
         elif SM.check_sampling(top_p=top_p, min_p=min_p)["top_p"] < 1.0 or min_p > 0.0:
             raise RuntimeError("per-request sampling is off (set_sampling_params)")
+        if self._stops is not None:  # (every admission: the slot's last request left its row, and its reason)
+            self._stops.set_row(s, **stops)
         if self._proc is not None:  # (every admission: the slot's last request left its counts and its parameters)
             self._proc.set_row(s, (pf.tokens if pf is not None else []) + prompt.tolist(), **controls)
         logits = self._prompt_pass(s, prompt) if pf is None else self._suffix_pass(s, pf, prompt)

@@ -15,6 +15,10 @@ Shared prefixes: a request may name a prefix — a token sequence registered wit
 store.  Its own tokens are then the suffix: it is served as prompt = prefix + suffix, but its admission copies the prefix's rows
 into the slot and runs the prompt pass over the suffix alone.  Prefixes are named, never detected: what a request computes does
 not depend on what happened to be cached when it was admitted.
+
+Stop conditions: a request may carry stop token ids, stop sequences of token ids and a minimum length (stopping.py).  They are
+matched on the device inside the step, so a request ends on the very step its stop appears whatever sync_every is, and the result
+says why each request ended ("finish_reason") and what matched ("stop_match").
 """
 from __future__ import annotations
 
@@ -27,6 +31,7 @@ from typing import Dict, List, Optional, Sequence
 
 from .batched import SLOT_ACTIVE, SLOT_FINISH, SLOT_PRODUCED, SLOT_STEP
 from .logit_processors import fp32
+from .stopping import MAX_IDS, MAX_SEQ_LEN, MAX_SEQS
 
 REFILL = ("free", "all")
 SAMPLING = ("temperature", "top_k", "top_p", "min_p")
@@ -52,6 +57,26 @@ class Request:
     top_k: Optional[int] = None
     top_p: Optional[float] = None
     min_p: Optional[float] = None
+    # stop conditions (None: the batcher's default; stop sequences have none).  The request ends right after one of the ids, or after
+    # the last token of one of the sequences (up to 8 of up to 8 token ids, matched against what it generated only); nothing but
+    # its budget and the cache end stops it before min_new_tokens tokens.  The stopping tokens stay in its output
+    stop_token_ids: Optional[List[int]] = None
+    stop_sequences: Optional[List[List[int]]] = None
+    min_new_tokens: Optional[int] = None
+
+    def stops(self, defaults: Optional[Dict] = None) -> Dict:
+        """the stop conditions that differ from "none" — the keyword arguments of the engine's admit; {}: the request asks for none"""
+        d = defaults or {}
+        ids = d.get("stop_token_ids", ()) if self.stop_token_ids is None else self.stop_token_ids
+        n = d.get("min_new_tokens", 0) if self.min_new_tokens is None else self.min_new_tokens
+        out = {}
+        if ids:
+            out["stop_token_ids"] = [int(t) for t in ids]
+        if self.stop_sequences:
+            out["stop_sequences"] = [[int(t) for t in q] for q in self.stop_sequences]
+        if n:
+            out["min_new_tokens"] = int(n)
+        return out
 
     def sampling(self, defaults: Dict) -> Dict:
         """the request's four sampling settings, `defaults` (a dict of the four) where it sets none of its own"""
@@ -131,6 +156,47 @@ def parse_sampling(d: dict, where: str) -> Dict:
     return out
 
 
+def parse_stops(d: dict, where: str, tokenizer=None) -> Dict:
+    """the stop-condition fields of one request object, validated; only those present.  "stop": strings, each encoded without a BOS
+    into one more stop sequence (needs a tokenizer) — the match stays on token ids: a text the model spells with other tokens than
+    the tokenizer gave for the string alone is not caught."""
+    def ids(v):
+        return isinstance(v, list) and all(isinstance(t, int) and not isinstance(t, bool) and t >= 0 for t in v)
+    out = {}
+    if "stop_token_ids" in d:
+        v = d["stop_token_ids"]
+        if not ids(v) or len(set(v)) > MAX_IDS:
+            raise ValueError(f"{where}: \"stop_token_ids\" must be a list of at most {MAX_IDS} token ids")
+        out["stop_token_ids"] = [int(t) for t in v]
+    seqs = []
+    if "stop_sequences" in d:
+        v = d["stop_sequences"]
+        if not isinstance(v, list) or not all(ids(q) and 1 <= len(q) <= MAX_SEQ_LEN for q in v):
+            raise ValueError(f"{where}: \"stop_sequences\" must be a list of lists of 1..{MAX_SEQ_LEN} token ids")
+        seqs += [[int(t) for t in q] for q in v]
+    if "stop" in d:
+        v = d["stop"]
+        if not isinstance(v, list) or not all(isinstance(x, str) and x for x in v):
+            raise ValueError(f"{where}: \"stop\" must be a list of non-empty strings")
+        if tokenizer is None:
+            raise ValueError(f"{where}: \"stop\" strings need a tokenizer (a checkpoint), not --synthetic: give \"stop_sequences\" of token ids")
+        for x in v:
+            q = [int(t) for t in tokenizer.encode(x)]
+            if not 1 <= len(q) <= MAX_SEQ_LEN:
+                raise ValueError(f"{where}: the \"stop\" string {x!r} encodes to {len(q)} tokens: a stop sequence has 1..{MAX_SEQ_LEN}")
+            seqs.append(q)
+    if len(seqs) > MAX_SEQS:
+        raise ValueError(f"{where}: {len(seqs)} stop sequences (\"stop_sequences\" and \"stop\" together): at most {MAX_SEQS}")
+    if seqs or "stop_sequences" in d or "stop" in d:
+        out["stop_sequences"] = seqs
+    if "min_new_tokens" in d:
+        v = d["min_new_tokens"]
+        if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v < 2 ** 31:
+            raise ValueError(f"{where}: \"min_new_tokens\" must be a non-negative integer")
+        out["min_new_tokens"] = int(v)
+    return out
+
+
 def parse_prefixes(lines: Sequence[str], tokenizer=None) -> Dict[str, List[int]]:
     """JSON Lines, one shared prefix per line: {"id": "sys", "tokens": [...]} or {"id": "sys", "prompt": "..."} (needs a tokenizer;
     BOS prepended as for prompts).  Blank lines are skipped; an empty file is an empty mapping."""
@@ -186,7 +252,10 @@ def parse_requests(lines: Sequence[str], default_max_new_tokens: int, tokenizer=
     "prefix": an id of `prefixes`; its tokens / prompt are then the suffix, and a prompt is encoded WITHOUT a BOS (the prefix
     holds it).  A line may carry its own logit processors: "repetition_penalty" (> 0), "presence_penalty", "frequency_penalty"
     and "logit_bias" ({"<id>": value}), its own sampling settings: "temperature" (>= 0), "top_k" (0: off), "top_p" (> 0; 1: off) and
-    "min_p" (in [0, 1); 0: off), and its own "seed"."""
+    "min_p" (in [0, 1); 0: off), and its own "seed".  A line may carry its own stop conditions: "stop_token_ids" (at most 16),
+    "stop_sequences" (at most 8 lists of 1..8 token ids), "min_new_tokens" and, with a tokenizer, "stop": strings, each encoded
+    WITHOUT a BOS into one more stop sequence.  The match is on token ids against the tokens the request generates: a string the
+    model spells with other tokens (another split, a leading-space variant) is not caught."""
     out = []
     for i, line in enumerate(lines):
         if not line.strip():
@@ -214,7 +283,7 @@ def parse_requests(lines: Sequence[str], default_max_new_tokens: int, tokenizer=
         if not isinstance(n, int) or n < 1:
             raise ValueError(f"request line {i + 1}: \"max_new_tokens\" must be a positive integer")
         out.append(Request([int(t) for t in toks], n, eos_id, prefix=pid, **parse_controls(d, f"request line {i + 1}"),
-                           **parse_sampling(d, f"request line {i + 1}")))
+                           **parse_sampling(d, f"request line {i + 1}"), **parse_stops(d, f"request line {i + 1}", tokenizer)))
     if not out:
         raise ValueError("no requests")
     return out
@@ -258,12 +327,19 @@ class ContinuousBatcher:
     Sampling: `temperature`, `top_k`, `top_p` and `min_p` here are the defaults of requests that set none of their own.  When a
     default or some request differs from (temperature, top_k, 1, 0) the engine also offers set_sampling_params(True), called once
     before the first admission, and admit(..., top_p=, min_p=); every request is then admitted with its own four settings, which
-    hold for all of its draws, and run_steps' temperature and top_k no longer matter.  Otherwise every call is today's."""
+    hold for all of its draws, and run_steps' temperature and top_k no longer matter.  Otherwise every call is today's.
+    Stop conditions: `stop_token_ids` and `min_new_tokens` here are the defaults of requests that set none of their own.  When a
+    default or some request asks for a stop id, a stop sequence or a minimum, or `finish_reason` is set, the engine also offers
+    set_stop_conditions(True), called once before the first admission, admit(..., stop_token_ids=, stop_sequences=,
+    min_new_tokens=) — only requests that ask for one are admitted with those keywords — and read_finish(slot) -> (reason, match);
+    the result gains "finish_reason" ("stop_token" / "stop_sequence" / "length" / "cache" per request, in input order) and
+    "stop_match" (the token id, the sequence's index, or -1).  "tokens" stays every token drawn, the stopping ones included."""
 
     def __init__(self, engine, sync_every: int = 8, refill: str = "free", temperature: float = 0.8, top_k: Optional[int] = 200,
                  seed: int = 1234, use_graph: bool = True, prefixes: Optional[Dict[str, List[int]]] = None,
                  logprobs: Optional[int] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-                 frequency_penalty: float = 0.0, top_p: float = 1.0, min_p: float = 0.0):
+                 frequency_penalty: float = 0.0, top_p: float = 1.0, min_p: float = 0.0, stop_token_ids=(), min_new_tokens: int = 0,
+                 finish_reason: bool = False):
         if refill not in REFILL:
             raise ValueError(f"refill must be one of {REFILL}")
         if int(sync_every) < 1:
@@ -279,6 +355,8 @@ class ContinuousBatcher:
         self._processors_set = False
         parse_sampling({"top_p": top_p, "min_p": min_p}, "ContinuousBatcher")
         self.top_p, self.min_p, self._sampling_set = float(top_p), float(min_p), False
+        self.stop_defaults = parse_stops({"stop_token_ids": list(stop_token_ids or ()), "min_new_tokens": min_new_tokens}, "ContinuousBatcher")
+        self.finish_reason, self._stops_set = bool(finish_reason), False
 
     def _clock(self):
         try:
@@ -320,6 +398,12 @@ class ContinuousBatcher:
         if any(s != plain for s in sampling) and not self._sampling_set:  # once: it drops the engine's captured step
             eng.set_sampling_params(True)
             self._sampling_set = True
+        stops = [r.stops(self.stop_defaults) if hasattr(r, "stops") else {} for r in requests]
+        if (self.finish_reason or any(stops)) and not self._stops_set:  # once: it drops the engine's captured step
+            eng.set_stop_conditions(True)
+            self._stops_set = True
+        reasons: List[Optional[str]] = [None] * len(requests)
+        matches: List[int] = [-1] * len(requests)
         pending = deque(range(len(requests)))
         lps: List[Optional[List[float]]] = [None] * len(requests)
         tops: List[Optional[List]] = [None] * len(requests)
@@ -347,6 +431,8 @@ class ContinuousBatcher:
                     if self._sampling_set:
                         T, k = sampling[r]["temperature"], sampling[r]["top_k"]
                         kw.update(top_p=sampling[r]["top_p"], min_p=sampling[r]["min_p"])
+                    if self._stops_set:
+                        kw.update(stops[r])
                     eng.admit(s, q.tokens, q.max_new_tokens, q.eos_id, self.seed + r if q.seed is None else q.seed, T, k, **kw)
                     prefix_admissions += 1 if plen[r] else 0
                     prefix_rows += plen[r]
@@ -365,6 +451,8 @@ class ContinuousBatcher:
                     lp, ids, tlp = eng.read_logprobs(s, state[SLOT_PRODUCED + s])
                     lps[r] = [float(v) for v in lp]
                     tops[r] = [[(int(i), float(v)) for i, v in zip(ii, vv)] for ii, vv in zip(ids, tlp)]
+                if self._stops_set:
+                    reasons[r], matches[r] = eng.read_finish(s)
                 slot_steps += state[SLOT_FINISH + s] - admitted_at[s]
                 slot_req[s] = None
         c1 = self._clock()
@@ -379,6 +467,8 @@ class ContinuousBatcher:
             extra["logprobs"] = lps
             if self.logprobs > 0:
                 extra["top_logprobs"] = tops
+        if self._stops_set:
+            extra["finish_reason"], extra["stop_match"] = reasons, matches
         return {
             **extra,
             "tokens": out, "slots": slots_used, "steps": steps, "admissions": admissions, "wall_s": wall,

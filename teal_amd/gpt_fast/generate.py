@@ -711,6 +711,35 @@ def check_sampling_args(args) -> Dict:
     return c
 
 
+def check_stop_args(args) -> Dict:
+    """--stop_token_ids / --min_new_tokens / --finish_reason: the batcher's keywords that are switched on ({}: none); every refusal
+    is raised here, before anything is loaded.  Stop conditions live in the retire launch of continuous batching — no other
+    engine retires — so the flags are valid with --requests only, where the first two are the defaults of requests that carry none
+    of their own."""
+    out = {}
+    raw = getattr(args, "stop_token_ids", None)
+    if raw is not None:
+        try:
+            ids = [int(x) for x in str(raw).split(",") if x.strip()]
+        except ValueError:
+            ids = None
+        if not ids or any(t < 0 for t in ids) or len(set(ids)) > 16:
+            raise SystemExit(f"--stop_token_ids must be 1..16 token ids (>= 0) separated by commas, got {raw!r}")
+        out["stop_token_ids"] = ids
+    n = getattr(args, "min_new_tokens", None)
+    if n is not None:
+        if int(n) < 0:
+            raise SystemExit(f"--min_new_tokens must be >= 0, got {n}")
+        if int(n) > 0:
+            out["min_new_tokens"] = int(n)
+    if getattr(args, "finish_reason", False):
+        out["finish_reason"] = True
+    if out and getattr(args, "requests", None) is None:
+        raise SystemExit("--stop_token_ids / --min_new_tokens / --finish_reason need --requests: stop conditions live in the retire "
+                         "launch of continuous batching, and no other decode path retires")
+    return out
+
+
 def _mean_logprob_line(lps) -> str:
     return f"    mean logprob {sum(lps) / max(1, len(lps)):.4f} over {len(lps)} tokens (model distribution, temperature 1)"
 
@@ -844,6 +873,12 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer) -> Dict:
         max_seq = cache_rows(reqs, model.config.block_size, prefixes)
         if prefixes:  # (a prefix no request names is registered too: it needs room for a one-token suffix)
             max_seq = max(max_seq, min(max(len(t) for t in prefixes.values()) + 2, model.config.block_size))
+        from teal_amd.gpt_fast.stopping import check_stops
+        for i, r in enumerate(reqs):  # an id outside this model's vocabulary: refused before anything runs
+            try:
+                check_stops(model.config.vocab_size, **r.stops(check_stop_args(args)))
+            except ValueError as e:
+                raise ValueError(f"request {i}: {e}") from None
     except (OSError, ValueError) as e:
         raise SystemExit(f"--requests: {e}")
     model.setup_caches(max_batch_size=B, max_seq_length=max_seq)
@@ -853,7 +888,7 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer) -> Dict:
     eng = SlotDecodeEngine(model, thresholds, B)
     batcher = ContinuousBatcher(eng, sync_every=args.sync_every, temperature=args.temperature, top_k=args.top_k, seed=1234,
                                 use_graph=bool(args.compile), prefixes=prefixes, logprobs=getattr(args, "logprobs", None),
-                                **check_processor_args(args), **check_sampling_args(args))
+                                **check_processor_args(args), **check_sampling_args(args), **check_stop_args(args))
     try:
         for name, toks in prefixes.items():  # once, before the warm-up run
             eng.register_prefix(name, toks)
@@ -872,6 +907,9 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer) -> Dict:
         print(f"[request {i}, slot {res['slots'][i]}] {text}")
         if "logprobs" in res and tokenizer is not None:
             print(_mean_logprob_line(res["logprobs"][i]))
+        if "finish_reason" in res and tokenizer is not None:
+            what = {"stop_token": f" (token {res['stop_match'][i]})", "stop_sequence": f" (stop sequence {res['stop_match'][i]})"}
+            print(f"    finish reason: {res['finish_reason'][i]}{what.get(res['finish_reason'][i], '')}")
     tps = res["useful_tokens_per_sec"]
     print(f"{len(reqs)} requests, {res['useful_tokens']} useful tokens in {res['wall_s']:.2f} s: {tps:.2f} tokens/sec; "
           f"{res['steps']} steps, {res['mean_active_slots']:.2f} active slots of {B} on average, "
@@ -885,7 +923,7 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer) -> Dict:
             "admission_share": res["admission_share"], "mean_active_slots": res["mean_active_slots"], "union_kept": res["union_kept"],
             "sync_every": res["sync_every"], "prefix_admissions": res["prefix_admissions"],
             "prefix_rows_reused": res["prefix_rows_reused"], "prefix_paths": res["prefix_paths"],
-            **{k: res[k] for k in ("logprobs", "top_logprobs") if k in res}}
+            **{k: res[k] for k in ("logprobs", "top_logprobs", "finish_reason", "stop_match") if k in res}}
 
 
 def sample_batch(logits: torch.Tensor, temperature: float, top_k: Optional[int]) -> torch.Tensor:
@@ -901,6 +939,7 @@ def main(args) -> Dict:
     n_lp = check_logprobs_args(args)
     proc = check_processor_args(args)
     samp = check_sampling_args(args)
+    check_stop_args(args)
     if getattr(args, "prefixes", None) is not None and getattr(args, "requests", None) is None:
         raise SystemExit("--prefixes names shared prefixes of continuous batching: it needs --requests")
     if getattr(args, "requests", None) is not None:
@@ -1126,6 +1165,14 @@ def build_parser() -> argparse.ArgumentParser:
                    "--requests: the default of requests that set none")
     p.add_argument("--min_p", type=float, default=None, help="min-p sampling: after top_p, keep the tokens at least this likely "
                    "relative to the most likely one (in [0, 1); 0: off)")
+    p.add_argument("--stop_token_ids", type=str, default=None, help="with --requests: token ids a,b,c (at most 16) — a request also "
+                   "ends right after any of them, like --eos_id.  The default of requests that set no \"stop_token_ids\"; a request "
+                   "line may also carry \"stop_sequences\" (token id lists) and, with a tokenizer, \"stop\" strings (matched as the "
+                   "token ids the tokenizer gives them: another spelling of the same text is not caught)")
+    p.add_argument("--min_new_tokens", type=int, default=None, help="with --requests: no stop id, EOS id or stop sequence ends a request "
+                   "before it produced this many tokens (its budget still does).  The default of requests that set none")
+    p.add_argument("--finish_reason", action="store_true", help="with --requests: report why each request ended (stop_token / "
+                   "stop_sequence / length / cache) even when no request carries a stop condition")
     p.add_argument("--sync_every", type=int, default=8, help="with --requests: steps per burst between two looks at the slot state")
     return p
 
