@@ -15,66 +15,30 @@ timed window starts from the same token, positions and draw counters.
 
 --legs 1,2 --settings off runs on a tree without the feature too (the parent commit's step, for the off leg's comparison).
 """
-import argparse
-import json
-import os
-import sys
-
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from teal_amd import _lib, runtime  # noqa: E402
-from teal_amd.gpt_fast import generate as G  # noqa: E402
-from teal_amd.gpt_fast.engine import DecodeEngine  # noqa: E402
+from _feature_bench import FeatureBench, capture, replay_ms  # (puts the repository root on sys.path)
+from teal_amd import _lib, runtime
 
 T, TOP_K = 0.8, 200
 SETTINGS = {"defaults": (T, TOP_K, 1.0, 0.0), "nucleus": (T, TOP_K, 0.9, 0.02)}
 
 
-def replay_ms(g, steps, reset):
-    """ms per replay over `steps` replays from the state reset() restores, after 3 warm replays from the same state"""
-    reset()
-    for _ in range(3):
-        g.replay()
-    reset()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(steps):
-        g.replay()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / steps
-
-
-def capture(fn):
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        fn()
-    torch.cuda.current_stream().wait_stream(s)
-    g = torch.cuda.CUDAGraph()
-    with runtime.graph_capture(g):
-        fn()
-    return g
-
-
-def leg_engine(name, eng, rows, settings, steps, graph_of, state, emit):
+def leg_engine(bench, name, eng, rows, graph_of, state):
     saved = [t.clone() for t in state]
 
     def reset():
         for t, v in zip(state, saved):
             t.copy_(v)
 
-    for rnd in (1, 2):
-        for key in settings:
-            if key != "off" or hasattr(eng, "set_sampling_params"):
-                eng.set_sampling_params(key != "off")
-            if key != "off":
-                for r in range(rows):
-                    eng.set_slot_sampling(r, *SETTINGS[key])
-            ms = replay_ms(graph_of(), steps, reset)
-            emit({"leg": name, "sampling": key, "run": rnd, "ms_per_step": round(ms, 4)})
+    for rnd, key in bench.rounds():
+        if key != "off" or hasattr(eng, "set_sampling_params"):
+            eng.set_sampling_params(key != "off")
+        if key != "off":
+            for r in range(rows):
+                eng.set_slot_sampling(r, *SETTINGS[key])
+        ms = replay_ms(graph_of(), bench.a.steps, reset)
+        bench.emit({"leg": name, "sampling": key, "run": rnd, "ms_per_step": round(ms, 4)})
 
 
 def leg_launch(V, dt, chain, steps, emit):
@@ -125,66 +89,23 @@ def leg_launch(V, dt, chain, steps, emit):
 
 
 def main():
-    p = argparse.ArgumentParser()
-    p.add_argument("--synthetic", default="7B")
-    p.add_argument("--precision", default="fp16", choices=["fp16", "bf16"])
-    p.add_argument("--sparsity", type=float, default=0.5)
-    p.add_argument("--n_layer", type=int, default=None)
-    p.add_argument("--steps", type=int, default=200)
-    p.add_argument("--pos", type=int, default=32, help="position of the first timed step")
-    p.add_argument("--chain", type=int, default=20, help="leg 3: launches per graph")
-    p.add_argument("--legs", default="1,2,3")
-    p.add_argument("--settings", default="off,defaults,nucleus")
-    p.add_argument("--note", default="", help="a line for the head of the record (e.g. which tree this is)")
-    p.add_argument("--out", default=None, help="also append the record to this file")
-    a = p.parse_args()
-    runtime.init()
-    dev, dt = "cuda", {"fp16": torch.float16, "bf16": torch.bfloat16}[a.precision]
-    legs, settings = a.legs.split(","), a.settings.split(",")
-    lines = []
-
-    def emit(rec):
-        line = json.dumps(rec)
-        print(line, flush=True)
-        lines.append(line)
-
-    emit({"model": a.synthetic, "n_layer": a.n_layer, "precision": a.precision, "sparsity": a.sparsity, "steps": a.steps, "pos": a.pos,
-          "chain": a.chain, "device": torch.cuda.get_device_name(0), "note": a.note})
+    bench = FeatureBench("off,defaults,nucleus")
+    a, legs = bench.a, bench.legs
     if "1" in legs or "2" in legs:
-        m = G.build_synthetic_model(a.synthetic, dev, dt, n_layer=a.n_layer)
-        ths = G.apply_sparsity(m, sparsity=a.sparsity, hist_path=None, greedy_lookup=None, synthetic=True)
-        V = m.config.vocab_size
-        max_seq = a.pos + a.steps + 16
-        g = torch.Generator(device=dev).manual_seed(0)
-        prompts = [torch.randint(0, V, (a.pos - s,), generator=torch.Generator().manual_seed(s)).tolist() for s in range(8)]
+        m, ths, prompts = bench.model()
     if "1" in legs:
-        m.max_seq_length, m.max_batch_size = -1, -1
-        m.setup_caches(max_batch_size=1, max_seq_length=max_seq)
-        eng = DecodeEngine(m, ths)
-        eng.tok_buf.copy_(torch.randint(0, V, (1, 1), device=dev, generator=g))
-        eng.pos_buf.fill_(a.pos)
-        eng.rng_state.copy_(torch.tensor([1234, 0], dtype=torch.int64))
-        leg_engine("DecodeEngine", eng, 1, settings, a.steps, lambda: eng.capture_loop(T, TOP_K), [eng.tok_buf, eng.pos_buf, eng.rng_state], emit)
+        eng, state = bench.decode_engine(m, ths)
+        leg_engine(bench, "DecodeEngine", eng, 1, lambda: eng.capture_loop(T, TOP_K), state)
         del eng
     if "2" in legs:
-        from teal_amd.gpt_fast.batched import SlotDecodeEngine
-        B = 8
-        m.max_seq_length, m.max_batch_size = -1, -1
-        m.setup_caches(max_batch_size=B, max_seq_length=max_seq)
-        eng = SlotDecodeEngine(m, ths, B)
-        for s in range(B):  # prompts of pos - s tokens: the slots sit at different positions, none retires inside a window
-            eng.admit(s, prompts[s], max_seq, None, 1234 + s, T, TOP_K)
-        leg_engine("SlotDecodeEngine B=8", eng, B, settings, a.steps, lambda: eng.capture(T, TOP_K),
-                   [eng.tok_buf, eng.pos_buf, eng.rng_state, eng.slot_state], emit)
-        assert eng.read_state()[0] == (1 << B) - 1, "a slot retired inside the timed window"
+        eng, state = bench.slot_engine(m, ths, prompts)  # (admitted at admit's own defaults: T and TOP_K)
+        leg_engine(bench, "SlotDecodeEngine B=8", eng, eng.B, lambda: eng.capture(T, TOP_K), state)
+        assert eng.read_state()[0] == (1 << eng.B) - 1, "a slot retired inside the timed window"
         del eng
     if "3" in legs:
         for V in (32000, 128256):
-            leg_launch(V, dt, a.chain, a.steps, emit)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
+            leg_launch(V, bench.dt, a.chain, a.steps, bench.emit)
+    bench.close()
 
 
 if __name__ == "__main__":

@@ -19,47 +19,13 @@ every window does the same work; a sequence's eight compares are issued whether 
 --legs 1,2 --settings off runs on a library without the feature too (TEAL_LIB_PATH: the parent commit's build, for the off leg's
 comparison in alternating processes).
 """
-import argparse
-import json
-import os
-import sys
-
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from teal_amd import _lib, runtime  # noqa: E402
-from teal_amd.gpt_fast import generate as G  # noqa: E402
-from teal_amd.gpt_fast.batched import SLOT_ACTIVE, SLOT_WORDS, SlotDecodeEngine  # noqa: E402
+from _feature_bench import FeatureBench, capture, replay_ms  # (puts the repository root on sys.path)
+from teal_amd import _lib, runtime
+from teal_amd.gpt_fast.batched import SLOT_ACTIVE, SLOT_WORDS, SlotDecodeEngine
 
 T, TOP_K = 0.8, 200
-
-
-def replay_ms(g, steps, reset):
-    """ms per replay over `steps` replays from the state reset() restores, after 3 warm replays from the same state"""
-    reset()
-    for _ in range(3):
-        g.replay()
-    reset()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(steps):
-        g.replay()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / steps
-
-
-def capture(fn):
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        fn()
-    torch.cuda.current_stream().wait_stream(s)
-    g = torch.cuda.CUDAGraph()
-    with runtime.graph_capture(g):
-        fn()
-    return g
 
 
 def full_tables(unused):
@@ -68,9 +34,10 @@ def full_tables(unused):
     return dict(stop_token_ids=ids, stop_sequences=[[ids[q]] * 8 for q in range(8)])
 
 
-def leg_engine(name, m, ths, B, prompts, max_seq, settings, steps, emit):
+def leg_engine(bench, name, m, ths, B, prompts):
+    bench.caches(m, B)
     eng = SlotDecodeEngine(m, ths, B)
-    V = m.config.vocab_size
+    V, max_seq, settings, steps = m.config.vocab_size, bench.max_seq, bench.settings, bench.a.steps
 
     def window(key, stops):
         """the slots admitted afresh under `key`, then one timed window"""
@@ -95,10 +62,9 @@ def leg_engine(name, m, ths, B, prompts, max_seq, settings, steps, emit):
         window("off", {})
         drawn = set(eng.history[:, :steps + 8].flatten().tolist())
         unused = [t for t in range(V - 1, -1, -1) if t not in drawn][:16]
-    for rnd in (1, 2):
-        for key in settings:
-            ms = window(key, full_tables(unused) if key == "full" else {})
-            emit({"leg": name, "stop_conditions": key, "run": rnd, "ms_per_step": round(ms, 4)})
+    for rnd, key in bench.rounds():
+        ms = window(key, full_tables(unused) if key == "full" else {})
+        bench.emit({"leg": name, "stop_conditions": key, "run": rnd, "ms_per_step": round(ms, 4)})
     del eng
 
 
@@ -141,48 +107,16 @@ def leg_launch(chain, steps, emit):
 
 
 def main():
-    p = argparse.ArgumentParser()
-    p.add_argument("--synthetic", default="7B")
-    p.add_argument("--precision", default="fp16", choices=["fp16", "bf16"])
-    p.add_argument("--sparsity", type=float, default=0.5)
-    p.add_argument("--n_layer", type=int, default=None)
-    p.add_argument("--steps", type=int, default=200)
-    p.add_argument("--pos", type=int, default=32, help="position of the first timed step")
-    p.add_argument("--chain", type=int, default=20, help="leg 3: launches per graph")
-    p.add_argument("--legs", default="1,2,3")
-    p.add_argument("--settings", default="off,empty,full")
-    p.add_argument("--note", default="", help="a line for the head of the record (e.g. which build this is)")
-    p.add_argument("--out", default=None, help="also append the record to this file")
-    a = p.parse_args()
-    runtime.init()
-    dev, dt = "cuda", {"fp16": torch.float16, "bf16": torch.bfloat16}[a.precision]
-    legs, settings = a.legs.split(","), a.settings.split(",")
-    lines = []
-
-    def emit(rec):
-        line = json.dumps(rec)
-        print(line, flush=True)
-        lines.append(line)
-
-    emit({"model": a.synthetic, "n_layer": a.n_layer, "precision": a.precision, "sparsity": a.sparsity, "steps": a.steps, "pos": a.pos,
-          "chain": a.chain, "device": torch.cuda.get_device_name(0), "library": _lib.LIB_OVERRIDE or "in-tree", "note": a.note})
+    bench = FeatureBench("off,empty,full", note_eg="which build this is", library=_lib.LIB_OVERRIDE or "in-tree")
+    a, legs = bench.a, bench.legs
     if "1" in legs or "2" in legs:
-        m = G.build_synthetic_model(a.synthetic, dev, dt, n_layer=a.n_layer)
-        ths = G.apply_sparsity(m, sparsity=a.sparsity, hist_path=None, greedy_lookup=None, synthetic=True)
-        V = m.config.vocab_size
-        max_seq = a.pos + a.steps + 16
-        prompts = [torch.randint(0, V, (a.pos - s,), generator=torch.Generator().manual_seed(s)).tolist() for s in range(8)]
+        m, ths, prompts = bench.model()
         for leg, B in (("1", 8), ("2", 1)):
             if leg in legs:
-                m.max_seq_length, m.max_batch_size = -1, -1
-                m.setup_caches(max_batch_size=B, max_seq_length=max_seq)
-                leg_engine(f"SlotDecodeEngine B={B}", m, ths, B, prompts, max_seq, settings, a.steps, emit)
+                leg_engine(bench, f"SlotDecodeEngine B={B}", m, ths, B, prompts)
     if "3" in legs:
-        leg_launch(a.chain, a.steps, emit)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
+        leg_launch(a.chain, a.steps, bench.emit)
+    bench.close()
 
 
 if __name__ == "__main__":

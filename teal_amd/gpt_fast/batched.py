@@ -129,26 +129,42 @@ class BatchedDecodeEngine(SamplerFeatures):
         } for t in self.ths]
         self._lm_segs = batched_segs([V], [NINF])
 
-    # ---- launches ---------------------------------------------------------------------------------
+    # ---- launches: with `_active` (SlotDecodeEngine: the address of its active word) the slot-predicated entry points --------
     def _gemm(self, gin: PrefillIn, segs, lin0, lin1, Z: int, out: torch.Tensor, counts: Optional[torch.Tensor], st) -> int:
-        w0 = lin0.weight
-        rc = self.L.teal_batched_sparse_gemm(ctypes.byref(gin), ctypes.byref(segs), w0.data_ptr(), w0.stride(1), w0.shape[0],
-                                             lin1.weight.data_ptr() if lin1 is not None else None,
-                                             lin1.weight.stride(1) if lin1 is not None else 0, lin1.weight.shape[0] if lin1 is not None else 0,
-                                             out.data_ptr(), out.numel() * 4, Z, self.B, counts.data_ptr() if counts is not None else None,
-                                             self.code, ctypes.byref(self._split), st)
+        w0, w1 = lin0.weight, lin1.weight if lin1 is not None else None
+        head = (ctypes.byref(gin), ctypes.byref(segs), w0.data_ptr(), w0.stride(1), w0.shape[0], w1.data_ptr() if lin1 is not None else None,
+                w1.stride(1) if lin1 is not None else 0, w1.shape[0] if lin1 is not None else 0, out.data_ptr(), out.numel() * 4, Z, self.B)
+        tail = (counts.data_ptr() if counts is not None else None, self.code, ctypes.byref(self._split), st)
+        if self._active is None:
+            rc, what = self.L.teal_batched_sparse_gemm(*head, *tail), "teal_batched_sparse_gemm"
+        else:
+            rc, what = self.L.teal_batched_sparse_gemm_slots(*head, self._active, *tail), "teal_batched_sparse_gemm_slots"
         if rc != 0:
-            _lib.check(rc, "teal_batched_sparse_gemm")
+            _lib.check(rc, what)
         return self._split.value
 
     def _attention(self, at, A: torch.Tensor, ns: int, st):
         cfg = self.cfg
-        kc, vc = at.kv_cache.k_cache, at.kv_cache.v_cache
-        rc = self.L.teal_batched_decode_attention(A.data_ptr(), ns, self.rope.data_ptr(), self.pos_buf.data_ptr(), kc.data_ptr(), vc.data_ptr(),
-                                                  self.yt.data_ptr(), self.partials.data_ptr(), self.partials.numel() * 4, self.B, cfg.n_head,
-                                                  cfg.n_local_heads, cfg.head_dim, self.max_seq, self.code, st)
+        head = (A.data_ptr(), ns, self.rope.data_ptr(), self.pos_buf.data_ptr())
+        tail = (at.kv_cache.k_cache.data_ptr(), at.kv_cache.v_cache.data_ptr(), self.yt.data_ptr(), self.partials.data_ptr(),
+                self.partials.numel() * 4, self.B, cfg.n_head, cfg.n_local_heads, cfg.head_dim, self.max_seq, self.code, st)
+        if self._active is None:
+            rc, what = self.L.teal_batched_decode_attention(*head, *tail), "teal_batched_decode_attention"
+        else:
+            rc, what = self.L.teal_batched_decode_attention_slots(*head, self._active, *tail), "teal_batched_decode_attention_slots"
         if rc != 0:
-            _lib.check(rc, "teal_batched_decode_attention")
+            _lib.check(rc, what)
+
+    def _sample_row(self, b: int, logits: torch.Tensor, temperature, top_k, feed, st):
+        args = (logits.data_ptr(), self.cfg.vocab_size, self.code, int(top_k or 0), float(temperature), self.rng_state[b].data_ptr(),
+                self.tok_buf[b:].data_ptr(), self.pos_buf[b:].data_ptr(), self.history[b].data_ptr(), self.history.shape[1],
+                self.ws.data_ptr(), self.ws.numel() * 4)
+        if self._active is None:
+            rc, what = self.L.teal_sample_topk_ws(*args, st), "teal_sample_topk (batched)"
+        else:
+            rc, what = self.L.teal_sample_topk_slot(*args, self._active, b, st), "teal_sample_topk_slot"
+        if rc != 0:
+            _lib.check(rc, what)
 
     def _resid(self, tokens: bool, slabs: Optional[torch.Tensor], split: int, st):
         m = self.model
@@ -196,23 +212,9 @@ class BatchedDecodeEngine(SamplerFeatures):
 
     # ---- sampling and the device-resident loop ----------------------------------------------------
     def _sample(self, temperature: float, top_k: Optional[int]):
-        st, V = runtime.stream_ptr(), self.cfg.vocab_size
-        src = self.logits
-        if self._proc is not None:  # tok_buf still holds the tokens this step was fed: each sequence's latest
-            self._proc.launch(self.logits, V, self.B, self.tok_buf, True, st=st)
-            src = self._proc.adj
-        if self._samp is not None:  # one launch, every sequence under its own row of settings
-            self._samp.launch(src, V, self.B, self.rng_state, self.tok_buf, self.pos_buf, self.history, self.history.shape[1], st=st)
-        else:
-            for b in range(self.B):
-                rc = self.L.teal_sample_topk_ws(src[b].data_ptr(), V, self.code, int(top_k or 0), float(temperature),
-                                                self.rng_state[b].data_ptr(), self.tok_buf[b:].data_ptr(), self.pos_buf[b:].data_ptr(),
-                                                self.history[b].data_ptr(), self.history.shape[1], self.ws.data_ptr(),
-                                                self.ws.numel() * 4, st)
-                if rc != 0:
-                    _lib.check(rc, "teal_sample_topk (batched)")
-        if self._lp is not None:
-            self._lp.launch(self.logits, V, V, self.code, self.B, self.tok_buf, self.rng_state, st=st)
+        # tok_buf still holds the tokens this step was fed: each sequence's latest, which the processors count first
+        self._draw(self.logits, self.cfg.vocab_size, self.B, temperature, top_k, self.rng_state, self.tok_buf, self.pos_buf, self.history,
+                   True, st=runtime.stream_ptr())
 
     @torch.no_grad()
     def sample_first(self, logits_rows: torch.Tensor) -> torch.Tensor:
@@ -417,36 +419,6 @@ class SlotDecodeEngine(BatchedDecodeEngine):
     def _active(self) -> int:
         return self.slot_state.data_ptr()
 
-    # ---- the step's launches, slot-predicated ----------------------------------------------------------------------------
-    def _gemm(self, gin: PrefillIn, segs, lin0, lin1, Z: int, out: torch.Tensor, counts: Optional[torch.Tensor], st) -> int:
-        w0 = lin0.weight
-        rc = self.L.teal_batched_sparse_gemm_slots(ctypes.byref(gin), ctypes.byref(segs), w0.data_ptr(), w0.stride(1), w0.shape[0],
-                                                   lin1.weight.data_ptr() if lin1 is not None else None,
-                                                   lin1.weight.stride(1) if lin1 is not None else 0, lin1.weight.shape[0] if lin1 is not None else 0,
-                                                   out.data_ptr(), out.numel() * 4, Z, self.B, self._active,
-                                                   counts.data_ptr() if counts is not None else None, self.code, ctypes.byref(self._split), st)
-        if rc != 0:
-            _lib.check(rc, "teal_batched_sparse_gemm_slots")
-        return self._split.value
-
-    def _attention(self, at, A: torch.Tensor, ns: int, st):
-        cfg = self.cfg
-        kc, vc = at.kv_cache.k_cache, at.kv_cache.v_cache
-        rc = self.L.teal_batched_decode_attention_slots(A.data_ptr(), ns, self.rope.data_ptr(), self.pos_buf.data_ptr(), self._active,
-                                                        kc.data_ptr(), vc.data_ptr(), self.yt.data_ptr(), self.partials.data_ptr(),
-                                                        self.partials.numel() * 4, self.B, cfg.n_head, cfg.n_local_heads, cfg.head_dim,
-                                                        self.max_seq, self.code, st)
-        if rc != 0:
-            _lib.check(rc, "teal_batched_decode_attention_slots")
-
-    def _sample_slot(self, b: int, logits: torch.Tensor, temperature: float, top_k: Optional[int], st):
-        rc = self.L.teal_sample_topk_slot(logits.data_ptr(), self.cfg.vocab_size, self.code, int(top_k or 0), float(temperature),
-                                          self.rng_state[b].data_ptr(), self.tok_buf[b:].data_ptr(), self.pos_buf[b:].data_ptr(),
-                                          self.history[b].data_ptr(), self.history.shape[1], self.ws.data_ptr(), self.ws.numel() * 4,
-                                          self._active, b, st)
-        if rc != 0:
-            _lib.check(rc, "teal_sample_topk_slot")
-
     def _retire(self, mask: int, count_step: bool, st):
         if self._stops is not None:  # the same place in the step, one launch for one
             self._stops.launch(self._active, self.tok_buf, self.pos_buf, self.history, self.B, mask, self.max_seq, count_step, st=st)
@@ -457,20 +429,8 @@ class SlotDecodeEngine(BatchedDecodeEngine):
             _lib.check(rc, "teal_batched_retire")
 
     def _sample(self, temperature: float, top_k: Optional[int]):
-        st, src = runtime.stream_ptr(), self.logits
-        if self._proc is not None:  # tok_buf still holds the tokens this step was fed; an inactive slot counts nothing
-            self._proc.launch(self.logits, self.cfg.vocab_size, self.B, self.tok_buf, True, active=self._active, st=st)
-            src = self._proc.adj
-        if self._samp is not None:  # one launch, every active slot under its own row of settings
-            self._samp.launch(src, self.cfg.vocab_size, self.B, self.rng_state, self.tok_buf, self.pos_buf, self.history,
-                              self.history.shape[1], active=self._active, st=st)
-        else:
-            for b in range(self.B):
-                self._sample_slot(b, src[b], temperature, top_k, st)
-        if self._lp is not None:  # predicated on the active word the samplers saw (retire clears bits behind it)
-            V = self.cfg.vocab_size
-            self._lp.launch(self.logits, V, V, self.code, self.B, self.tok_buf, self.rng_state, active=self._active, st=st)
-        self._retire((1 << self.B) - 1, True, st)
+        super()._sample(temperature, top_k)  # (an inactive slot counts nothing, draws nothing and records nothing)
+        self._retire((1 << self.B) - 1, True, runtime.stream_ptr())
 
     def _loop_state(self):
         # the warm-up step retires too (and, with stop conditions on, writes a stopped slot's REASON and MATCH)
@@ -662,18 +622,10 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         for j, off in enumerate((SLOT_BUDGET, SLOT_PRODUCED, SLOT_EOS, SLOT_FINISH)):
             self.slot_state[off + s:off + s + 1].copy_(upd[j:j + 1])
         self.slot_state[SLOT_ACTIVE:SLOT_ACTIVE + 1].bitwise_or_(1 << s)
-        st, src = runtime.stream_ptr(), logits
-        if self._proc is not None:  # the first draw: nothing generated yet, so nothing is counted
-            self._proc.launch(logits, 0, 1, self.tok_buf[s:], False, row0=s, active=self._active, st=st)
-            src = self._proc.adj[s]
-        if self._samp is not None:
-            self._samp.launch(src, 0, 1, self.rng_state[s], self.tok_buf[s:], self.pos_buf[s:], self.history[s], self.history.shape[1],
-                              row0=s, active=self._active, st=st)
-        else:
-            self._sample_slot(s, src, temperature, top_k, st)
-        if self._lp is not None:  # the request's first token: entry 0 of its row
-            self._lp.launch(logits, 0, self.cfg.vocab_size, self.code, 1, self.tok_buf[s:], self.rng_state[s], row0=s,
-                            active=self._active, st=st)
+        st = runtime.stream_ptr()
+        # the first draw, entry 0 of the request's rows: nothing generated yet, so the processors count nothing
+        self._draw(logits, 0, 1, temperature, top_k, self.rng_state[s], self.tok_buf[s:], self.pos_buf[s:], self.history[s], False,
+                   row0=s, st=st)
         self._retire(1 << s, False, st)
 
     # ---- the batcher's view ------------------------------------------------------------------------------------------------

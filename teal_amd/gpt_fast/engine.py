@@ -736,10 +736,8 @@ class DecodeEngine(SamplerFeatures):
 
     # ---- device-resident decode loop: one hipGraph replay == one token, no host-side glue ---------
     def _self_step(self, temperature, top_k):
-        logits = self(self.tok_buf, self.pos_buf)
-        self.sample_fused(self._adjusted(logits, True), temperature, top_k, feed=True)
-        if self._lp is not None:
-            self._record_logprobs(logits, self.tok_buf)
+        logits = self(self.tok_buf, self.pos_buf)  # tok_buf holds the token this step was fed: the sequence's latest, counted first
+        self._draw(logits, 0, 1, temperature, top_k, self.rng_state, self.tok_buf, self.pos_buf, self.history, True)
 
     # ---- logit processors and token logprobs (SamplerFeatures): one more launch in front of / behind the sampler, when on -----
     speculating = False  # a SpeculativeDecoder drafts with this engine (set by it, cleared by its release())
@@ -753,16 +751,8 @@ class DecodeEngine(SamplerFeatures):
             raise NotImplementedError(f"{what} are not available under tensor parallelism: this rank's lm_head holds a slice of "
                                       f"the vocabulary, and the {launch} launch reads whole rows")
 
-    def _adjusted(self, logits: torch.Tensor, count_token: bool) -> torch.Tensor:
-        """the row the sampler reads: `logits` itself, or (processors on) their adjusted copy; count_token: the token in tok_buf —
-        the one this step was fed, the sequence's latest — is counted as generated first"""
-        if self._proc is None:
-            return logits
-        self._proc.launch(logits, 0, 1, self.tok_buf, count_token)
-        return self._proc.adj[0]
-
-    def _record_logprobs(self, logits: torch.Tensor, token: torch.Tensor):
-        self._lp.launch(logits, 0, self.cfg.vocab_size, self.code, 1, token, self.rng_state)
+    def _sample_row(self, row, logits, temperature, top_k, feed, st):
+        self.sample_fused(logits, temperature, top_k, feed)
 
     def read_logprobs(self, drawn: int, n: int):
         """(lp [n], top_ids [n, top_n], top_lp [n, top_n]) of the tokens history[drawn : drawn + n] — decode_n(..., drawn=drawn)'s"""
@@ -811,10 +801,8 @@ class DecodeEngine(SamplerFeatures):
         the torch sampler of generate.sample takes ~10): opens the sample's random stream; follow with decode_n(..., drawn=1)"""
         assert logits_row.is_contiguous() and logits_row.numel() == self.cfg.vocab_size and logits_row.dtype == self.dtype
         self.begin_sequence()
-        tok = self.sample_fused(self._adjusted(logits_row, False), temperature, top_k, feed=False)
-        if self._lp is not None:
-            self._record_logprobs(logits_row, tok)
-        return tok
+        self._draw(logits_row, 0, 1, temperature, top_k, self.rng_state, self.token, None, None, False, fed=self.tok_buf)
+        return self.token
 
     def decode_n(self, first_token: torch.Tensor, pos: int, n: int, temperature: float = 0.8,
                  top_k: Optional[int] = 200, use_graph: bool = True, drawn: int = 0, prompt_tokens=None) -> torch.Tensor:

@@ -1,6 +1,7 @@
 """What the fused engines share on the host side: the model's linears and the pointers a captured pass holds, the checks
 every dense-chain engine starts `supports` with, and the sampler-side features (token logprobs, logit processors, per-request
-sampling) of the decode engines.  A new per-request feature of the sampler goes into `SamplerFeatures` once, plus each engine's `_sample`.
+sampling) of the decode engines with the one launch sequence that draws a token under them.  A new per-request feature of the
+sampler goes into `SamplerFeatures` only.
 """
 from __future__ import annotations
 
@@ -78,12 +79,14 @@ class _SlotCaches:
 
 class SamplerFeatures:
     """Token logprobs (logprobs.py: one launch behind the sampler), per-request logit processors (logit_processors.py: one
-    launch in front of it) and per-request sampling (sampling.py: one launch in the samplers' place), all off until switched on.  The host class provides `_feature_rows` (its sequences), `history`
-    (int32 [..., length]: a logprob row is as long), `cfg.vocab_size`, `dtype` and a `_graph` the setters drop."""
+    launch in front of it) and per-request sampling (sampling.py: one launch in the samplers' place), all off until switched on,
+    and `_draw`, the launches of a draw under them.  The host class provides `_feature_rows` (its sequences), `history` (int32
+    [..., length]: a logprob row is as long), `cfg.vocab_size`, `dtype`, `code`, a `_graph` the setters drop and `_sample_row`."""
 
     _lp: Optional[LP.LogprobBuffers] = None      # set_logprobs
     _proc: Optional[PR.LogitProcessors] = None   # set_logit_processors
     _samp: Optional[SM.SamplingParams] = None    # set_sampling_params
+    _active: Optional[int] = None                # the address of a slot engine's active word: its launches are predicated on it
 
     def _feature_refusal(self, what: str) -> None:
         """raises if this engine cannot switch `what` ("logprobs" / "logit processors" / "per-request sampling") on"""
@@ -161,6 +164,31 @@ class SamplerFeatures:
     lp_state = property(lambda self: None if self._proc is None else self._proc.state)
     lp_params = property(lambda self: None if self._proc is None else self._proc.params)
     lp_bias = property(lambda self: None if self._proc is None else self._proc.bias)
+
+    def _sample_row(self, row: int, logits: torch.Tensor, temperature, top_k, feed: bool, st):
+        """the engine's fused top-k sampler, one launch: sequence `row` draws from its row `logits`; feed: the token also moves
+        the sequence's position and history on"""
+        raise NotImplementedError
+
+    def _draw(self, logits: torch.Tensor, stride: int, rows: int, temperature, top_k, rng_state: torch.Tensor, tokens: torch.Tensor,
+              pos: Optional[torch.Tensor], history: Optional[torch.Tensor], count_token: bool, row0: int = 0,
+              fed: Optional[torch.Tensor] = None, st=None):
+        """Sequences row0 .. row0+rows-1 draw their next token from `logits` (rows `stride` elements apart; 0: the one row as it
+        stands): the processors' launch (if on), then ONE sampling launch over the rows or the fused top-k sampler row by row,
+        then the logprob launch (if on) over the logits as the model gave them.  rng_state / tokens / pos / history are the first
+        row's; pos and history None: the draw feeds no loop state.  count_token: the processors first count each row's token in
+        `fed` (default `tokens`: the buffer the step was fed from) as generated."""
+        active, src = self._active, logits
+        if self._proc is not None:
+            self._proc.launch(logits, stride, rows, tokens if fed is None else fed, count_token, row0=row0, active=active, st=st)
+            src = self._proc.adj[row0:row0 + rows] if stride else self._proc.adj[row0]
+        if self._samp is not None:  # one launch, every row under its own settings
+            self._samp.launch(src, stride, rows, rng_state, tokens, pos, history, self.history.shape[-1], row0=row0, active=active, st=st)
+        else:
+            for r in range(rows):
+                self._sample_row(row0 + r, src[r] if stride else src, temperature, top_k, pos is not None, st)
+        if self._lp is not None:  # (a slot engine: predicated on the active word the samplers saw — retire clears bits behind it)
+            self._lp.launch(logits, stride, self.cfg.vocab_size, self.code, rows, tokens, rng_state, row0=row0, active=active, st=st)
 
     def _feature_loop_state(self):
         """the features' share of what a captured step carries from replay to replay"""

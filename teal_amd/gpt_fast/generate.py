@@ -635,6 +635,22 @@ def check_batched_args(args) -> int:
     return B
 
 
+def _engine_path_refusals(args, flags: str, plural: bool, why_spec: str, why_engine: str) -> None:
+    """the four refusals every feature that lives in a launch of the fused engines' step shares: speculative decoding, tensor
+    parallelism, no TEAL thresholds, no engine path.  flags: as the user wrote them (plural: more than one); why_spec /
+    why_engine: the feature's own reason behind the first ("" for none) and the last"""
+    do, need = ("do", "need") if plural else ("does", "needs")
+    if getattr(args, "draft_checkpoint_path", None) is not None or getattr(args, "self_speculate", False):
+        raise SystemExit(f"{flags} {do} not combine with speculative decoding{why_spec}")
+    if int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1"))) > 1:
+        raise SystemExit(f"{flags} {do} not run under tensor parallelism (a rank's lm_head holds a slice of the vocabulary)")
+    if getattr(args, "dense", False) or (not args.synthetic and args.hist_path is None):
+        raise SystemExit(f"{flags} {need} TEAL thresholds (--hist_path, or --synthetic): the fused engines run patched models only")
+    if getattr(args, "requests", None) is None and (getattr(args, "no_engine", False) or not (args.compile or args.engine)):
+        raise SystemExit(f"{flags} {need} a fused engine (--compile or --engine, without --no_engine, or --requests): the module "
+                         f"path{why_engine}")
+
+
 def check_logprobs_args(args) -> Optional[int]:
     """--logprobs: None (off), 0 (each generated token's logprob) or 1..8 (and that many most likely alternates); every refusal
     is raised here, before anything is loaded.  The logprobs come from a launch inside the fused engines' step, so the flag
@@ -644,15 +660,7 @@ def check_logprobs_args(args) -> Optional[int]:
         return None
     if not 0 <= int(n) <= 8:
         raise SystemExit(f"--logprobs must be in 0..8 (alternates per token), got {n}")
-    if getattr(args, "draft_checkpoint_path", None) is not None or getattr(args, "self_speculate", False):
-        raise SystemExit("--logprobs does not combine with speculative decoding")
-    if int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1"))) > 1:
-        raise SystemExit("--logprobs does not run under tensor parallelism (a rank's lm_head holds a slice of the vocabulary)")
-    if getattr(args, "dense", False) or (not args.synthetic and args.hist_path is None):
-        raise SystemExit("--logprobs needs TEAL thresholds (--hist_path, or --synthetic): the fused engines run patched models only")
-    if getattr(args, "requests", None) is None and (getattr(args, "no_engine", False) or not (args.compile or args.engine)):
-        raise SystemExit("--logprobs needs a fused engine (--compile or --engine, without --no_engine, or --requests): the module "
-                         "path returns token ids only")
+    _engine_path_refusals(args, "--logprobs", False, "", " returns token ids only")
     return int(n)
 
 
@@ -670,16 +678,8 @@ def check_processor_args(args) -> Dict:
     c = {k: v for k, v in c.items() if v != (1.0 if k == "repetition_penalty" else 0.0)}
     if not c:
         return {}
-    flags = "--repetition_penalty / --presence_penalty / --frequency_penalty"
-    if getattr(args, "draft_checkpoint_path", None) is not None or getattr(args, "self_speculate", False):
-        raise SystemExit(f"{flags} do not combine with speculative decoding (the accept rule compares the models' own distributions)")
-    if int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1"))) > 1:
-        raise SystemExit(f"{flags} do not run under tensor parallelism (a rank's lm_head holds a slice of the vocabulary)")
-    if getattr(args, "dense", False) or (not args.synthetic and args.hist_path is None):
-        raise SystemExit(f"{flags} need TEAL thresholds (--hist_path, or --synthetic): the fused engines run patched models only")
-    if getattr(args, "requests", None) is None and (getattr(args, "no_engine", False) or not (args.compile or args.engine)):
-        raise SystemExit(f"{flags} need a fused engine (--compile or --engine, without --no_engine, or --requests): the module "
-                         "path samples from the raw logits")
+    _engine_path_refusals(args, "--repetition_penalty / --presence_penalty / --frequency_penalty", True,
+                          " (the accept rule compares the models' own distributions)", " samples from the raw logits")
     return c
 
 
@@ -697,17 +697,8 @@ def check_sampling_args(args) -> Dict:
             raise SystemExit(f"--{name} must be {rule}, got {c[name]!r}") from None
     if c["top_p"] >= 1.0 and c["min_p"] == 0.0:
         return {}
-    flags = "--top_p / --min_p"
-    if getattr(args, "draft_checkpoint_path", None) is not None or getattr(args, "self_speculate", False):
-        raise SystemExit(f"{flags} do not combine with speculative decoding (the accept rule compares the models' distributions under "
-                         "one temperature and top_k)")
-    if int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1"))) > 1:
-        raise SystemExit(f"{flags} do not run under tensor parallelism (a rank's lm_head holds a slice of the vocabulary)")
-    if getattr(args, "dense", False) or (not args.synthetic and args.hist_path is None):
-        raise SystemExit(f"{flags} need TEAL thresholds (--hist_path, or --synthetic): the fused engines run patched models only")
-    if getattr(args, "requests", None) is None and (getattr(args, "no_engine", False) or not (args.compile or args.engine)):
-        raise SystemExit(f"{flags} need a fused engine (--compile or --engine, without --no_engine, or --requests): the module "
-                         "path's sampler knows temperature and top_k only")
+    _engine_path_refusals(args, "--top_p / --min_p", True, " (the accept rule compares the models' distributions under one temperature "
+                          "and top_k)", "'s sampler knows temperature and top_k only")
     return c
 
 
