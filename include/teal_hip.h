@@ -173,9 +173,23 @@ int teal_sparse_gateup_silu(const void* x, const void* w1T, const void* w3T, voi
 #define TEAL_IN_ATTN_MERGE 4 /* x = attention output merged from the split-KV partials per head written by
                               * teal_decode_attention_split(y = NULL, nsplit = 4 or 8): x points at the fp32
                               * partials [Z/head_dim][nsplit][head_dim + 2]; att_head_dim = head_dim,
-                              * att_nsplit = nsplit (0 means 4); Z <= 16384 (nsplit 4) / 8192 (nsplit 8) */
+                              * att_nsplit = nsplit (0 means 4); Z <= 16384 (nsplit 4) / 8192 (nsplit 8).  A split whose
+                              * weight is zero (an empty split: sum == 0) is skipped whatever its o holds, as in the merge launch */
 #define TEAL_OUT_ROUNDED 0   /* y rounded to dtype (runs the ordered slab reduce when split-K is used) */
-#define TEAL_OUT_SLABS 1     /* leave the fp32 split-K slabs for the next launch's RESID_NORM producer */
+#define TEAL_OUT_SLABS 1     /* leave the fp32 split-K slabs for the next launch's RESID_NORM producer.
+                              * Which rows slab k (of *nslabs_out = split) sums — part of the ABI: both kernels follow it, and so
+                              * does the partial that a TEAL_OUT_ROUNDED / TEAL_OUT_SLAB_SUM launch folds in slice order.  The
+                              * vector is cut into chunks of 64 activations, chunk c = elements 64 c .. 64 c + 63; a round is 16
+                              * chunks.  While split <= the vector's rounds (ceil(ceil(Z / 64) / 16)) and a slice's lists fit
+                              * the LDS (always, for the lean kernel):
+                              *   element-wise producers (PLAIN, SILU_MUL, MASKED, ATTN_MERGE): chunk c belongs to slice c mod
+                              *     split (and, inside its workgroup, to wave (c div split) mod 16);
+                              *   RESID_NORM (every workgroup holds the whole vector, wave w the chunks w + 16 k): chunk
+                              *     w + 16 k belongs to slice (k + w) mod split.
+                              * Otherwise (general kernel only: more slices than rounds, or lists beyond the LDS) the kept rows
+                              * of a column tile form ONE ascending list of `total` entries and slice k sums entries
+                              * [total * k / split, total * (k + 1) / split) (integer division).
+                              * Slab k holds the fp32 sum of its kept rows only; a slice that keeps nothing writes +0.0. */
 #define TEAL_OUT_QKV_ROPE 3  /* nseg == 3 = q | k | v of ONE fused wqkv image, RESID_NORM input: when the launch needs no
                               * split-K (and the lean kernel takes it: *nslabs_out = 0), its epilogue applies RoPE to q and
                               * to the new k row and appends k, v to the caches (gpt-fast/model.py:170-178): y[0] = rotated

@@ -288,11 +288,24 @@ __global__ __launch_bounds__(WAVES * 64) void sparse_gemv_kernel(const Params p)
             if constexpr (NS == 8) Ls += TEAL_DPPF(Ls, 0x141);
 #undef TEAL_DPPF
             const int cw = __float_as_int(f / Ls);
+            // A split that contributes nothing (empty: sum 0; or e^(m - M) underflowed) is skipped, as merge_head does
+            // (teal_attention.hip: `if (ls > 0)`): whatever its o holds, NaN included, stays out of the sum.  Every lane holds
+            // the weight of a (chunk, split) the wave uses, so one ballot tells whether any split is skipped at all: the
+            // usual case, none, keeps the unguarded chain (wave-uniform branch)
+            const bool all_live = __ballot(__int_as_float(cw) > 0.0f) == ~0ull;
 #pragma unroll
             for (int k = 0; k < KM; ++k) {
                 float Os = 0.0f;
+                if (all_live) {
 #pragma unroll
-                for (int q = 0; q < NS; ++q) Os = fmaf(ov[k][q], __int_as_float(__builtin_amdgcn_readlane(cw, NS * k + q)), Os);
+                    for (int q = 0; q < NS; ++q) Os = fmaf(ov[k][q], __int_as_float(__builtin_amdgcn_readlane(cw, NS * k + q)), Os);
+                } else {
+#pragma unroll
+                    for (int q = 0; q < NS; ++q) {
+                        const float wq = __int_as_float(__builtin_amdgcn_readlane(cw, NS * k + q));
+                        if (wq > 0.0f) Os = fmaf(ov[k][q], wq, Os);
+                    }
+                }
                 xr[k] = float_to_bits<BF16>(Os);
             }
 #pragma unroll
