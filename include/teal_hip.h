@@ -718,6 +718,13 @@ int teal_set_phase_buffer(void* dev_u64);
  * workgroups, and the buffer must hold u64_per_launch * (launches between two teal_set_phase_stride calls) uint64;
  * 0 (default): every launch stamps the start of the buffer. */
 int teal_set_phase_stride(size_t u64_per_launch);
+
+/* Probe of the epilogues' row-group reduction (teal_common.h: row_reduce_scatter) against the shuffle butterfly it replaces,
+ * on caller-supplied bit patterns.  in: uint32 [nwaves][64 lanes][8 accumulators], read as floats; lanes_per_row 8 or 16.
+ *   scatter: uint32 [nwaves][64][2] — lane 16 r + i (i < lanes_per_row) holds the totals of accumulators r and 4 + r over the
+ *            lanes l with l % lanes_per_row == i;
+ *   shuffle: uint32 [nwaves][64][8] — `v += __shfl_xor(v, off)` for off = lanes_per_row .. 32: lane i holds every total. */
+int teal_probe_row_reduce(const void* in_u32, void* scatter_u32, void* shuffle_u32, int nwaves, int lanes_per_row, void* stream);
 #endif /* TEAL_DIAGNOSTICS */
 
 /* ---- introspection (pure functions of their arguments; teal_get_config also of the device's CU count) - */

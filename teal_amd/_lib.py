@@ -83,7 +83,7 @@ EXPORTS = (
 
 # what libteal_hip_diag.so exports on top (include/teal_hip.h, #ifdef TEAL_DIAGNOSTICS); libteal_hip.so must export NONE of them
 DIAG_EXPORTS = ("teal_set_tuning", "teal_set_fast", "teal_set_wave_local", "teal_set_phase_buffer", "teal_set_phase_stride",
-                "teal_last_launch_desc")
+                "teal_last_launch_desc", "teal_probe_row_reduce")
 
 _lib = None    # what load() returns: the product library (or the diagnostics build under TEAL_LIB_FLAVOR=diag / diagnostics())
 _diag = None   # the diagnostics build, once loaded
@@ -249,6 +249,7 @@ def _open(path: str, diag: bool) -> ctypes.CDLL:
         L.teal_set_wave_local.argtypes = [ci]
         L.teal_set_fast.argtypes = [ci]
         L.teal_last_launch_desc.restype = ctypes.c_char_p
+        L.teal_probe_row_reduce.argtypes = [vp, vp, vp, ci, ci, vp]
     L.teal_is_diagnostics_build = diag
     return L
 

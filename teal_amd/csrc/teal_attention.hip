@@ -490,22 +490,30 @@ __global__ __launch_bounds__(NT) void decode_attention_split_kernel(
             }
         }
     }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        if constexpr (SL <= 8) o[j] = xor_add<8>(o[j]);
-        o[j] = xor_add<32>(xor_add<16>(o[j]));
+    // row groups of the wave as a reduce-scatter (teal_common.h: the butterfly's pairs and order, no LDS-crossbar
+    // instruction): lane 16 r + i holds the totals of columns 8 i + r and 8 i + 4 + r, and all 64 lanes deposit
+    float olo, ohi;
+    row_reduce_scatter<SL>(o, olo, ohi);
+    if (SL == 16 || (lane & 15) < SL) {
+        const int slot = scatter_slot((lane & 15) * 8 + (lane >> 4));
+        part[wave * hd + slot] = olo;
+        part[wave * hd + (slot ^ 4)] = ohi;
     }
-    if (lane < SL) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) part[wave * hd + lane * 8 + j] = o[j];
-    }
+    // (indices of the final sum: ahead of the barrier, where its threads wait for the slowest wave anyway; pinned as
+    // integers — a pointer that passes through an asm statement loses its address space and turns into flat accesses)
+    int pidx = scatter_slot(tid & (hd - 1)), oidx = 2 + (tid & (hd - 1));
+    asm volatile("" : "+v"(pidx), "+v"(oidx));
     __syncthreads();
     stamp_p(5);
     if (tid < hd) {
+        float pw[NW];  // every partial requested before the first add (one LDS round trip), the adds in wave order
+#pragma unroll
+        for (int w = 0; w < NW; ++w) pw[w] = part[w * hd + pidx];
+        __builtin_amdgcn_sched_barrier(0);
         float acc = 0.0f;
 #pragma unroll
-        for (int w = 0; w < NW; ++w) acc += part[w * hd + tid];
-        out[2 + tid] = acc;
+        for (int w = 0; w < NW; ++w) acc += pw[w];
+        out[oidx] = acc;
     }
     if (tid == 0) { out[0] = mx; out[1] = tot; }
     stamp_p(7);
@@ -798,32 +806,34 @@ __global__ __launch_bounds__(NT) void decode_attention_gqa_kernel(
             }
         }
     }
-    // sum over the row groups of the wave (lanes with the same 16-byte slice)
+    // sum over the row groups of the wave (lanes with the same 16-byte slice), a reduce-scatter per head: lane 16 q + i holds
+    // the totals of the head's columns 8 i + q and 8 i + 4 + q (teal_common.h: row_reduce_scatter, scatter_slot)
+    float olo[REP], ohi[REP];
 #pragma unroll
-    for (int r = 0; r < REP; ++r)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                float v = o[r][j][e];
-                if constexpr (SL <= 8) v = xor_add<8>(v);
-                v = xor_add<32>(xor_add<16>(v));
-                o[r][j][e] = v;
-            }
+    for (int r = 0; r < REP; ++r) {
+        const float v[8] = {o[r][0][0], o[r][0][1], o[r][1][0], o[r][1][1], o[r][2][0], o[r][2][1], o[r][3][0], o[r][3][1]};
+        row_reduce_scatter<SL>(v, olo[r], ohi[r]);
+    }
     __syncthreads();  // every wave is done reading probabilities: the region becomes the per-wave partial o
     float* part = sc;
-    if (lane < SL) {
+    if (SL == 16 || (lane & 15) < SL) {
+        const int slot = scatter_slot((lane & 15) * 8 + (lane >> 4));
 #pragma unroll
-        for (int r = 0; r < REP; ++r)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                *reinterpret_cast<f32x2*>(part + (wave * REP + r) * hd + lane * 8 + 2 * j) = o[r][j];
+        for (int r = 0; r < REP; ++r) {
+            part[(wave * REP + r) * hd + slot] = olo[r];
+            part[(wave * REP + r) * hd + (slot ^ 4)] = ohi[r];
+        }
     }
     __syncthreads();
     for (int c = tid; c < REP * hd; c += NT) {
+        const float* psrc = part + (c & ~(hd - 1)) + scatter_slot(c & (hd - 1));
+        float pw[NW];  // every partial requested before the first add, the adds in wave order
+#pragma unroll
+        for (int w = 0; w < NW; ++w) pw[w] = psrc[w * REP * hd];
+        __builtin_amdgcn_sched_barrier(0);
         float acc = 0.0f;
 #pragma unroll
-        for (int w = 0; w < NW; ++w) acc += part[w * REP * hd + c];
+        for (int w = 0; w < NW; ++w) acc += pw[w];
         out_of(c / hd)[2 + (c % hd)] = acc;
     }
     if (tid < REP) {

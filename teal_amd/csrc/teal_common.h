@@ -243,9 +243,10 @@ __device__ __forceinline__ float wave_sum_f(float v) {
 
 // v[lane] + v[lane ^ OFF] for OFF = 8, 16, 32 — the butterfly steps of the row-group reductions — without the LDS
 // crossbar round trip of __shfl_xor (ds_bpermute) where the ISA offers something cheaper: a DPP row rotate inside the
-// 16-lane row (8), ds_swizzle's SWAP mode (16: no address VGPR, no LDS bank access); 32 stays a shuffle
-// (v_permlane32_swap through the builtin returned both halves unswapped on this toolchain: not used).
-// Same operands as the shuffle, a + b == b + a: bit-identical sums.
+// 16-lane row (8), ds_swizzle's SWAP mode (16: no address VGPR, no LDS bank access); 32 stays a shuffle: a butterfly
+// keeps ONE value per lane, and v_permlane32_swap with the same value as both operands hands both halves back unswapped
+// (the half-swap instructions exchange halves of two DIFFERENT registers: row_reduce_scatter below is the form that fits
+// them).  Same operands as the shuffle, a + b == b + a: bit-identical sums.
 template <int OFF>
 __device__ __forceinline__ float xor_add(const float v) {
     const int iv = __builtin_bit_cast(int, v);
@@ -257,6 +258,39 @@ __device__ __forceinline__ float xor_add(const float v) {
         return v + __shfl_xor(v, OFF);
     }
 }
+
+// Half-swap steps of a reduce-scatter.  v_permlane16_swap exchanges rows 1, 3 of its first operand with rows 0, 2 of its
+// second, v_permlane32_swap lanes 32-63 of the first with lanes 0-31 of the second: fed two DIFFERENT accumulators a, b,
+// the sum of the two results is a[l] + a[l ^ OFF] in one half of the lanes (the even rows / lanes 0-31) and
+// b[l ^ OFF] + b[l] in the other — in both halves the operand order of the butterfly's lower lane, so NaN payloads agree
+// with xor_add as well.  One VALU exchange and one add per PAIR of accumulators, no LDS crossbar.
+__device__ __forceinline__ float swap16_add(const float a, const float b) {
+    const auto r = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
+    return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
+}
+__device__ __forceinline__ float swap32_add(const float a, const float b) {
+    const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
+    return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
+}
+
+// The row-group reduction of the GEMV and attention epilogues as a reduce-scatter: a lane's 8 accumulators are summed over
+// the 64 / LPR lanes that share lane % LPR, with the pairs and the order of xor_add<8> (LPR 8), <16>, <32>, and the totals
+// are left spread over the wave: lane 16 r + i (i < LPR) holds the total of v[r] in `lo` and of v[4 + r] in `hi`, both
+// bit-identical to what the butterfly leaves in lane i.  Lanes with i >= LPR hold nothing of use.
+template <int LPR>
+__device__ __forceinline__ void row_reduce_scatter(const float (&v)[8], float& lo, float& hi) {
+    static_assert(LPR == 8 || LPR == 16, "row groups of 8 or 16 lanes");
+    float t[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) t[j] = LPR <= 8 ? xor_add<8>(v[j]) : v[j];
+    lo = swap32_add(swap16_add(t[0], t[1]), swap16_add(t[2], t[3]));
+    hi = swap32_add(swap16_add(t[4], t[5]), swap16_add(t[6], t[7]));
+}
+
+// where the total of tile column c = 8 i + j (row-group lane i, accumulator j) sits in a wave's [LPR * 8] LDS deposit: the
+// column itself, with bit 2 flipped for the columns past 64 — the 64 lanes of a deposit store (columns 8 i + r: `lo`,
+// 8 i + 4 + r: `hi`) and the 64 threads of a wave that reads consecutive columns back each touch 64 different banks
+__device__ __forceinline__ int scatter_slot(const int c) { return c ^ ((c >> 4) & 4); }
 
 // max of a float over the 64 lanes of a wave (result valid in every lane): DPP row shifts + four v_readlane, no LDS
 // crossbar traffic (six __shfl_xor = ds_bpermute round trips otherwise)

@@ -442,29 +442,22 @@ __global__ __launch_bounds__(1024) void gemv_fast_kernel(const void* in0, const 
     if (prio_set) __builtin_amdgcn_s_setprio(0);
     if constexpr (PHASE) { if (a.phase && lane == 0) a.phase[(size_t)bid * kPhaseRow + 16 + wave] = wall_clock64(); }
 
-    // ---- reduce: row groups of the wave (shuffles), then waves in fixed order through LDS -------------------
-    // lane ^ 8 as a DPP row rotate, lane ^ 16 as a ds_swizzle swap, lane ^ 32 a shuffle (round 2: +0.7 % tokens/s over shuffles for
-    // every step; same pairs, same order: bit-identical)
-#pragma unroll
-    for (int j = 0; j < CPL; ++j) {
-        if constexpr (LPR <= 8) acc[j] = xor_add<8>(acc[j]);
-        acc[j] = xor_add<32>(xor_add<16>(acc[j]));
-    }
-    if constexpr (PAIR) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if constexpr (LPR <= 8) acc2[j] = xor_add<8>(acc2[j]);
-            acc2[j] = xor_add<32>(xor_add<16>(acc2[j]));
-        }
-    }
-    if (lane < LPR) {
-        float* r = red + wave * BN + lane * CPL;
-#pragma unroll
-        for (int j = 0; j < CPL; ++j) r[j] = acc[j];
+    // ---- reduce: row groups of the wave (lane exchanges), then waves in fixed order through LDS ---------------
+    // lane ^ 8 as a DPP row rotate, lane ^ 16 and lane ^ 32 as half-swaps of two accumulators at a time (row_reduce_scatter:
+    // the pairs and the order of the butterfly, bit-identical; no LDS-crossbar instruction on the path of the last wave).
+    // Lane 16 r + i holds the totals of columns 8 i + r and 8 i + 4 + r: all 64 lanes deposit, two words each.
+    float lo, hi, lo2 = 0.0f, hi2 = 0.0f;
+    row_reduce_scatter<LPR>(acc, lo, hi);
+    if constexpr (PAIR) row_reduce_scatter<LPR>(acc2, lo2, hi2);
+    if (LPR == 16 || (lane & 15) < LPR) {
+        const int slot = scatter_slot((lane & 15) * CPL + (lane >> 4));
+        float* r = red + wave * BN;
+        r[slot] = lo;
+        r[slot ^ 4] = hi;
         if constexpr (PAIR) {
-            float* r2 = red + (WAVES + wave) * BN + lane * 8;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) r2[j] = acc2[j];
+            float* r2 = red + (WAVES + wave) * BN;
+            r2[slot] = lo2;
+            r2[slot ^ 4] = hi2;
         }
     }
     float* xsw = red + (PAIR ? 2 : 1) * WAVES * BN;  // int8: [WAVES] per-wave activation sums
@@ -473,15 +466,55 @@ __global__ __launch_bounds__(1024) void gemv_fast_kernel(const void* in0, const 
         xs = xor_add<32>(xor_add<16>(xs));
         if (lane == 0) xsw[wave] = xs;
     }
+    // What the epilogue needs besides the sums, ahead of the barrier: the waves that run it are the oldest of the workgroup
+    // and wait here for the slowest one.  ROPE: (cos, sin) unpacked, q / k / v decided and the address of the store — the
+    // output column or the cache row (head_dim is 64 or 128: a shift, not a division) — pinned in registers.
+    float rope_c = 0.0f, rope_s = 0.0f;
+    uint16_t* rope_dst = nullptr;
+    bool rope_rot = false;
+    if constexpr (ROPE) {
+        if (tid < BN) {
+            const uint32_t c = (uint32_t)tile * BN + tid;
+            rope_c = bits_to_float(rope_cs & 0xFFFFu, BF16);
+            rope_s = bits_to_float(rope_cs >> 16, BF16);
+            const uint32_t dimq = (uint32_t)a.rope_dim, kvw = (uint32_t)a.rope_kv, hdm = (uint32_t)a.rope_hd;
+            const bool isq = c < dimq, isk = c < dimq + kvw;
+            const uint32_t cc = c - dimq - (isk ? 0u : kvw);
+            const uint32_t kvh = cc >> (6u + (hdm >> 7)), d = cc & (hdm - 1u);
+            rope_rot = isk;  // q and k are rotated, v is stored as projected
+            rope_dst = isq ? reinterpret_cast<uint16_t*>(a.y) + c
+                           : (isk ? a.kc : a.vc) + ((size_t)kvh * (size_t)a.rope_max_seq + (size_t)rope_p) * hdm + d;
+            asm volatile("" : "+v"(rope_dst), "+v"(rope_c), "+v"(rope_s));
+        }
+    }
     __syncthreads();
     stamp(6);
     if (tid < BN) {  // whole waves: BN is a multiple of 64
         const uint32_t c = (uint32_t)tile * BN + tid;
+        const float* rsrc = red + scatter_slot(tid);
         float gs = 0.0f, us = 0.0f;
+        if constexpr (KR <= 8) {
+            // every partial requested before the first add (one LDS round trip), the adds in wave order
+            float pg[WAVES], pu[PAIR ? WAVES : 1];
 #pragma unroll
-        for (int wv = 0; wv < WAVES; ++wv) {
-            gs += red[wv * BN + tid];
-            if constexpr (PAIR) us += red[(WAVES + wv) * BN + tid];
+            for (int wv = 0; wv < WAVES; ++wv) {
+                pg[wv] = rsrc[wv * BN];
+                if constexpr (PAIR) pu[wv] = rsrc[(WAVES + wv) * BN];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int wv = 0; wv < WAVES; ++wv) {
+                gs += pg[wv];
+                if constexpr (PAIR) us += pu[wv];
+            }
+        } else {
+            // KR 16 (MODE 1 on vectors past 8192) sits at the 128-VGPR limit of a 1024-thread workgroup and spills already:
+            // 16 partials live at once cost it one more spilled register, so it keeps the compiler's own grouping of the reads
+#pragma unroll
+            for (int wv = 0; wv < WAVES; ++wv) {
+                gs += rsrc[wv * BN];
+                if constexpr (PAIR) us += rsrc[(WAVES + wv) * BN];
+            }
         }
         if constexpr (W8) {
             // sum q * x = sum (q + 1152) * x - 1152 * sum x (fma8 on bytes), then the per-column scale in fp32 before the one
@@ -510,18 +543,10 @@ __global__ __launch_bounds__(1024) void gemv_fast_kernel(const void* in0, const 
                 // (projection rounded, rotation in fp32, rounded again — what the attention launch did with the same helpers)
                 const uint16_t b16 = float_to_bits<BF16>(gs);
                 const float f = bits_to_float(b16, BF16);
-                const float pr = __shfl_xor(f, 1);
-                const float cs = bits_to_float(rope_cs & 0xFFFFu, BF16), sn = bits_to_float(rope_cs >> 16, BF16);
-                const uint16_t rb = float_to_bits<BF16>((tid & 1) ? rope_odd(pr, f, cs, sn) : rope_even(f, pr, cs, sn));
-                const uint32_t dimq = (uint32_t)a.rope_dim, kvw = (uint32_t)a.rope_kv, hdm = (uint32_t)a.rope_hd;
-                if (c < dimq) {
-                    reinterpret_cast<uint16_t*>(a.y)[c] = rb;
-                } else {
-                    const bool isk = c < dimq + kvw;
-                    const uint32_t cc = c - dimq - (isk ? 0u : kvw);
-                    const uint32_t kvh = cc / hdm, d = cc & (hdm - 1u);
-                    (isk ? a.kc : a.vc)[((size_t)kvh * (size_t)a.rope_max_seq + (size_t)rope_p) * hdm + d] = isk ? rb : b16;
-                }
+                const float pr = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, f), 0xB1, 0xf, 0xf, false));  // quad_perm [1,0,3,2]
+                const uint16_t rb = float_to_bits<BF16>((tid & 1) ? rope_odd(pr, f, rope_c, rope_s) : rope_even(f, pr, rope_c, rope_s));
+                // (global, said explicitly: the pointer went through the asm statement above and would be a flat store)
+                *(__attribute__((address_space(1))) uint16_t*)rope_dst = rope_rot ? rb : b16;
             } else if (a.act0 && s == 0) {  // the gate tiles of gate | up: activation applied here (model.py:258)
                 reinterpret_cast<uint16_t*>(a.y)[c] = silu_bits<BF16>(gs);
             } else if (a.sum32) {           // TEAL_OUT_SLAB_SUM without split-K: the unrounded fp32 sum

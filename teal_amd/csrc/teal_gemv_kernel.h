@@ -591,23 +591,42 @@ __global__ __launch_bounds__(WAVES * 64) void sparse_gemv_kernel(const Params p)
     stamp(p, 5);
     if (p.phase && lane == 0) p.phase[(size_t)blockIdx.x * kPhaseRow + 16 + (wave & 15)] = wall_clock64();  // per-wave end of stream
     // ---- reduce: row groups of the wave, then waves (fixed order) --------------------------------
-#pragma unroll
-    for (int off = LPR; off < 64; off <<= 1) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] += __shfl_xor(acc[j], off);
-        if constexpr (PAIR) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc2[j] += __shfl_xor(acc2[j], off);
+    if constexpr (LPR <= 16) {
+        // the lean kernel's reduce-scatter (teal_common.h: row_reduce_scatter — the butterfly's pairs and order): lane
+        // 16 r + i holds the totals of columns 8 i + r and 8 i + 4 + r; deposited where column c is read back, red[.. + c]
+        float lo, hi;
+        row_reduce_scatter<LPR>(acc, lo, hi);
+        const int c0 = (lane & 15) * 8 + (lane >> 4);
+        if (LPR == 16 || (lane & 15) < LPR) {
+            red[wave * BN + c0] = lo;
+            red[wave * BN + c0 + 4] = hi;
         }
-    }
-    if (lane < LPR) {
-        float* r = red + wave * BN + lane * 8;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] = acc[j];
         if constexpr (PAIR) {
-            float* r2 = red + (WAVES + wave) * BN + lane * 8;
+            row_reduce_scatter<LPR>(acc2, lo, hi);
+            if (LPR == 16 || (lane & 15) < LPR) {
+                red[(WAVES + wave) * BN + c0] = lo;
+                red[(WAVES + wave) * BN + c0 + 4] = hi;
+            }
+        }
+    } else {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) r2[j] = acc2[j];
+        for (int off = LPR; off < 64; off <<= 1) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[j] += __shfl_xor(acc[j], off);
+            if constexpr (PAIR) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc2[j] += __shfl_xor(acc2[j], off);
+            }
+        }
+        if (lane < LPR) {
+            float* r = red + wave * BN + lane * 8;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) r[j] = acc[j];
+            if constexpr (PAIR) {
+                float* r2 = red + (WAVES + wave) * BN + lane * 8;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) r2[j] = acc2[j];
+            }
         }
     }
     float* xsw = red + (PAIR ? 2 : 1) * WAVES * BN;  // W8: [2][WAVES] per-wave activation sums

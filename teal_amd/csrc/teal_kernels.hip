@@ -121,6 +121,32 @@ __global__ __launch_bounds__(1024) void compact_kernel(const uint16_t* __restric
 }
 
 
+#ifdef TEAL_DIAGNOSTICS
+// row_reduce_scatter against the __shfl_xor butterfly it replaces, on raw bit patterns: one wave per workgroup, lane l reads
+// in[wave][l][0..8)
+template <int LPR>
+__global__ __launch_bounds__(64) void row_reduce_probe_kernel(const uint32_t* __restrict__ in, uint32_t* __restrict__ scatter_out,
+                                                              uint32_t* __restrict__ shuffle_out) {
+    const int lane = threadIdx.x;
+    const size_t base = ((size_t)blockIdx.x * 64 + lane) * 8;
+    float v[8], b[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = b[j] = __builtin_bit_cast(float, in[base + j]);
+    float lo, hi;
+    row_reduce_scatter<LPR>(v, lo, hi);
+    scatter_out[((size_t)blockIdx.x * 64 + lane) * 2] = __builtin_bit_cast(uint32_t, lo);
+    scatter_out[((size_t)blockIdx.x * 64 + lane) * 2 + 1] = __builtin_bit_cast(uint32_t, hi);
+#pragma unroll
+    for (int off = LPR; off < 64; off <<= 1) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) b[j] += __shfl_xor(b[j], off);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) shuffle_out[base + j] = __builtin_bit_cast(uint32_t, b[j]);
+}
+#endif
+
+
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
@@ -660,6 +686,17 @@ int teal_set_phase_stride(size_t u64_per_launch) {
     g_phase_stride = u64_per_launch;
     g_phase_seq = 0;
     return TEAL_OK;
+}
+
+int teal_probe_row_reduce(const void* in_u32, void* scatter_u32, void* shuffle_u32, int nwaves, int lanes_per_row, void* stream) {
+    if (!in_u32 || !scatter_u32 || !shuffle_u32 || nwaves <= 0 || (lanes_per_row != 8 && lanes_per_row != 16)) return TEAL_ERR_ARG;
+    const uint32_t* in = reinterpret_cast<const uint32_t*>(in_u32);
+    uint32_t* so = reinterpret_cast<uint32_t*>(scatter_u32);
+    uint32_t* sh = reinterpret_cast<uint32_t*>(shuffle_u32);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (lanes_per_row == 8) hipLaunchKernelGGL((row_reduce_probe_kernel<8>), dim3(nwaves), dim3(64), 0, st, in, so, sh);
+    else hipLaunchKernelGGL((row_reduce_probe_kernel<16>), dim3(nwaves), dim3(64), 0, st, in, so, sh);
+    return hipGetLastError() == hipSuccess ? TEAL_OK : TEAL_ERR_LAUNCH;
 }
 #endif  // TEAL_DIAGNOSTICS
 
