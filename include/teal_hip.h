@@ -661,6 +661,48 @@ int teal_sample_rows(const void* logits, size_t logits_stride, int vocab, int dt
 int teal_batched_retire_stops(int32_t* slot_state, const int32_t* tokens, int32_t* pos, const int32_t* history, int history_stride,
                               int32_t* stops, int B, int slot_mask, int max_seq, int count_step, void* stream);
 
+/* ---- constrained decoding, teal_amd/csrc/teal_constrain.hip -------------------------------------------------------------------
+ * Per-request token automata stepped on the device: one launch behind the logit processors (it reads their rows when they are
+ * on) and in front of the samplers (they read its `out`).  Logprobs and dumps go on reading the model's raw logits.
+ * A token automaton has S >= 1 states, state 0 the start.  State s has edges(s): (token, next) pairs, tokens strictly ascending in
+ * 0 .. vocab-1, next in -1 .. S-1; default(s) in -1 .. S-1; accept(s) in {0, 1}.  delta(s, t) = the `next` of the edge that names
+ * t, if there is one, else default(s); t is ALLOWED in s iff delta(s, t) >= 0 (an edge with next = -1 is an exception to a
+ * non-negative default: "anything but these").
+ * Its image, S + edges words of int32 in `arena`: S header rows {edge_begin, edge_end, default, accept} — word offsets relative to
+ * the image, edge_end - edge_begin = 2 * the state's edges — then the edges as (token, next) word pairs.  table: int32 [B][4] =
+ * {base, S, 0, 0}: base the image's word offset in `arena`, or -1: row r is unconstrained.  Any number of rows may share an image.
+ * The rule, for row r with EOS id e = eos[r] (-1: none), about to make draw c = rng_state[r][1] (before the sampler runs), fed
+ * t = tokens[r], the request's latest token:
+ *   1. state    c == 0: s_c = 0.  c > 0: p = trace[r][c-1] & 0x3FFFFFFF, clamped into 0 .. S-1, and
+ *                 t == e:              s_c = p     (the EOS id never moves the automaton: an EOS drawn and ignored below a minimum)
+ *                 delta(p, t) >= 0:    s_c = delta(p, t)
+ *                 else:                s_c = p, with bit 30 (TEAL_CONSTRAIN_VIOLATION) set in the trace word — the fed token was
+ *                                      banned; cannot happen for a token drawn under the mask
+ *               trace[r][c] = s_c (| bit 30).
+ *   2. mask     out[r][v] = logits[r][v], the same 16 bits, if v is allowed in s_c, or if v == e and accept(s_c); every other entry
+ *               becomes -MAXF, the dtype's most negative finite value — never an infinity, as with teal_logit_adjust.  The EOS id is
+ *               banned in a non-accepting state whatever default(s_c) says; edges may not name it.
+ *   3. unconstrained rows (base < 0): out[r] is a bit-for-bit copy of logits[r] (-0, infinities, NaN payloads); trace[r][c] = 0.
+ *   4. inactive rows (active != NULL and bit slot0 + r of active[0] clear) change nothing: `out` row untouched, no trace word.
+ * Guarantee: a banned token enters the samplers' race with weight expf((-MAXF - mx) / T), exactly 0 when the largest allowed logit
+ * mx is above -MAXF / 2 and T <= 100 (fp16: the exponent is then at most about -327; expf reaches 0 near -104), and the row's
+ * maximum is an allowed token with weight 1 — a banned token never wins.  Callers refuse a constrained request with T > 100.
+ * The host validates images (sorted tokens inside the vocabulary, next / default in range, no edge on the EOS id, no dead end);
+ * the device only keeps a damaged image's reads inside `arena`.  The caller's contract: c < trace_len (a counter past it writes no
+ * word and starts from state 0), as for the stop launch's history.
+ * Grid (ceil(vocab / 8192), B), 1024 threads, 16-byte loads and stores.  Every workgroup of a row recomputes s_c (uniform), builds
+ * a bitmap of its 8192 entries in LDS from the state's default and its sub-range of the sorted edges (LDS bit atomics: order does
+ * not matter) and applies it; workgroup x == 0 alone writes trace[r][c].  No workgroup reads a word the launch writes; no
+ * workspace; replays from the same state are bit-identical.
+ * rng_state: uint64 [B][2] = {seed, draw counter} (read only); tokens, eos: int32 [B]; trace: int32 [B][trace_len]; strides in
+ * elements.  The checks of teal_logit_adjust, before any HIP call, and TEAL_ERR_ARG also for trace_len < 1, arena_words == 0 and
+ * an `out` that overlaps `logits`. */
+#define TEAL_CONSTRAIN_VIOLATION (1 << 30)
+#define TEAL_CONSTRAIN_STATE_MASK 0x3FFFFFFF
+int teal_constrain_logits(const void* logits, size_t logits_stride, int vocab, int dtype, int B, const int32_t* tokens,
+                          const void* rng_state, const int32_t* eos, const int32_t* table, const int32_t* arena, size_t arena_words,
+                          int32_t* trace, int trace_len, void* out, size_t out_stride, const int32_t* active, int slot0, void* stream);
+
 /* ---- shared prompt prefixes of continuous batching, teal_amd/csrc/teal_prefix.hip ------------------------------------
  * A prefix is a token sequence whose K / V rows (every layer) are computed once and kept in a device store; a request that names
  * it is admitted by copying those rows into its slot's caches and running a prompt pass over its own tokens only. */

@@ -23,7 +23,7 @@ SOURCES = ("teal_kernels.hip", "teal_attention.hip", "teal_sampler.hip", "teal_g
            "teal_gemv_w8_f16.hip", "teal_gemv_w8_bf16.hip", "teal_gemv_fast_f16.hip", "teal_gemv_fast_bf16.hip", "teal_gemv_int4.hip",
            "teal_gemv_fast_w8_f16.hip", "teal_gemv_fast_w8_bf16.hip", "teal_comparators.hip", "teal_prefill.hip",
            "teal_speculative.hip", "teal_batched.hip", "teal_prefix.hip", "teal_logprob.hip", "teal_logit_adjust.hip",
-           "teal_sample_rows.hip", "teal_stop.hip")
+           "teal_sample_rows.hip", "teal_stop.hip", "teal_constrain.hip")
 # translation units whose kernels take their hot arguments as scalar parameters: the command processor preloads the
 # first 11 dwords into SGPRs at wave launch (no scalar-cache miss before the first activation load)
 PRELOAD = {"teal_gemv_fast_f16.hip": 12, "teal_gemv_fast_bf16.hip": 12, "teal_gemv_fast_w8_f16.hip": 12,
@@ -64,7 +64,7 @@ OPTIONAL_WITH_OVERRIDE = ("teal_decode_attention_split_roped", "teal_prefill_gem
                           "teal_batched_decode_attention", "teal_batched_sparse_gemm_slots", "teal_batched_decode_attention_slots",
                           "teal_batched_retire", "teal_sample_topk_slot", "teal_kv_copy_rows", "teal_decode_attention_split_plan",
                           "teal_token_logprobs", "teal_score_step", "teal_logit_adjust", "teal_sample_rows",
-                          "teal_batched_retire_stops")
+                          "teal_batched_retire_stops", "teal_constrain_logits")
 
 # every symbol include/teal_hip.h declares
 EXPORTS = (
@@ -78,7 +78,7 @@ EXPORTS = (
     "teal_batched_sparse_gemm", "teal_batched_round_rows", "teal_batched_decode_attention_ws_bytes", "teal_batched_decode_attention",
     "teal_batched_sparse_gemm_slots", "teal_batched_decode_attention_slots", "teal_batched_retire", "teal_sample_topk_slot",
     "teal_kv_copy_rows", "teal_decode_attention_split_plan", "teal_token_logprobs", "teal_score_step",
-    "teal_logit_adjust", "teal_sample_rows", "teal_batched_retire_stops",
+    "teal_logit_adjust", "teal_sample_rows", "teal_batched_retire_stops", "teal_constrain_logits",
 )
 
 # what libteal_hip_diag.so exports on top (include/teal_hip.h, #ifdef TEAL_DIAGNOSTICS); libteal_hip.so must export NONE of them
@@ -236,6 +236,8 @@ def _open(path: str, diag: bool) -> ctypes.CDLL:
         L.teal_sample_rows.argtypes = [vp, sz, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, ci, vp]
     if hasattr(L, "teal_batched_retire_stops"):
         L.teal_batched_retire_stops.argtypes = [vp, vp, vp, vp, ci, vp, ci, ci, ci, ci, vp]
+    if hasattr(L, "teal_constrain_logits"):
+        L.teal_constrain_logits.argtypes = [vp, sz, ci, ci, ci, vp, vp, vp, vp, vp, sz, vp, ci, vp, sz, vp, ci, vp]
     for name in EXPORTS + (DIAG_EXPORTS if diag else ()):
         if LIB_OVERRIDE and name in OPTIONAL_WITH_OVERRIDE and not hasattr(L, name):
             continue  # an older build loaded for A/B: callers of this entry point fail with AttributeError when they reach it

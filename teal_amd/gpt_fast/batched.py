@@ -24,6 +24,7 @@ import torch
 
 from .. import _lib, runtime
 from ..kernels.sparse_gemv import BATCH_MAX, batched_segs
+from . import constraints as CN
 from . import logit_processors as PR
 from . import sampling as SM
 from . import stopping as ST
@@ -392,7 +393,8 @@ class SlotDecodeEngine(BatchedDecodeEngine):
     slot-predicated samplers and teal_batched_retire, which counts each active slot's token and switches the slot off on its EOS
     id, its budget or the cache end.  `admit` puts one request into a free slot between replays.  With stop conditions on
     (set_stop_conditions) teal_batched_retire_stops takes the retire launch's place: stop ids, stop sequences, a minimum length
-    and a finish reason per request (stopping.py)."""
+    and a finish reason per request (stopping.py).  With constraints on (set_constraints) one more launch in front of the samplers
+    steps each slot's token automaton and masks the row it draws from (constraints.py)."""
 
     _stops: Optional[ST.StopConditions] = None   # set_stop_conditions
 
@@ -464,6 +466,53 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         if not 0 <= int(slot) < self.B:
             raise ValueError(f"slot {slot} outside 0..{self.B - 1}")
         return self._stop_conditions().read()[int(slot)]
+
+    # ---- constraints -------------------------------------------------------------------------------------------------------
+    def set_constraints(self, on: bool, capacity_words: int = 1 << 20):
+        """off (the default): every step and every admission issues exactly the launches it issues without this feature.  on: one
+        launch between the logit processors (if on) and the samplers steps each slot's token automaton on the token the step was
+        fed and bans, in the row the samplers read, every token the automaton's state does not allow (admit(..., constraint=);
+        slots without one are copied bit for bit).  capacity_words: the arena the registered automata's images share.  Allowed on
+        an idle engine only (a running slot's automaton would start in the middle of its output); drops the captured graphs and
+        every registered constraint."""
+        if int(self.slot_state[SLOT_ACTIVE].item()) != 0:
+            raise RuntimeError("set_constraints needs an idle engine: a slot is active")
+        self._con = CN.Constraints(self.B, self.cfg.vocab_size, self.dtype, self.history.shape[-1], self.history.device,
+                                   capacity_words) if on else None
+        self._graph = None
+
+    def _eos_words(self, row0: int) -> int:
+        return self.slot_state.data_ptr() + 4 * (SLOT_EOS + row0)
+
+    def register_constraint(self, name: str, automaton: CN.Automaton):
+        """the automaton's image into the arena under `name`, for admit(..., constraint=name).  It is checked at this engine's
+        vocabulary here (ValueError with the reason) and against each request's own EOS id at its admission.  Allowed while slots
+        run: the arena's free blocks are no running slot's."""
+        con = self._constraints()
+        if not isinstance(automaton, CN.Automaton):
+            raise ValueError(f"register_constraint takes an Automaton, got {type(automaton).__name__}")
+        automaton.check(self.cfg.vocab_size, None, eos_known=False)
+        con.register(name, automaton)
+
+    def drop_constraint(self, name: str):
+        """frees the image; refused (RuntimeError) while a running slot names it"""
+        con = self._constraints()
+        state = int(self.slot_state[SLOT_ACTIVE].item())
+        for s, n in enumerate(con.row_names):  # a finished slot's row still names its last constraint: it lets go here
+            if n == name and not (state >> s) & 1:
+                con.set_row(s, None)
+        torch.cuda.current_stream().synchronize()  # (a launch that reads the image may still be in flight)
+        con.drop(name)
+
+    def has_constraint(self, name: str) -> bool:
+        return self._con is not None and name in self._con.images
+
+    def read_constraint_trace(self, slot: int, n: int) -> List[int]:
+        """the automaton states draws 0 .. n-1 of the request in `slot` were made in (bit 30 set: the fed token was banned —
+        cannot happen for tokens drawn under the mask); all 0 for an unconstrained request"""
+        if not 0 <= int(slot) < self.B:
+            raise ValueError(f"slot {slot} outside 0..{self.B - 1}")
+        return self._constraints().read_trace(slot, n)
 
     # ---- admission ---------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -571,7 +620,7 @@ class SlotDecodeEngine(BatchedDecodeEngine):
     def admit(self, slot: int, tokens, budget: int, eos_id: Optional[int], seed: int, temperature: float = 0.8,
               top_k: Optional[int] = 200, prefix: Optional[str] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
               frequency_penalty: float = 0.0, logit_bias: Optional[Dict] = None, top_p: float = 1.0, min_p: float = 0.0,
-              stop_token_ids=(), stop_sequences=(), min_new_tokens: int = 0):
+              stop_token_ids=(), stop_sequences=(), min_new_tokens: int = 0, constraint: Optional[str] = None):
         """Request -> slot `slot` (free): the dense prompt pass into that slot's caches, the first token drawn from the last row's
         logits (draw 0 of the stream `seed`), the slot's token, position, history, rng state, budget and EOS set on the device and
         its bit set.  A request whose first token ends it (budget 1, EOS) is switched off again by the same retire rule.
@@ -585,7 +634,10 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         request; off, `temperature` and `top_k` are those of this first draw only (run_steps has its own).
         stop_token_ids / stop_sequences / min_new_tokens: the request's stop conditions (they need set_stop_conditions(True)): up
         to 16 ids, up to 8 sequences of up to 8 token ids, matched against the tokens it generates — never its prompt or prefix;
-        neither they nor `eos_id` end it before min_new_tokens tokens.  The stopping tokens stay in its output."""
+        neither they nor `eos_id` end it before min_new_tokens tokens.  The stopping tokens stay in its output.
+        constraint: a registered constraint's name (it needs set_constraints(True)) — every token of the request, the first
+        included, is drawn from the tokens its automaton allows, and `eos_id` only in an accepting state.  The automaton is checked
+        against this request's `eos_id` here; a temperature above 100 is refused (a banned token's weight must be exactly 0)."""
         s, B = int(slot), self.B
         prompt = torch.as_tensor(tokens, dtype=torch.int32).view(-1).to(self.logits.device)
         T = int(prompt.numel())
@@ -606,6 +658,15 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         stops = ST.check_stops(self.cfg.vocab_size, stop_token_ids, stop_sequences, min_new_tokens)
         if self._stops is None and not ST.is_default(stops):
             raise RuntimeError("stop conditions are off (set_stop_conditions)")
+        if constraint is not None:
+            if self._con is None:
+                raise RuntimeError("constraints are off (set_constraints)")
+            self._con.automaton(constraint).check(self.cfg.vocab_size, eos_id)
+            if float(temperature) > CN.MAX_TEMPERATURE:
+                raise ValueError(f"a constrained request needs temperature <= {CN.MAX_TEMPERATURE:g} (above it a banned token's weight "
+                                 f"is no longer exactly 0), got {temperature}")
+        if self._con is not None:  # (every admission: the slot's next occupant never inherits a constraint)
+            self._con.set_row(s, constraint)
         if self._samp is not None:  # (every admission: the slot's last request left its settings)
             self._samp.set_row(s, temperature, top_k, top_p, min_p)
         elif SM.check_sampling(top_p=top_p, min_p=min_p)["top_p"] < 1.0 or min_p > 0.0:

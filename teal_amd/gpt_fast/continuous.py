@@ -19,6 +19,10 @@ not depend on what happened to be cached when it was admitted.
 Stop conditions: a request may carry stop token ids, stop sequences of token ids and a minimum length (stopping.py).  They are
 matched on the device inside the step, so a request ends on the very step its stop appears whatever sync_every is, and the result
 says why each request ended ("finish_reason") and what matched ("stop_match").
+
+Constraints: a request may follow a token automaton (constraints.py) — a registered one by name, one of a list of `choices`, or any
+sequence over `allowed_token_ids`.  The automaton advances on the device inside the step, so every token is drawn under it whatever
+sync_every is; the match is on token ids, not text.
 """
 from __future__ import annotations
 
@@ -30,6 +34,7 @@ from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
 
 from .batched import SLOT_ACTIVE, SLOT_FINISH, SLOT_PRODUCED, SLOT_STEP
+from .constraints import MAX_TEMPERATURE, Automaton
 from .logit_processors import fp32
 from .stopping import MAX_IDS, MAX_SEQ_LEN, MAX_SEQS
 
@@ -63,6 +68,29 @@ class Request:
     stop_token_ids: Optional[List[int]] = None
     stop_sequences: Optional[List[List[int]]] = None
     min_new_tokens: Optional[int] = None
+    # constrained decoding, at most one of the three: the id of a registered automaton; token-id lists of which the request produces
+    # exactly one, then its EOS id (it needs one); token ids the request draws all its tokens from
+    constraint: Optional[str] = None
+    choices: Optional[List[List[int]]] = None
+    allowed_token_ids: Optional[List[int]] = None
+
+    def __post_init__(self):
+        if sum(v is not None for v in (self.constraint, self.choices, self.allowed_token_ids)) > 1:
+            raise ValueError("a request takes at most one of constraint, choices and allowed_token_ids")
+
+    def constraint_spec(self):
+        """None, or (name, automaton): the automaton built from `choices` / `allowed_token_ids` under a name made of its content
+        (equal lists share one image), or (constraint, None) for a registered one"""
+        if self.constraint is not None:
+            return self.constraint, None
+        if self.choices is not None:
+            Automaton.from_choices(self.choices)  # (refuses what is no list of token id lists)
+            canon = sorted({tuple(c) for c in self.choices})  # the set decides, not the order or a repeat
+            return "choices:" + json.dumps(canon, separators=(",", ":")), Automaton.from_choices(canon)
+        if self.allowed_token_ids is not None:
+            a = Automaton.from_allowed(self.allowed_token_ids)
+            return "allowed:" + json.dumps([t for t, _ in a.states[0]["edges"]], separators=(",", ":")), a
+        return None
 
     def stops(self, defaults: Optional[Dict] = None) -> Dict:
         """the stop conditions that differ from "none" — the keyword arguments of the engine's admit; {}: the request asks for none"""
@@ -197,6 +225,76 @@ def parse_stops(d: dict, where: str, tokenizer=None) -> Dict:
     return out
 
 
+def parse_constraint_fields(d: dict, where: str, tokenizer=None, constraints: Optional[Dict] = None) -> Dict:
+    """the constraint fields of one request object, validated; only the one present.  "choices" strings are each encoded alone,
+    WITHOUT a BOS (needs a tokenizer) — the match stays on token ids, with the caveat of "stop" strings."""
+    kinds = [k for k in ("constraint", "choices", "allowed_token_ids") if k in d]
+    if len(kinds) > 1:
+        raise ValueError(f"{where}: at most one of \"constraint\", \"choices\" and \"allowed_token_ids\", got " + " and ".join(f'"{k}"' for k in kinds))
+
+    def ids(v):
+        return isinstance(v, list) and bool(v) and all(isinstance(t, int) and not isinstance(t, bool) and t >= 0 for t in v)
+    if "constraint" in d:
+        c = d["constraint"]
+        if not isinstance(c, str) or c not in (constraints or {}):
+            raise ValueError(f"{where}: unknown constraint {c!r}" + ("" if constraints else " (no constraints were given)"))
+        return {"constraint": c}
+    if "choices" in d:
+        v = d["choices"]
+        if not isinstance(v, list) or not v or not (all(ids(q) for q in v) or all(isinstance(q, str) and q for q in v)):
+            raise ValueError(f"{where}: \"choices\" must be a non-empty list of non-empty token id lists, or of non-empty strings")
+        if isinstance(v[0], str):
+            if tokenizer is None:
+                raise ValueError(f"{where}: \"choices\" strings need a tokenizer (a checkpoint), not --synthetic: give lists of token ids")
+            enc = []
+            for x in v:
+                q = [int(t) for t in tokenizer.encode(x)]
+                if not q:
+                    raise ValueError(f"{where}: the \"choices\" string {x!r} encodes to no tokens")
+                enc.append(q)
+            v = enc
+        return {"choices": [[int(t) for t in q] for q in v]}
+    if "allowed_token_ids" in d:
+        if not ids(d["allowed_token_ids"]):
+            raise ValueError(f"{where}: \"allowed_token_ids\" must be a non-empty list of token ids")
+        return {"allowed_token_ids": [int(t) for t in d["allowed_token_ids"]]}
+    return {}
+
+
+def parse_constraints(lines: Sequence[str]) -> Dict[str, Automaton]:
+    """JSON Lines, one token automaton per line: {"id": "yes-no", "states": [{"edges": [[token, next], ...], "default": -1,
+    "accept": true}, ...]} (state 0 is the start).  Blank lines are skipped; an empty file is an empty mapping."""
+    out: Dict[str, Automaton] = {}
+    for i, line in enumerate(lines):
+        if not line.strip():
+            continue
+        try:
+            d = json.loads(line)
+        except json.JSONDecodeError as e:
+            raise ValueError(f"constraint line {i + 1}: not JSON ({e})") from None
+        if not isinstance(d, dict) or not isinstance(d.get("id"), str) or not d["id"]:
+            raise ValueError(f"constraint line {i + 1}: needs an \"id\" (a non-empty string)")
+        if d["id"] in out:
+            raise ValueError(f"constraint line {i + 1}: duplicate id {d['id']!r}")
+        try:
+            out[d["id"]] = Automaton.from_json(d)
+        except ValueError as e:
+            raise ValueError(f"constraint line {i + 1}: {e}") from None
+    return out
+
+
+def check_constraint_ids(request_lines: Sequence[str], constraints: Dict) -> None:
+    """every "constraint" a request line names is an id of `constraints` — needs no tokenizer, so it runs before anything is loaded
+    (malformed lines are left to parse_requests, which names them)"""
+    for i, line in enumerate(request_lines):
+        try:
+            d = json.loads(line) if line.strip() else None
+        except json.JSONDecodeError:
+            d = None
+        if isinstance(d, dict) and d.get("constraint") is not None and d["constraint"] not in constraints:
+            raise ValueError(f"request line {i + 1}: unknown constraint {d['constraint']!r}")
+
+
 def parse_prefixes(lines: Sequence[str], tokenizer=None) -> Dict[str, List[int]]:
     """JSON Lines, one shared prefix per line: {"id": "sys", "tokens": [...]} or {"id": "sys", "prompt": "..."} (needs a tokenizer;
     BOS prepended as for prompts).  Blank lines are skipped; an empty file is an empty mapping."""
@@ -246,7 +344,7 @@ def check_prefix_ids(request_lines: Sequence[str], prefix_lines: Sequence[str]) 
 
 
 def parse_requests(lines: Sequence[str], default_max_new_tokens: int, tokenizer=None, eos_id: Optional[int] = None,
-                   prefixes: Optional[Dict[str, List[int]]] = None) -> List[Request]:
+                   prefixes: Optional[Dict[str, List[int]]] = None, constraints: Optional[Dict[str, Automaton]] = None) -> List[Request]:
     """JSON Lines, one request per line: {"tokens": [...]} or {"prompt": "..."} (needs a tokenizer; BOS prepended as generate.py
     does), with an optional "max_new_tokens" (default: `default_max_new_tokens`).  Blank lines are skipped.  A line may carry
     "prefix": an id of `prefixes`; its tokens / prompt are then the suffix, and a prompt is encoded WITHOUT a BOS (the prefix
@@ -255,7 +353,9 @@ def parse_requests(lines: Sequence[str], default_max_new_tokens: int, tokenizer=
     "min_p" (in [0, 1); 0: off), and its own "seed".  A line may carry its own stop conditions: "stop_token_ids" (at most 16),
     "stop_sequences" (at most 8 lists of 1..8 token ids), "min_new_tokens" and, with a tokenizer, "stop": strings, each encoded
     WITHOUT a BOS into one more stop sequence.  The match is on token ids against the tokens the request generates: a string the
-    model spells with other tokens (another split, a leading-space variant) is not caught."""
+    model spells with other tokens (another split, a leading-space variant) is not caught.  A line may carry ONE constraint:
+    "constraint" (an id of `constraints`), "choices" (token id lists, or strings — each encoded alone WITHOUT a BOS, with the same
+    caveat; the request produces exactly one of them and then the EOS id, so it needs `eos_id`) or "allowed_token_ids"."""
     out = []
     for i, line in enumerate(lines):
         if not line.strip():
@@ -282,8 +382,12 @@ def parse_requests(lines: Sequence[str], default_max_new_tokens: int, tokenizer=
         n = d.get("max_new_tokens", default_max_new_tokens)
         if not isinstance(n, int) or n < 1:
             raise ValueError(f"request line {i + 1}: \"max_new_tokens\" must be a positive integer")
+        con = parse_constraint_fields(d, f"request line {i + 1}", tokenizer, constraints)
+        if "choices" in con and eos_id is None:
+            raise ValueError(f"request line {i + 1}: \"choices\" needs an EOS id (--eos_id): a finished choice ends on it, and without "
+                             "one its last state is a dead end")
         out.append(Request([int(t) for t in toks], n, eos_id, prefix=pid, **parse_controls(d, f"request line {i + 1}"),
-                           **parse_sampling(d, f"request line {i + 1}"), **parse_stops(d, f"request line {i + 1}", tokenizer)))
+                           **parse_sampling(d, f"request line {i + 1}"), **parse_stops(d, f"request line {i + 1}", tokenizer), **con))
     if not out:
         raise ValueError("no requests")
     return out
@@ -333,13 +437,17 @@ class ContinuousBatcher:
     set_stop_conditions(True), called once before the first admission, admit(..., stop_token_ids=, stop_sequences=,
     min_new_tokens=) — only requests that ask for one are admitted with those keywords — and read_finish(slot) -> (reason, match);
     the result gains "finish_reason" ("stop_token" / "stop_sequence" / "length" / "cache" per request, in input order) and
-    "stop_match" (the token id, the sequence's index, or -1).  "tokens" stays every token drawn, the stopping ones included."""
+    "stop_match" (the token id, the sequence's index, or -1).  "tokens" stays every token drawn, the stopping ones included.
+    Constraints: `constraints` (id -> Automaton) are what requests may name.  Exactly when some request carries a constraint, choices
+    or allowed_token_ids the engine also offers set_constraints(True), called once before the first admission, has_constraint(id),
+    register_constraint(id, automaton) — one per distinct content — and admit(..., constraint=id); only those requests are admitted
+    with the keyword."""
 
     def __init__(self, engine, sync_every: int = 8, refill: str = "free", temperature: float = 0.8, top_k: Optional[int] = 200,
                  seed: int = 1234, use_graph: bool = True, prefixes: Optional[Dict[str, List[int]]] = None,
                  logprobs: Optional[int] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                  frequency_penalty: float = 0.0, top_p: float = 1.0, min_p: float = 0.0, stop_token_ids=(), min_new_tokens: int = 0,
-                 finish_reason: bool = False):
+                 finish_reason: bool = False, constraints: Optional[Dict[str, Automaton]] = None):
         if refill not in REFILL:
             raise ValueError(f"refill must be one of {REFILL}")
         if int(sync_every) < 1:
@@ -357,6 +465,7 @@ class ContinuousBatcher:
         self.top_p, self.min_p, self._sampling_set = float(top_p), float(min_p), False
         self.stop_defaults = parse_stops({"stop_token_ids": list(stop_token_ids or ()), "min_new_tokens": min_new_tokens}, "ContinuousBatcher")
         self.finish_reason, self._stops_set = bool(finish_reason), False
+        self.constraints, self._constraints_set = dict(constraints or {}), False
 
     def _clock(self):
         try:
@@ -402,6 +511,34 @@ class ContinuousBatcher:
         if (self.finish_reason or any(stops)) and not self._stops_set:  # once: it drops the engine's captured step
             eng.set_stop_conditions(True)
             self._stops_set = True
+        cons: List[Optional[str]] = [None] * len(requests)
+        automata: Dict[str, Automaton] = {}
+        for i, r in enumerate(requests):  # refused before anything runs
+            spec = r.constraint_spec() if hasattr(r, "constraint_spec") else None
+            if spec is None:
+                continue
+            name, a = spec
+            if a is None:
+                if name not in self.constraints:
+                    raise ValueError(f"request {i}: unknown constraint {name!r}")
+                a = self.constraints[name]
+            if r.choices is not None and r.eos_id is None:
+                raise ValueError(f"request {i}: choices need an EOS id: a finished choice ends on it")
+            try:
+                a.check(eng.cfg.vocab_size, r.eos_id)
+            except ValueError as e:
+                raise ValueError(f"request {i}: {e}") from None
+            T = sampling[i]["temperature"] if self._sampling_set else self.temperature
+            if float(T) > MAX_TEMPERATURE:
+                raise ValueError(f"request {i}: a constrained request needs temperature <= {MAX_TEMPERATURE:g}, got {T}")
+            cons[i], automata[name] = name, a
+        if automata:
+            if not self._constraints_set:  # once: it drops the engine's captured step
+                eng.set_constraints(True)
+                self._constraints_set = True
+            for name, a in automata.items():
+                if not eng.has_constraint(name):
+                    eng.register_constraint(name, a)
         reasons: List[Optional[str]] = [None] * len(requests)
         matches: List[int] = [-1] * len(requests)
         pending = deque(range(len(requests)))
@@ -433,6 +570,8 @@ class ContinuousBatcher:
                         kw.update(top_p=sampling[r]["top_p"], min_p=sampling[r]["min_p"])
                     if self._stops_set:
                         kw.update(stops[r])
+                    if cons[r] is not None:
+                        kw["constraint"] = cons[r]
                     eng.admit(s, q.tokens, q.max_new_tokens, q.eos_id, self.seed + r if q.seed is None else q.seed, T, k, **kw)
                     prefix_admissions += 1 if plen[r] else 0
                     prefix_rows += plen[r]

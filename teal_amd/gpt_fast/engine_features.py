@@ -1,6 +1,6 @@
 """What the fused engines share on the host side: the model's linears and the pointers a captured pass holds, the checks
-every dense-chain engine starts `supports` with, and the sampler-side features (token logprobs, logit processors, per-request
-sampling) of the decode engines with the one launch sequence that draws a token under them.  A new per-request feature of the
+every dense-chain engine starts `supports` with, and the sampler-side features (token logprobs, logit processors, constraints,
+per-request sampling) of the decode engines with the one launch sequence that draws a token under them.  A new per-request feature of the
 sampler goes into `SamplerFeatures` only.
 """
 from __future__ import annotations
@@ -10,6 +10,7 @@ from typing import Dict, Optional
 import torch
 
 from ..monkeypatch import UP_SHIFT_BYTES, to_column_major
+from . import constraints as CN
 from . import logit_processors as PR
 from . import logprobs as LP
 from . import sampling as SM
@@ -79,13 +80,15 @@ class _SlotCaches:
 
 class SamplerFeatures:
     """Token logprobs (logprobs.py: one launch behind the sampler), per-request logit processors (logit_processors.py: one
-    launch in front of it) and per-request sampling (sampling.py: one launch in the samplers' place), all off until switched on,
+    launch in front of it), constraints (constraints.py: one launch between the two, on a slot engine) and per-request sampling
+    (sampling.py: one launch in the samplers' place), all off until switched on,
     and `_draw`, the launches of a draw under them.  The host class provides `_feature_rows` (its sequences), `history` (int32
     [..., length]: a logprob row is as long), `cfg.vocab_size`, `dtype`, `code`, a `_graph` the setters drop and `_sample_row`."""
 
     _lp: Optional[LP.LogprobBuffers] = None      # set_logprobs
     _proc: Optional[PR.LogitProcessors] = None   # set_logit_processors
     _samp: Optional[SM.SamplingParams] = None    # set_sampling_params
+    _con: Optional[CN.Constraints] = None        # set_constraints (a slot engine's)
     _active: Optional[int] = None                # the address of a slot engine's active word: its launches are predicated on it
 
     def _feature_refusal(self, what: str) -> None:
@@ -154,6 +157,22 @@ class SamplerFeatures:
     sampling_params = property(lambda self: None if self._samp is None else self._samp.params)
     sampling_kept = property(lambda self: None if self._samp is None else self._samp.kept)
 
+    def set_constraints(self, on: bool, capacity_words: int = 1 << 20):
+        """constrained decoding belongs to the slot engine: an automaton starts over at an admission and opens the request's EOS id,
+        and this engine has neither — switching it on is refused with that reason (off is what it is)"""
+        if on:
+            raise NotImplementedError(f"{type(self).__name__} has no constrained decoding: a constraint starts at an admission and ends on "
+                                      "the request's EOS word, which only SlotDecodeEngine has")
+
+    def _constraints(self) -> CN.Constraints:
+        if self._con is None:
+            raise RuntimeError("constraints are off (set_constraints)")
+        return self._con
+
+    def _eos_words(self, row0: int) -> int:
+        """the address of sequence row0's EOS word (int32, one per sequence): the constrain launch's `eos`"""
+        raise NotImplementedError
+
     def _step_key(self, temperature, top_k):
         """the sampler's share of a captured step's key: the two scalars baked into the fused top-k sampler's launches, or —
         per-request sampling on — nothing, the rows being read on the device"""
@@ -174,7 +193,7 @@ class SamplerFeatures:
               pos: Optional[torch.Tensor], history: Optional[torch.Tensor], count_token: bool, row0: int = 0,
               fed: Optional[torch.Tensor] = None, st=None):
         """Sequences row0 .. row0+rows-1 draw their next token from `logits` (rows `stride` elements apart; 0: the one row as it
-        stands): the processors' launch (if on), then ONE sampling launch over the rows or the fused top-k sampler row by row,
+        stands): the processors' launch (if on), the constrain launch (if on) over what they left, then ONE sampling launch over the rows or the fused top-k sampler row by row,
         then the logprob launch (if on) over the logits as the model gave them.  rng_state / tokens / pos / history are the first
         row's; pos and history None: the draw feeds no loop state.  count_token: the processors first count each row's token in
         `fed` (default `tokens`: the buffer the step was fed from) as generated."""
@@ -182,6 +201,10 @@ class SamplerFeatures:
         if self._proc is not None:
             self._proc.launch(logits, stride, rows, tokens if fed is None else fed, count_token, row0=row0, active=active, st=st)
             src = self._proc.adj[row0:row0 + rows] if stride else self._proc.adj[row0]
+        if self._con is not None:  # each row's automaton moves on the token it was fed, then masks the row the samplers read
+            self._con.launch(src, stride, rows, tokens if fed is None else fed, rng_state, self._eos_words(row0), row0=row0, active=active,
+                             st=st)
+            src = self._con.con[row0:row0 + rows] if stride else self._con.con[row0]
         if self._samp is not None:  # one launch, every row under its own settings
             self._samp.launch(src, stride, rows, rng_state, tokens, pos, history, self.history.shape[-1], row0=row0, active=active, st=st)
         else:
@@ -194,8 +217,10 @@ class SamplerFeatures:
         """the features' share of what a captured step carries from replay to replay"""
         return (list(self._lp.tensors()) if self._lp is not None else []) + \
                (list(self._proc.loop_tensors()) if self._proc is not None else []) + \
-               (list(self._samp.loop_tensors()) if self._samp is not None else [])
+               (list(self._samp.loop_tensors()) if self._samp is not None else []) + \
+               (list(self._con.loop_tensors()) if self._con is not None else [])
 
     def _feature_key(self):
-        """the features' share of a captured step's key (per-request sampling adds its word only while it is on)"""
-        return (None if self._lp is None else self._lp.top_n, self._proc is not None) + (("sampling",) if self._samp is not None else ())
+        """the features' share of a captured step's key (per-request sampling and constraints add their word only while on)"""
+        return (None if self._lp is None else self._lp.top_n, self._proc is not None) + (("sampling",) if self._samp is not None else ()) + \
+               (("constraints",) if self._con is not None else ())

@@ -849,8 +849,20 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer) -> Dict:
     """--requests FILE through ContinuousBatcher on a SlotDecodeEngine of --batch_size slots (one hipGraph replay per step under
     --compile, with one warm-up run first)"""
     from teal_amd.gpt_fast.batched import SlotDecodeEngine
-    from teal_amd.gpt_fast.continuous import ContinuousBatcher, cache_rows, parse_prefixes, parse_requests
+    from teal_amd.gpt_fast.continuous import ContinuousBatcher, cache_rows, parse_constraints, parse_prefixes, parse_requests
     B = int(args.batch_size)
+    constraints = {}
+    if getattr(args, "constraints", None) is not None:
+        try:
+            with open(args.constraints) as f:
+                constraints = parse_constraints(f.read().splitlines())
+            for name, a in constraints.items():  # a token outside this model's vocabulary: refused before anything runs
+                try:
+                    a.check(model.config.vocab_size, args.eos_id, eos_known=args.eos_id is not None)
+                except ValueError as e:
+                    raise ValueError(f"constraint {name!r}: {e}") from None
+        except (OSError, ValueError) as e:
+            raise SystemExit(f"--constraints: {e}")
     prefixes = {}
     if getattr(args, "prefixes", None) is not None:
         try:
@@ -860,7 +872,8 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer) -> Dict:
             raise SystemExit(f"--prefixes: {e}")
     try:
         with open(args.requests) as f:
-            reqs = parse_requests(f.read().splitlines(), args.max_new_tokens, tokenizer, args.eos_id, prefixes=prefixes)
+            reqs = parse_requests(f.read().splitlines(), args.max_new_tokens, tokenizer, args.eos_id, prefixes=prefixes,
+                                  constraints=constraints)
         max_seq = cache_rows(reqs, model.config.block_size, prefixes)
         if prefixes:  # (a prefix no request names is registered too: it needs room for a one-token suffix)
             max_seq = max(max_seq, min(max(len(t) for t in prefixes.values()) + 2, model.config.block_size))
@@ -879,7 +892,8 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer) -> Dict:
     eng = SlotDecodeEngine(model, thresholds, B)
     batcher = ContinuousBatcher(eng, sync_every=args.sync_every, temperature=args.temperature, top_k=args.top_k, seed=1234,
                                 use_graph=bool(args.compile), prefixes=prefixes, logprobs=getattr(args, "logprobs", None),
-                                **check_processor_args(args), **check_sampling_args(args), **check_stop_args(args))
+                                **check_processor_args(args), **check_sampling_args(args), **check_stop_args(args),
+                                **({"constraints": constraints} if constraints else {}))
     try:
         for name, toks in prefixes.items():  # once, before the warm-up run
             eng.register_prefix(name, toks)
@@ -933,8 +947,18 @@ def main(args) -> Dict:
     check_stop_args(args)
     if getattr(args, "prefixes", None) is not None and getattr(args, "requests", None) is None:
         raise SystemExit("--prefixes names shared prefixes of continuous batching: it needs --requests")
+    if getattr(args, "constraints", None) is not None and getattr(args, "requests", None) is None:
+        raise SystemExit("--constraints names token automata of continuous batching: it needs --requests (an automaton starts at an "
+                         "admission and ends on the request's EOS id)")
     if getattr(args, "requests", None) is not None:
         check_requests_args(args)
+        from teal_amd.gpt_fast.continuous import check_constraint_ids, parse_constraints
+        try:  # a malformed automaton, or a request on a constraint nobody defined: refused before anything is loaded, too
+            cf = getattr(args, "constraints", None)
+            check_constraint_ids(Path(args.requests).read_text().splitlines(),
+                                 parse_constraints(Path(cf).read_text().splitlines()) if cf is not None else {})
+        except (OSError, ValueError) as e:
+            raise SystemExit(f"--constraints: {e}" if cf is not None else f"--requests: {e}")
         from teal_amd.gpt_fast.continuous import check_prefix_ids
         try:  # a request on a prefix nobody defined: refused before anything is loaded, too
             pf = getattr(args, "prefixes", None)
@@ -1139,6 +1163,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--prefixes", type=Path, default=None, help="with --requests: a JSON Lines file of shared prefixes, one per line "
                    "({\"id\": \"sys\", \"tokens\": [...]} or {\"id\": \"sys\", \"prompt\": \"...\"}); a request line that carries "
                    "\"prefix\": \"sys\" gives only its own suffix and reuses the prefix's K / V rows, computed once")
+    p.add_argument("--constraints", type=Path, default=None, help="with --requests: a JSON Lines file of token automata, one per line "
+                   "({\"id\": \"yes-no\", \"states\": [{\"edges\": [[token, next], ...], \"default\": -1, \"accept\": true}, ...]}, state 0 "
+                   "the start); a request line that carries \"constraint\": \"yes-no\" draws every token under it.  Request lines "
+                   "may also carry \"choices\" or \"allowed_token_ids\" without this file")
     p.add_argument("--eos_id", type=int, default=None, help="with --requests: a request also ends right after this token id (off "
                    "by default: budgets alone end requests)")
     p.add_argument("--logprobs", type=int, default=None, help="return each generated token's log-probability under the model's own "
