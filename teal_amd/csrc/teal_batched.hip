@@ -3,7 +3,7 @@
 // TEAL's rule is per token: sequence b's projection is W . (x_b (.) [|x_b| > tau]) (the reference's SparsifyFn masks every
 // token's activations element-wise against the site's threshold).  One step of B sequences therefore needs every weight row
 // that ANY of them keeps — the union — read once, and each sequence adds only its own kept rows.  The layer is the prompt
-// pass's chain over the same transposed hand-over layout [feature][8] (teal_prefill.hip), with two launches of its own:
+// pass's chain over the same transposed hand-over layout [feature][8] (teal_slab.h), with two launches of its own:
 //
 //   batched_gemm_kernel       the prompt pass's GEMM (256-column tiles, row groups dealt to slices, the slice's activation rows
 //                             staged in LDS once, one broadcast LDS read per row for the 8 sequences) plus one step after the
@@ -15,17 +15,12 @@
 //                             dimension), then batched_merge_kernel.
 //
 // Rounding points are the module path's (16-bit projection outputs, RoPE, attention output); sums are fp32.
-#include "teal_common.h"
-
-#include <limits.h>
+#include "teal_slab.h"
 
 namespace teal {
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kBatchMax = 8;           // sequences per launch: one 16-byte word of 16-bit activations per feature
-constexpr int kBMaxSplit = 16;
 constexpr int kBPhaseRows = 2048;      // rows a workgroup stages per phase (128 groups of 16)
 constexpr int kBChunks = kBPhaseRows / 64;
 constexpr int kBCountStride = 9;       // counts[slice][segment][9]: kept per sequence (0 .. 7), union (8)
@@ -33,55 +28,15 @@ constexpr int kBAttnChunk = 32;        // context rows a workgroup stages per ro
 constexpr int kBAttnMaxQ = 16;         // query heads of one KV head per workgroup
 constexpr int kBAttnMaxSplit = 64;
 
-struct BProd {
-    const uint16_t* xt;      // PROD 0: [Z][8];  PROD 1: the residual rows ht [Z][8]
-    const float* sumsq;      // PROD 1: [nwg][8]
-    const uint16_t* norm_w;  // PROD 1: [Z]
-    const float* gu;         // PROD 2: slabs [gu_split][2 Z][8] of the gate | up launch
-    float eps;
-    int nwg, gu_split, B;
-};
-
 struct BSegs {
     int nseg;
     int end[3];   // exclusive end column of each segment over [0, n_total)
     float tau[3];
 };
 
-// sum of `split` slabs [slice][n_total][8] of one column in slice order, rounded once to the activation dtype
-template <bool BF16>
-__device__ __forceinline__ void b_rounded_row(const float* __restrict__ slabs, const int split, const size_t n_total, const size_t col,
-                                              float (&out)[8]) {
-    f32x4 a0 = (f32x4){0.f, 0.f, 0.f, 0.f}, a1 = a0;
-    for (int s = 0; s < split; ++s) {
-        const float* p = slabs + ((size_t)s * n_total + col) * 8;
-        a0 += *reinterpret_cast<const f32x4*>(p);
-        a1 += *reinterpret_cast<const f32x4*>(p + 4);
-    }
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        out[s] = bits_to_float(float_to_bits<BF16>(a0[s]), BF16);
-        out[4 + s] = bits_to_float(float_to_bits<BF16>(a1[s]), BF16);
-    }
-}
-
-template <bool BF16>
-__device__ __forceinline__ u32x4 b_pack_row(const float (&v)[8]) {
-    u32x4 r;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) r[j] = (uint32_t)float_to_bits<BF16>(v[2 * j]) | ((uint32_t)float_to_bits<BF16>(v[2 * j + 1]) << 16);
-    return r;
-}
-
-template <bool BF16>
-__device__ __forceinline__ void b_unpack_row(const u32x4 v, float (&x)[8]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { x[2 * j] = bits_to_float(v[j] & 0xFFFFu, BF16); x[2 * j + 1] = bits_to_float(v[j] >> 16, BF16); }
-}
-
 // ------------------------------------------------------------------------------------------------
 // slabs[slice][n][8] (fp32) = sum over the slice's rows m with float32(|x_b[m]|) > tau_seg of W^T[m][n] * x_b[m], sequences b < B.
-//   grid (256-column tiles, row slices); rows in groups of 16, group q belongs to slice q mod split (teal_prefill.hip's layout).
+//   grid (256-column tiles, row slices); rows in groups of 16, group q belongs to slice q mod split (the layout of teal_slab.h).
 // Per phase (<= 2048 rows of the slice): stage the rows' 8 activations in LDS, each with a keep mask (bit 8 * ls + b: sequence b
 // keeps the row under the threshold of the tile's ls-th segment), then compact the rows with a non-zero mask — the union of the
 // tile — into a list in row order (chunks of 64 rows: one ballot each, a prefix sum over the chunk counts).  Wave w streams list
@@ -94,7 +49,7 @@ __device__ __forceinline__ void b_unpack_row(const u32x4 v, float (&x)[8]) {
 // kept, so it adds nothing to the union, the counts or any slab (its own columns are exactly 0).  SLOTS = false is the code of
 // teal_batched_sparse_gemm.
 template <bool BF16, int NP, int PROD, bool SLOTS>
-__global__ __launch_bounds__(1024) void batched_gemm_kernel(const BProd pr, const BSegs sg, const uint16_t* __restrict__ w0, const int ld0,
+__global__ __launch_bounds__(1024) void batched_gemm_kernel(const SlabProd pr, const BSegs sg, const uint16_t* __restrict__ w0, const int ld0,
                                                             const uint16_t* __restrict__ w1, const int ld1, const int tiles0,
                                                             float* __restrict__ slabs, int* __restrict__ counts, const int Z, const int n_total,
                                                             const int* __restrict__ active) {
@@ -181,10 +136,10 @@ __global__ __launch_bounds__(1024) void batched_gemm_kernel(const BProd pr, cons
             const uint32_t m = (uint32_t)(slice + split * (jb + (r >> 4))) * 16u + (uint32_t)(r & 15);
             float x[8];
             if constexpr (PROD == 0) {
-                b_unpack_row<BF16>(*reinterpret_cast<const u32x4*>(pr.xt + (size_t)m * 8), x);
+                unpack_row<BF16>(*reinterpret_cast<const u32x4*>(pr.xt + (size_t)m * 8), x);
             } else if constexpr (PROD == 1) {  // x = round(round(h * rstd) * w)  (gpt-fast/model.py:289-291)
                 const float nw = bits_to_float(pr.norm_w[m], BF16);
-                b_unpack_row<BF16>(*reinterpret_cast<const u32x4*>(pr.xt + (size_t)m * 8), x);
+                unpack_row<BF16>(*reinterpret_cast<const u32x4*>(pr.xt + (size_t)m * 8), x);
 #pragma unroll
                 for (int s = 0; s < 8; ++s) {
                     const float xn = bits_to_float(float_to_bits<BF16>(x[s] * rstd[s]), BF16);
@@ -192,8 +147,8 @@ __global__ __launch_bounds__(1024) void batched_gemm_kernel(const BProd pr, cons
                 }
             } else {  // x = round(round(silu(round(gate))) * round(up))  (gpt-fast/model.py:258-259)
                 float gv[8], uv[8];
-                b_rounded_row<BF16>(pr.gu, pr.gu_split, (size_t)2 * Z, (size_t)m, gv);
-                b_rounded_row<BF16>(pr.gu, pr.gu_split, (size_t)2 * Z, (size_t)Z + m, uv);
+                slab_column<BF16, 8>(pr.gu, pr.gu_split, (size_t)2 * Z, (size_t)m, gv);
+                slab_column<BF16, 8>(pr.gu, pr.gu_split, (size_t)2 * Z, (size_t)Z + m, uv);
 #pragma unroll
                 for (int s = 0; s < 8; ++s) {
                     const float sl = bits_to_float(float_to_bits<BF16>(gv[s] / (1.0f + expf(-gv[s]))), BF16);
@@ -204,19 +159,19 @@ __global__ __launch_bounds__(1024) void batched_gemm_kernel(const BProd pr, cons
 #pragma unroll
             for (int s = 0; s < 8; ++s) {
                 if constexpr (SLOTS) {
-                    const bool live = s < pr.B && ((on >> s) & 1u);
+                    const bool live = s < pr.rows && ((on >> s) & 1u);
                     x[s] = live ? x[s] : 0.0f;  // slots of absent or inactive sequences: zero, never kept
 #pragma unroll
                     for (int i = 0; i < 3; ++i)
                         if (i < nls && live && keep_rule(x[s], tau[i])) mk |= 1u << (8 * i + s);
                 } else {
-                    x[s] = s < pr.B ? x[s] : 0.0f;  // slots of absent sequences: zero, never kept
+                    x[s] = s < pr.rows ? x[s] : 0.0f;  // slots of absent sequences: zero, never kept
 #pragma unroll
                     for (int i = 0; i < 3; ++i)
-                        if (i < nls && s < pr.B && keep_rule(x[s], tau[i])) mk |= 1u << (8 * i + s);
+                        if (i < nls && s < pr.rows && keep_rule(x[s], tau[i])) mk |= 1u << (8 * i + s);
                 }
             }
-            xs[r] = b_pack_row<BF16>(x);
+            xs[r] = pack_row<BF16>(x);
             msk[r] = mk;
         }
         __syncthreads();
@@ -259,7 +214,7 @@ __global__ __launch_bounds__(1024) void batched_gemm_kernel(const BProd pr, cons
         __syncthreads();
         const int nlist = coff[kBChunks];
         const int njw = nlist > wave ? (nlist - wave + WAVES - 1) / WAVES : 0;  // this wave's entries: wave + 16 j
-        // ---- stream the listed rows: two batches of U rows in flight (teal_prefill.hip's pipeline)
+        // ---- stream the listed rows: two batches of U rows in flight (the pipeline of prefill_gemm_kernel, teal_prefill.hip)
         // (the list entry is read again where the row is consumed: held across the pipeline it cost 32 scalar registers and
         //  spilled the kernel)
         auto issue = [&](u32x2 (&w)[U], const int j0, auto guard) {
@@ -344,7 +299,7 @@ __global__ __launch_bounds__(256) void batched_round_rows_kernel(const float* __
     const int col = blockIdx.x * 256 + threadIdx.x;
     if (col >= N) return;
     float r[8];
-    b_rounded_row<BF16>(slabs, split, (size_t)N, (size_t)col, r);
+    slab_column<BF16, 8>(slabs, split, (size_t)N, (size_t)col, r);
 #pragma unroll
     for (int b = 0; b < 8; ++b)
         if (b < B) y[(size_t)b * N + col] = float_to_bits<BF16>(r[b]);
@@ -586,41 +541,13 @@ int batched_gemm_launch(const teal_prefill_in_t* in, const teal_batched_segs_t* 
     }
     if (sg.end[sg.nseg - 1] != ntot) return TEAL_ERR_SHAPE;
     for (int s = sg.nseg; s < 3; ++s) { sg.end[s] = ntot; sg.tau[s] = sg.tau[sg.nseg - 1]; }
-    BProd pr = {};
-    pr.B = B;
-    switch (in->mode) {
-        case TEAL_PREFILL_IN_XT:
-            if (!in->xt || !aligned16(in->xt)) return TEAL_ERR_ARG;
-            pr.xt = reinterpret_cast<const uint16_t*>(in->xt);
-            break;
-        case TEAL_PREFILL_IN_NORM:
-            if (!in->xt || !aligned16(in->xt) || !in->sumsq || !aligned16(in->sumsq) || !in->norm_w || in->nwg < 1 || in->nwg > 64) return TEAL_ERR_ARG;
-            pr.xt = reinterpret_cast<const uint16_t*>(in->xt);
-            pr.sumsq = in->sumsq; pr.nwg = in->nwg; pr.norm_w = reinterpret_cast<const uint16_t*>(in->norm_w); pr.eps = in->eps;
-            break;
-        case TEAL_PREFILL_IN_SILU_MUL:
-            if (!in->gu_slabs || !aligned16(in->gu_slabs) || in->gu_split < 1 || in->gu_split > kBMaxSplit) return TEAL_ERR_ARG;
-            if (in->gu_slabs == slabs) return TEAL_ERR_ARG;  // the launch reads its producer's slabs while it writes its own
-            pr.gu = in->gu_slabs; pr.gu_split = in->gu_split;
-            break;
-        default: return TEAL_ERR_ARG;
-    }
+    SlabProd pr;
+    if (const int rc = slab_prod_fill(in, slabs, kSlabMaxSplit, B, &pr)) return rc;
     if (!aligned16(w0T) || (w1T && !aligned16(w1T)) || !aligned16(slabs)) return TEAL_ERR_ALIGN;
     DeviceCtx* ctx = device_ctx();
     if (!ctx) return TEAL_ERR_NO_DEVICE;
-    // the prompt pass's geometry (teal_prefill_gemm): never more workgroups than CUs, every wave keeping a full pair of batches
-    // of a dense slice, the fewest 8-row batches per wave (ties: the fewer slabs)
     constexpr int bn = 256;
-    const int tiles = ntot / bn, ngroups = Z >> 4;
-    int smax = ctx->num_cu / tiles;
-    if (smax > Z / 256) smax = Z / 256;
-    if (smax > kBMaxSplit) smax = kBMaxSplit;
-    if (smax < 1) smax = 1;
-    int split = 1, best = INT_MAX;
-    for (int c = 1; c <= smax; ++c) {
-        const int batches = ((ngroups + c - 1) / c + 7) / 8;
-        if (batches < best) { best = batches; split = c; }
-    }
+    const int tiles = ntot / bn, split = slab_gemm_split(ctx->num_cu, tiles, Z, kSlabMaxSplit);
     if (slabs_bytes < (size_t)split * ntot * 8 * sizeof(float)) return TEAL_ERR_WORKSPACE;
     const dim3 grid(tiles, split), block(1024);
     const size_t lds = (size_t)kBPhaseRows * 28 + (size_t)(2 * kBChunks + 1) * sizeof(int) + (size_t)16 * 3 * kBCountStride * sizeof(int);
@@ -661,7 +588,7 @@ int teal_batched_sparse_gemm_slots(const teal_prefill_in_t* in, const teal_batch
 }
 
 int teal_batched_round_rows(const float* slabs, int split, int N, int B, void* y, int dtype, void* stream) {
-    if (!slabs || !y || split < 1 || split > kBMaxSplit || N <= 0) return TEAL_ERR_ARG;
+    if (!slabs || !y || split < 1 || split > kSlabMaxSplit || N <= 0) return TEAL_ERR_ARG;
     if (dtype != TEAL_F16 && dtype != TEAL_BF16) return TEAL_ERR_DTYPE;
     if (B < 1 || B > kBatchMax) return TEAL_ERR_SHAPE;
     if (!aligned16(slabs)) return TEAL_ERR_ALIGN;
@@ -684,7 +611,7 @@ namespace {
 int batched_attention_launch(const float* qkv_slabs, int split, const void* rope, const int32_t* pos, const int32_t* active, void* k_cache,
                              void* v_cache, void* yt, float* partials, size_t partials_bytes, int B, int n_head, int n_kv_head, int head_dim,
                              int max_seq, int dtype, void* stream) {
-    if (!qkv_slabs || !rope || !pos || !k_cache || !v_cache || !yt || !partials || split < 1 || split > kBMaxSplit) return TEAL_ERR_ARG;
+    if (!qkv_slabs || !rope || !pos || !k_cache || !v_cache || !yt || !partials || split < 1 || split > kSlabMaxSplit) return TEAL_ERR_ARG;
     if (dtype != TEAL_F16 && dtype != TEAL_BF16) return TEAL_ERR_DTYPE;
     if ((head_dim != 64 && head_dim != 128) || n_head <= 0 || n_kv_head <= 0 || n_head % n_kv_head || B < 1 || B > kBatchMax || max_seq < 1)
         return TEAL_ERR_SHAPE;

@@ -10,7 +10,8 @@
 //   gemm(wqkv) [RMSNorm while staging] -> attention (RoPE, cache rows 0..T-1, causal softmax) -> gemm(wo) -> resid ->
 //   gemm(w1 | w3) [RMSNorm while staging] -> gemm(w2) [silu * up while staging] -> resid
 //
-// Every hand-over between launches is TRANSPOSED: [feature][KR], KR = 8 for T <= 8 and 16 for 9 <= T <= 16 (round 6: prompts of
+// (The layout, the producer struct, the split choice and the slab / row helpers are in teal_slab.h, shared with the verify pass
+// and the batched step.)  Every hand-over between launches is TRANSPOSED: [feature][KR], KR = 8 for T <= 8 and 16 for 9 <= T <= 16 (round 6: prompts of
 // 9-16 tokens cost 2.1-2.2x the 8-token pass through the module path, profiles/r06_prefill_vs_prompt_length.txt) — the tokens of a
 // feature are one or two 16-byte words (16-bit activations) or KR / 4 of them (fp32 split-K slabs) — so that "row m of every
 // token" is contiguous: a GEMM workgroup
@@ -19,70 +20,11 @@
 // the strided one in the W^T image, which rules the matrix cores' operand layout out without a second copy of the weights).
 // Rounding points are those of the module path's 16-bit tensors (projection outputs, RoPE, attention output, residual adds,
 // RMSNorm twice, silu, product); sums are fp32.  Floating-point parity is against the module path, tolerance in the tests.
-#include "teal_common.h"
-
-#include <limits.h>
+#include "teal_slab.h"
 
 namespace teal {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kRowsMax = 16;  // most tokens a pass takes; a feature's row holds rows_for(T) of them
-constexpr int kPrefillMaxSplit = 16;
-constexpr int rows_for(const int T) { return T <= 8 ? 8 : 16; }
-
-// sum of `split` slabs in slice order, rounded once to the activation dtype: what a projection's 16-bit output tensor holds
-template <bool BF16, int KR>
-__device__ __forceinline__ void rounded_row(const float* __restrict__ slabs, const int split, const size_t n_total, const size_t col,
-                                            float (&out)[KR]) {
-    constexpr int NW = KR / 4, UU = KR == 8 ? 4 : 2;  // 16-byte words per row; slices whose loads are in flight together
-    f32x4 acc[NW];
-#pragma unroll
-    for (int w = 0; w < NW; ++w) acc[w] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    for (int k0 = 0; k0 < split; k0 += UU) {  // (clamped: a repeated slice is not added); slice order kept
-        f32x4 v[UU][NW];
-#pragma unroll
-        for (int u = 0; u < UU; ++u) {
-            const float* p = slabs + ((size_t)min(k0 + u, split - 1) * n_total + col) * KR;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) v[u][w] = *reinterpret_cast<const f32x4*>(p + 4 * w);
-        }
-#pragma unroll
-        for (int u = 0; u < UU; ++u) {
-            if (k0 + u < split) {
-#pragma unroll
-                for (int w = 0; w < NW; ++w) acc[w] += v[u][w];
-            }
-        }
-    }
-#pragma unroll
-    for (int w = 0; w < NW; ++w)
-#pragma unroll
-        for (int s = 0; s < 4; ++s) out[4 * w + s] = bits_to_float(float_to_bits<BF16>(acc[w][s]), BF16);
-}
-
-// a feature's KR tokens as KR / 8 16-byte words of 16-bit values
-template <bool BF16, int KR>
-__device__ __forceinline__ void store_row(uint16_t* __restrict__ p, const float (&v)[KR]) {
-#pragma unroll
-    for (int w = 0; w < KR / 8; ++w) {
-        u32x4 r;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            r[j] = (uint32_t)float_to_bits<BF16>(v[8 * w + 2 * j]) | ((uint32_t)float_to_bits<BF16>(v[8 * w + 2 * j + 1]) << 16);
-        *reinterpret_cast<u32x4*>(p + 8 * w) = r;
-    }
-}
-
-template <bool BF16, int KR>
-__device__ __forceinline__ void load_row(const uint16_t* __restrict__ p, float (&x)[KR]) {
-#pragma unroll
-    for (int w = 0; w < KR / 8; ++w) {
-        const u32x4 v = *reinterpret_cast<const u32x4*>(p + 8 * w);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { x[8 * w + 2 * j] = bits_to_float(v[j] & 0xFFFFu, BF16); x[8 * w + 2 * j + 1] = bits_to_float(v[j] >> 16, BF16); }
-    }
-}
 
 // 1 / rms per token from the per-workgroup sums of squares sumsq [nwg][KR] (lane = producing workgroup, nwg <= 64; the total in
 // workgroup order)
@@ -111,21 +53,9 @@ __device__ __forceinline__ void rstd_rows(const float* __restrict__ sumsq, const
 // is built without packed fp32, profiles/r06_concurrent_packed_fp32.txt: the 6-token pass 4.09 -> 4.25 ms).  First build (row groups inside a wave, the
 // activations through vector loads, 8 rows in flight): 2.1-3.5 TB/s; profiles/r05_prefill_kernel_stats.txt.
 // ------------------------------------------------------------------------------------------------
-// What the staging loop builds a row's eight activations from (PROD): 0 = xt itself; 1 = RMSNorm of the residual rows ht with the
-// per-workgroup sums of squares the resid launch left (every wave adds them itself) and the norm weight; 2 = silu(gate) * up from
-// the slabs of the gate | up launch.  Folding these into the staging removes a launch each: every workgroup builds only the rows
-// of its own slice (a 16th of the vector in the narrow projections), once.
-struct PrefillProd {
-    const uint16_t* xt;       // PROD 0: [Z][8];  PROD 1: the residual rows ht [Z][8]
-    const float* sumsq;       // PROD 1: [nwg][8]
-    const uint16_t* norm_w;   // PROD 1: [Z]
-    const float* gu;          // PROD 2: slabs [gu_split][2 Z][8] of the gate | up launch
-    float eps;
-    int nwg, gu_split, T;
-};
-
+// What the staging loop builds a row's activations from (PROD 0 / 1 / 2): SlabProd, teal_slab.h.
 template <bool BF16, int NP, int PROD, int KR>
-__global__ __launch_bounds__(1024) void prefill_gemm_kernel(const PrefillProd pr, const uint16_t* __restrict__ w0, const int ld0,
+__global__ __launch_bounds__(1024) void prefill_gemm_kernel(const SlabProd pr, const uint16_t* __restrict__ w0, const int ld0,
                                                             const uint16_t* __restrict__ w1, const int ld1, const int tiles0,
                                                             float* __restrict__ slabs, const int Z, const int n_total) {
     const uint16_t* __restrict__ xt = pr.xt;
@@ -190,7 +120,7 @@ __global__ __launch_bounds__(1024) void prefill_gemm_kernel(const PrefillProd pr
 #pragma unroll
                 for (int s_ = 0; s_ < KR; ++s_) {
                     const float xn = bits_to_float(float_to_bits<BF16>(x[s_] * rstd[s_]), BF16);
-                    x[s_] = s_ < pr.T ? bits_to_float(float_to_bits<BF16>(xn * nw), BF16) : 0.0f;
+                    x[s_] = s_ < pr.rows ? bits_to_float(float_to_bits<BF16>(xn * nw), BF16) : 0.0f;
                 }
                 store_row<BF16, KR>(dst, x);
             } else {  // x = round(round(silu(round(gate))) * round(up))  (gpt-fast/model.py:258-259)
@@ -200,7 +130,7 @@ __global__ __launch_bounds__(1024) void prefill_gemm_kernel(const PrefillProd pr
 #pragma unroll
                 for (int s_ = 0; s_ < KR; ++s_) {
                     const float sl = bits_to_float(float_to_bits<BF16>(gv[s_] / (1.0f + expf(-gv[s_]))), BF16);
-                    x[s_] = s_ < pr.T ? bits_to_float(float_to_bits<BF16>(sl * uv[s_]), BF16) : 0.0f;
+                    x[s_] = s_ < pr.rows ? bits_to_float(float_to_bits<BF16>(sl * uv[s_]), BF16) : 0.0f;
                 }
                 store_row<BF16, KR>(dst, x);
             }
@@ -461,44 +391,15 @@ int teal_prefill_gemm(const teal_prefill_in_t* in, const void* w0T, int ld0, int
     if (dtype != TEAL_F16 && dtype != TEAL_BF16) return TEAL_ERR_DTYPE;
     if (T < 1 || T > kRowsMax || (Z & 255) || Z > 65536 || (ld0 & 7) || (ld1 & 7) || ld0 < n0 || (n1 > 0 && ld1 < n1)) return TEAL_ERR_SHAPE;
     const int kr = rows_for(T);
-    PrefillProd pr = {};
-    pr.T = T;
-    switch (in->mode) {
-        case TEAL_PREFILL_IN_XT:
-            if (!in->xt || !aligned16(in->xt)) return TEAL_ERR_ARG;
-            pr.xt = reinterpret_cast<const uint16_t*>(in->xt);
-            break;
-        case TEAL_PREFILL_IN_NORM:
-            if (!in->xt || !aligned16(in->xt) || !in->sumsq || !aligned16(in->sumsq) || !in->norm_w || in->nwg < 1 || in->nwg > 64) return TEAL_ERR_ARG;
-            pr.xt = reinterpret_cast<const uint16_t*>(in->xt);
-            pr.sumsq = in->sumsq; pr.nwg = in->nwg; pr.norm_w = reinterpret_cast<const uint16_t*>(in->norm_w); pr.eps = in->eps;
-            break;
-        case TEAL_PREFILL_IN_SILU_MUL:
-            if (!in->gu_slabs || !aligned16(in->gu_slabs) || in->gu_split < 1 || in->gu_split > kPrefillMaxSplit) return TEAL_ERR_ARG;
-            pr.gu = in->gu_slabs; pr.gu_split = in->gu_split;
-            if (in->gu_slabs == slabs) return TEAL_ERR_ARG;  // the launch reads its producer's slabs while it writes its own
-            break;
-        default: return TEAL_ERR_ARG;
-    }
+    SlabProd pr;
+    if (const int rc = slab_prod_fill(in, slabs, kSlabMaxSplit, T, &pr)) return rc;
     if (!aligned16(w0T) || (w1T && !aligned16(w1T)) || !aligned16(slabs)) return TEAL_ERR_ALIGN;
     DeviceCtx* ctx = device_ctx();
     if (!ctx) return TEAL_ERR_NO_DEVICE;
-    const int ncu = ctx->num_cu, ntot = n0 + n1;
-    // 256-column tiles; the 16-row groups are dealt to `split` slices: never more workgroups than CUs (a 16-wave workgroup owns its
-    // CU: 86 tiles x 3 = 258 workgroups ran 62 us, x 2 = 172 run 38), every wave keeping at least one full pair of batches
-    // (split <= Z / 256), and among the candidates the one whose waves stream the fewest 8-row batches (ties: the fewer slabs)
     constexpr int bn = 256;
+    const int ntot = n0 + n1;
     if (n0 % bn || n1 % bn) return TEAL_ERR_SHAPE;
-    const int tiles = ntot / bn, ngroups = Z >> 4;
-    int smax = ncu / tiles;
-    if (smax > Z / 256) smax = Z / 256;
-    if (smax > kPrefillMaxSplit) smax = kPrefillMaxSplit;
-    if (smax < 1) smax = 1;
-    int split = 1, best = INT_MAX;
-    for (int c = 1; c <= smax; ++c) {
-        const int batches = ((ngroups + c - 1) / c + 7) / 8;
-        if (batches < best) { best = batches; split = c; }
-    }
+    const int tiles = ntot / bn, split = slab_gemm_split(ctx->num_cu, tiles, Z, kSlabMaxSplit);
     if (slabs_bytes < (size_t)split * ntot * kr * sizeof(float)) return TEAL_ERR_WORKSPACE;
     const dim3 grid(tiles, split), block(1024);
     const size_t lds = (size_t)16 * bn * 2 * sizeof(float);  // 32 KB: the activation rows of a phase, then the reduction tile

@@ -1,41 +1,21 @@
 // teal_speculative.hip — the verify side of speculative decoding (gpt-fast/generate.py:98-217) for gfx950 / CDNA4, wave64.
 //
 // One round: k draft steps (the fused decode step, TEAL-sparse), then ONE dense pass over the k + 1 tokens [x0, d1 .. dk] at
-// positions p .. p+k through the prompt pass's GEMMs (teal_prefill.hip), with
+// positions p .. p+k through the prompt pass's GEMMs (teal_prefill.hip; the slab layout and its helpers: teal_slab.h), with
 //   verify_attention_kernel + verify_merge_kernel   attention of the k + 1 rows against the whole cache (split-KV)
 //   spec_round_logits_kernel                        the lm_head slabs of every row, summed and rounded once (the module's logits)
 //   spec_row_stats_kernel                           per row: max, top-k pivot, softmax normaliser
 //   spec_decide_kernel                              the reference's accept / reject rule (gpt-fast/generate.py:123-146)
 // Everything that decides the round stays on the device: the accepted count, the emitted tokens, the next round's position
 // and input token.  The draw convention is in include/teal_hip.h (teal_spec_accept).
-#include "teal_common.h"
+#include "teal_slab.h"
 
 namespace teal {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kVerifyMaxT = 16;     // the prompt pass's most tokens per pass
 constexpr int kVerifyChunk = 32;    // context rows a workgroup stages per round
 constexpr int kVerifyMaxQ = 64;     // query rows (heads of a group x tokens) per workgroup
 constexpr int kVerifyMaxSplit = 64;
-constexpr int verify_rows_for(const int T) { return T <= 8 ? 8 : 16; }
-
-// sum of `split` slabs [slice][n_total][KR] of column `col` in slice order, rounded once to the activation dtype
-template <bool BF16, int KR>
-__device__ __forceinline__ void slab_column(const float* __restrict__ slabs, const int split, const size_t n_total, const size_t col,
-                                            float (&out)[KR]) {
-    f32x4 acc[KR / 4];
-#pragma unroll
-    for (int w = 0; w < KR / 4; ++w) acc[w] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    for (int s = 0; s < split; ++s) {
-        const float* p = slabs + ((size_t)s * n_total + col) * KR;
-#pragma unroll
-        for (int w = 0; w < KR / 4; ++w) acc[w] += *reinterpret_cast<const f32x4*>(p + 4 * w);
-    }
-#pragma unroll
-    for (int w = 0; w < KR / 4; ++w)
-#pragma unroll
-        for (int s = 0; s < 4; ++s) out[4 * w + s] = bits_to_float(float_to_bits<BF16>(acc[w][s]), BF16);
-}
 
 // ------------------------------------------------------------------------------------------------
 // Attention of T <= 16 new tokens at positions p0 .. p0+T-1 (p0 read from the device) against cache rows 0 .. p0+t.
@@ -439,7 +419,7 @@ int teal_verify_attention(const float* qkv_slabs, int split, const void* rope, c
     auto* kc = reinterpret_cast<uint16_t*>(k_cache);
     auto* vc = reinterpret_cast<uint16_t*>(v_cache);
     auto* y = reinterpret_cast<uint16_t*>(yt);
-    const int kr = verify_rows_for(T);
+    const int kr = rows_for(T);
 #define TEAL_VA(BF, HDV, KRV) do { \
         hipLaunchKernelGGL((verify_attention_kernel<BF, HDV, KRV>), grid, dim3(256), 0, st, qkv_slabs, split, pos, rp, kc, vc, partials, T, \
                            n_head, n_kv_head, hq, max_seq, scale); \
@@ -477,7 +457,7 @@ int teal_spec_accept(const float* logit_slabs, int split, const void* draft_logi
     auto* rs = reinterpret_cast<unsigned long long*>(rng_state);
     const dim3 gr((vocab + 255) / 256);
 #define TEAL_SA(BF) do { \
-        if (verify_rows_for(T) == 8) hipLaunchKernelGGL((spec_round_logits_kernel<BF, 8>), gr, dim3(256), 0, st, logit_slabs, split, vocab, T, tl); \
+        if (rows_for(T) == 8) hipLaunchKernelGGL((spec_round_logits_kernel<BF, 8>), gr, dim3(256), 0, st, logit_slabs, split, vocab, T, tl); \
         else hipLaunchKernelGGL((spec_round_logits_kernel<BF, 16>), gr, dim3(256), 0, st, logit_slabs, split, vocab, T, tl); \
         hipLaunchKernelGGL((spec_row_stats_kernel<BF>), dim3(2 * k + 1), dim3(1024), 0, st, tl, dl, vocab, k, top_k, inv_temp, stats); \
         hipLaunchKernelGGL((spec_decide_kernel<BF>), dim3(1), dim3(1024), 0, st, tl, dl, stats, vocab, k, inv_temp, rs, tokens, spec_pos, pos_out, \

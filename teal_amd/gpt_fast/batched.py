@@ -28,16 +28,16 @@ from . import constraints as CN
 from . import logit_processors as PR
 from . import sampling as SM
 from . import stopping as ST
-from .engine_features import SamplerFeatures, _SlotCaches, dense_16bit_refusal, relayout
+from .engine_features import SamplerFeatures, _SlotCaches, dense_16bit_refusal, slab_chain_refusal
 from .model import Transformer
-from .prefill import IN_NORM, IN_SILU_MUL, IN_XT, MAX_T, PrefillEngine, PrefillIn
+from .prefill import MAX_T, PrefillEngine, PrefillIn, SlabChain
 from .speculative import VerifyPass
 
 PROJ_LAUNCHES = (("qkv", ("q", "k", "v")), ("o", ("o",)), ("gateup", ("gate", "up")), ("down", ("down",)))
 NINF = float("-inf")
 
 
-class BatchedDecodeEngine(SamplerFeatures):
+class BatchedDecodeEngine(SlabChain, SamplerFeatures):
     @staticmethod
     def supports(model: Transformer) -> Optional[str]:
         """None if the batched step can run `model` as it stands (batch = the caches' max_batch_size), else the reason."""
@@ -49,23 +49,25 @@ class BatchedDecodeEngine(SamplerFeatures):
             "quantised (int8 / int4) weights are not batched")
         if why is not None:
             return why
-        dt = model.output.weight.dtype
         inter = model.layers[0].feed_forward.w1.out_features
-        qd, kv = cfg.n_head * cfg.head_dim, cfg.n_local_heads * cfg.head_dim
-        if (cfg.head_dim not in (64, 128) or cfg.dim != qd or cfg.dim % 256 or cfg.dim > 16384 or inter % 256 or inter > 65536
-                or (qd + 2 * kv) % 256 or kv % 8 or cfg.vocab_size % 256):
-            return ("shape outside the batched kernels' contract (head_dim 64 / 128, dim = n_head * head_dim <= 16384, "
-                    "dim / intermediate / qkv width / vocab multiples of 256)")
-        if model.freqs_cis is None or model.freqs_cis.dtype != dt:
-            return "caches are not set up (model.setup_caches) in the model dtype"
-        B = None
-        for layer in model.layers:
-            kc = getattr(layer.attention, "kv_cache", None)
-            if kc is None or kc.k_cache.dim() != 4 or not kc.k_cache.is_contiguous() or not kc.v_cache.is_contiguous():
-                return "KV caches must be contiguous [B, n_kv, max_seq, head_dim] tensors"
-            B = kc.k_cache.shape[0] if B is None else B
-            if kc.k_cache.shape[0] != B or kc.v_cache.shape[0] != B:
+        kv = cfg.n_local_heads * cfg.head_dim
+        caches_why = "KV caches must be contiguous [B, n_kv, max_seq, head_dim] tensors"
+        sizes = []  # the layers' batch sizes
+
+        def one_batch_size(kc):
+            if kc.k_cache.dim() != 4:
+                return caches_why
+            sizes.append(kc.k_cache.shape[0])
+            if kc.k_cache.shape[0] != sizes[0] or kc.v_cache.shape[0] != sizes[0]:
                 return "KV caches must share one batch size"
+            return None
+
+        why = slab_chain_refusal(model, "shape outside the batched kernels' contract (head_dim 64 / 128, dim = n_head * head_dim <= 16384, "
+                                 "dim / intermediate / qkv width / vocab multiples of 256)", caches_why,
+                                 own_shape=bool(inter > 65536 or kv % 8 or cfg.vocab_size % 256), cache_rule=one_batch_size)
+        if why is not None:
+            return why
+        B = sizes[0] if sizes else None
         if B is None or not 1 <= B <= BATCH_MAX:
             return f"batch size {B} outside 1..{BATCH_MAX} (setup_caches(max_batch_size=B))"
         return None
@@ -80,42 +82,26 @@ class BatchedDecodeEngine(SamplerFeatures):
             raise ValueError(f"BatchedDecodeEngine: batch {B} must equal the caches' max_batch_size ({cache_b}) and be <= {BATCH_MAX}")
         if len(thresholds) != len(model.layers):
             raise ValueError("one thresholds dict per layer")
-        self.L = _lib.load()
-        runtime.init()
-        self.model, self.cfg, self.B = model, model.config, B
+        SlabChain.__init__(self, model, BATCH_MAX)
+        self.cfg, self.B = model.config, B
         self._feature_rows = B
         cfg = self.cfg
         dev, dt = model.output.weight.device, model.output.weight.dtype
-        self.dtype, self.code = dt, runtime.dtype_code(dt)
-        relayout(model)
+        self.dtype = dt
         self.ths = [dict(t) for t in thresholds]
-        self.dim, self.hd = cfg.dim, cfg.head_dim
-        self.kv = cfg.n_local_heads * cfg.head_dim
-        self.nqkv = self.dim + 2 * self.kv
-        self.inter = model.layers[0].feed_forward.w1.out_features
-        self.max_seq = model.max_seq_length
         V = cfg.vocab_size
         z = lambda *shape, dtype=dt: torch.zeros(*shape, device=dev, dtype=dtype)  # noqa: E731
         i32 = dict(dtype=torch.int32)
         self.tok_buf = z(BATCH_MAX, **i32)   # the B current tokens
         self.pos_buf = z(BATCH_MAX, **i32)   # the B positions (device; may differ)
-        self.ht, self.yt = z(self.dim, BATCH_MAX), z(self.dim, BATCH_MAX)
-        n = 16 * max(self.nqkv, 2 * self.inter, self.dim) * BATCH_MAX
-        self.slabs = [z(n, dtype=torch.float32), z(n, dtype=torch.float32)]
         self.lm_slabs = z(16 * V * BATCH_MAX, dtype=torch.float32)
-        self.sumsq = z(64 * BATCH_MAX, dtype=torch.float32)
         self.logits = z(B, V)
         nb = int(self.L.teal_batched_decode_attention_ws_bytes(B, cfg.n_head, cfg.head_dim))
         self.partials = z((nb + 3) // 4, dtype=torch.float32)
         # kept counts of the last step: [layer][launch][slice 16][segment 3][9] (per sequence, union)
         self.counts = z(len(model.layers), len(PROJ_LAUNCHES), 16 * 3 * 9, **i32)
         self.splits = [[0] * len(PROJ_LAUNCHES) for _ in model.layers]
-        self.rope = model.freqs_cis.contiguous()
-        self.eps = float(cfg.norm_eps)
-        self.nwg = (self.dim + 255) // 256
-        self._split = ctypes.c_int(0)
         # sampling state, one set per sequence
-        self.ws = runtime.new_workspace(self.dim, V)
         self.rng_state = torch.zeros(B, 2, dtype=torch.int64, device=dev)
         self.history = z(B, self.max_seq + 1, **i32)
         self._seed = 1234
@@ -167,34 +153,15 @@ class BatchedDecodeEngine(SamplerFeatures):
         if rc != 0:
             _lib.check(rc, what)
 
-    def _resid(self, tokens: bool, slabs: Optional[torch.Tensor], split: int, st):
-        m = self.model
-        rc = self.L.teal_prefill_resid_norm(m.tok_embeddings.weight.data_ptr() if tokens else None,
-                                            self.tok_buf.data_ptr() if tokens else None, self.B, None if tokens else self.ht.data_ptr(),
-                                            slabs.data_ptr() if slabs is not None else None, split, None, self.eps, self.dim,
-                                            self.ht.data_ptr(), None, None, self.sumsq.data_ptr(), self.code, st)
-        if rc != 0:
-            _lib.check(rc, "teal_prefill_resid_norm")
-
-    def _norm_in(self, norm_w) -> PrefillIn:
-        return PrefillIn(mode=IN_NORM, xt=self.ht.data_ptr(), sumsq=self.sumsq.data_ptr(), nwg=self.nwg, norm_w=norm_w.data_ptr(), eps=self.eps)
-
     def _step(self, ths_override: Optional[float] = None):
         """one step for all B sequences from tok_buf / pos_buf -> self.logits [B, vocab] (no host synchronisation)"""
         m, cfg, L, st = self.model, self.cfg, self.L, runtime.stream_ptr()
-        A, Bs = self.slabs
-        self._resid(True, None, 0, st)
-        for i, layer in enumerate(m.layers):
-            at, ff, sg, cnt = layer.attention, layer.feed_forward, self._segs[i], self.counts[i]
-            sp = self.splits[i]
-            sp[0] = ns = self._gemm(self._norm_in(layer.attention_norm.weight), sg["qkv"], at.wqkv, None, self.dim, A, cnt[0], st)
-            self._attention(at, A, ns, st)
-            sp[1] = ns = self._gemm(PrefillIn(mode=IN_XT, xt=self.yt.data_ptr()), sg["o"], at.wo, None, self.dim, Bs, cnt[1], st)
-            self._resid(False, Bs, ns, st)
-            sp[2] = ns = self._gemm(self._norm_in(layer.ffn_norm.weight), sg["gateup"], ff.w1, ff.w3, self.dim, A, cnt[2], st)
-            sp[3] = ns = self._gemm(PrefillIn(mode=IN_SILU_MUL, gu_slabs=A.data_ptr(), gu_split=ns), sg["down"], ff.w2, None, self.inter, Bs,
-                                    cnt[3], st)
-            self._resid(False, Bs, ns, st)
+
+        def gemm(i, j, gin, lin0, lin1, Z, out):
+            self.splits[i][j] = ns = self._gemm(gin, self._segs[i][PROJ_LAUNCHES[j][0]], lin0, lin1, Z, out, self.counts[i, j], st)
+            return ns
+
+        self._walk(self.B, self.tok_buf.data_ptr(), gemm, lambda at, A, ns: self._attention(at, A, ns, st), st)
         ns = self._gemm(self._norm_in(m.norm.weight), self._lm_segs, m.output, None, self.dim, self.lm_slabs, None, st)
         rc = L.teal_batched_round_rows(self.lm_slabs.data_ptr(), ns, cfg.vocab_size, self.B, self.logits.data_ptr(), self.code, st)
         if rc != 0:

@@ -66,6 +66,32 @@ def dense_16bit_refusal(model, quantised, quantised_why: str) -> Optional[str]:
     return None
 
 
+def slab_chain_refusal(model, shape_why: str, caches_why: str, own_shape: bool = False, then: Optional[str] = None,
+                       cache_rule=None) -> Optional[str]:
+    """why the dense slab chain (prompt pass, verify pass, batched step) cannot take `model`'s shapes and caches, or None, tried in
+    this order: the shape contract (head_dim 64 / 128, dim = n_head * head_dim <= 16384, widths % 256) or the caller's `own_shape`
+    -> shape_why; `then`, a reason of the caller's own; freqs_cis in the model dtype; per layer a contiguous KV cache -> caches_why,
+    then cache_rule(kv_cache), the caller's own rule (a reason or None)."""
+    cfg = model.config
+    inter = model.layers[0].feed_forward.w1.out_features
+    qd, kv = cfg.n_head * cfg.head_dim, cfg.n_local_heads * cfg.head_dim
+    if (cfg.head_dim not in (64, 128) or cfg.dim != qd or cfg.dim % 256 or cfg.dim > 16384 or inter % 256 or (qd + 2 * kv) % 256
+            or own_shape):
+        return shape_why
+    if then is not None:
+        return then
+    if model.freqs_cis is None or model.freqs_cis.dtype != model.output.weight.dtype:
+        return "caches are not set up (model.setup_caches) in the model dtype"
+    for layer in model.layers:
+        kc = getattr(layer.attention, "kv_cache", None)
+        if kc is None or not kc.k_cache.is_contiguous() or not kc.v_cache.is_contiguous():
+            return caches_why
+        why = cache_rule(kc) if cache_rule is not None else None
+        if why is not None:
+            return why
+    return None
+
+
 class _SlotCaches:
     """the K / V base pointers of slot `slot` of batch-B caches: slot s of a contiguous [B, n_kv, max_seq, hd] cache is itself a
     contiguous [1, n_kv, max_seq, hd] cache"""

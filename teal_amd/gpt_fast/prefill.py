@@ -25,7 +25,7 @@ from typing import Optional
 import torch
 
 from .. import _lib, runtime
-from .engine_features import dense_16bit_refusal, pointer_key, relayout
+from .engine_features import dense_16bit_refusal, pointer_key, relayout, slab_chain_refusal
 from .model import Transformer
 
 MAX_T = 16  # most tokens of a pass; the hand-over layout is [feature][8] for T <= 8 and [feature][16] for 9 <= T <= 16 (buffers sized for 16)
@@ -37,40 +37,13 @@ class PrefillIn(ctypes.Structure):  # teal_prefill_in_t
                 ("norm_w", ctypes.c_void_p), ("eps", ctypes.c_float), ("gu_slabs", ctypes.c_void_p), ("gu_split", ctypes.c_int)]
 
 
-class PrefillEngine:
-    @staticmethod
-    def supports(model: Transformer) -> Optional[str]:
-        """None if the fused prompt pass can run `model` as it stands, else the reason (the caller keeps the module path)."""
-        return PrefillEngine._supports(model, any_batch=False)
+class SlabChain:
+    """The dense layer chain over the transposed hand-over layout ([feature][8 or 16] activations, fp32 split-K slabs;
+    teal_amd/csrc/teal_slab.h) that the prompt pass, the verify / suffix pass and the batched / slot step share: the buffers of
+    `cols` token (or sequence) columns, the resid launch and the walk over the layers.  A pass is `_walk` with its own GEMM and
+    attention launches, then its own tail."""
 
-    @staticmethod
-    def _supports(model: Transformer, any_batch: bool) -> Optional[str]:
-        cfg = model.config
-        if int(getattr(model, "tp_world", 1)) > 1:
-            return "tensor-parallel models prefill through the module path (its all-reduce hooks)"
-        why = dense_16bit_refusal(model, lambda lin: hasattr(lin, "scales_and_zeros") or hasattr(lin, "scales"),
-                                  "quantised weights prefill through the module path")
-        if why is not None:
-            return why
-        dt = model.output.weight.dtype
-        inter = model.layers[0].feed_forward.w1.out_features
-        qd, kv = cfg.n_head * cfg.head_dim, cfg.n_local_heads * cfg.head_dim
-        if cfg.head_dim not in (64, 128) or cfg.dim != qd or cfg.dim % 256 or cfg.dim > 16384 or inter % 256 or (qd + 2 * kv) % 256:
-            return "shape outside the prompt-pass kernels' contract (head_dim 64 / 128, dim = n_head * head_dim <= 16384, widths % 256)"
-        if cfg.vocab_size % 8:
-            return "vocab_size must be a multiple of 8"
-        if model.freqs_cis is None or model.freqs_cis.dtype != dt:
-            return "caches are not set up (model.setup_caches) in the model dtype"
-        for layer in model.layers:
-            kc = getattr(layer.attention, "kv_cache", None)
-            if kc is None or (kc.k_cache.shape[0] != 1 and not any_batch) or not kc.k_cache.is_contiguous() or not kc.v_cache.is_contiguous():
-                return "KV caches must be contiguous with max_batch_size == 1"
-        return None
-
-    def __init__(self, model: Transformer):
-        why = type(self).supports(model)
-        if why is not None:
-            raise ValueError(f"{type(self).__name__} cannot run this model: {why}")
+    def __init__(self, model: Transformer, cols: int):
         self.L = _lib.load()
         runtime.init()
         self.model, cfg = model, model.config
@@ -82,21 +55,79 @@ class PrefillEngine:
         self.nqkv = self.dim + 2 * self.kv
         self.inter = model.layers[0].feed_forward.w1.out_features
         self.max_seq = model.max_seq_length
-        z = lambda *shape, dtype=dt: torch.zeros(*shape, device=dev, dtype=dtype)  # noqa: E731
-        self.tokens = z(MAX_T, dtype=torch.int32)
-        self.ht, self.yt = z(self.dim, MAX_T), z(self.dim, MAX_T)
+        self.ht, self.yt = torch.zeros(self.dim, cols, device=dev, dtype=dt), torch.zeros(self.dim, cols, device=dev, dtype=dt)
         # two slab buffers [slices <= 16][columns][8 or 16] fp32, used alternately (launches are stream-ordered: a consumer has read its
         # producer's slabs before the next-but-one GEMM overwrites them; the down projection reads gate | up's while writing its own)
-        n = 16 * max(self.nqkv, 2 * self.inter, self.dim) * MAX_T
-        self.slabs = [z(n, dtype=torch.float32), z(n, dtype=torch.float32)]
-        self.x_last = z(self.dim)
-        self.sumsq = z(64 * MAX_T, dtype=torch.float32)  # per-workgroup sums of squares: resid launch -> normalising consumer
-        self.logits = z(1, 1, cfg.vocab_size)
+        n = 16 * max(self.nqkv, 2 * self.inter, self.dim) * cols
+        self.slabs = [torch.zeros(n, device=dev, dtype=torch.float32) for _ in range(2)]
+        self.sumsq = torch.zeros(64 * cols, device=dev, dtype=torch.float32)  # per-workgroup sums of squares: resid launch -> normalising consumer
         self.rope = model.freqs_cis.contiguous()
         self.ws = runtime.new_workspace(self.dim, cfg.vocab_size)
         self.eps = float(cfg.norm_eps)
         self.nwg = (self.dim + 255) // 256
         self._split = ctypes.c_int(0)
+
+    def _resid(self, token_ptr: Optional[int], slabs: Optional[torch.Tensor], split: int, n: int, st, final_norm=None):
+        """h = the embedding rows of the n int32 tokens at `token_ptr`, or (token_ptr None) h += round(sum slabs); leaves the
+        per-workgroup sums of squares for the normalising consumer.  final_norm: also the normalised vector of the LAST token as a
+        plain vector in `x_last` (the lm_head's input)."""
+        rc = self.L.teal_prefill_resid_norm(self.model.tok_embeddings.weight.data_ptr() if token_ptr else None, token_ptr, n,
+                                            None if token_ptr else self.ht.data_ptr(), slabs.data_ptr() if slabs is not None else None, split,
+                                            final_norm.data_ptr() if final_norm is not None else None, self.eps, self.dim, self.ht.data_ptr(),
+                                            None, self.x_last.data_ptr() if final_norm is not None else None, self.sumsq.data_ptr(), self.code, st)
+        if rc != 0:
+            _lib.check(rc, "teal_prefill_resid_norm")
+
+    def _norm_in(self, norm_w) -> PrefillIn:
+        return PrefillIn(mode=IN_NORM, xt=self.ht.data_ptr(), sumsq=self.sumsq.data_ptr(), nwg=self.nwg, norm_w=norm_w.data_ptr(), eps=self.eps)
+
+    def _walk(self, n: int, token_ptr: int, gemm, attention, st, final_norm=None):
+        """The chain for n columns whose tokens are at `token_ptr`: the embedding resid, then per layer qkv, attention, wo, resid,
+        gate | up, down, resid.  gemm(i, j, gin, lin0, lin1, Z, out) -> split is the pass's GEMM launch (layer i; j = 0 qkv, 1 wo,
+        2 gate | up, 3 down), attention(at, slabs, ns) its attention launch over the qkv slabs; final_norm goes to the last resid."""
+        A, B = self.slabs
+        layers = list(self.model.layers)
+        self._resid(token_ptr, None, 0, n, st)
+        for i, layer in enumerate(layers):
+            at, ff = layer.attention, layer.feed_forward
+            ns = gemm(i, 0, self._norm_in(layer.attention_norm.weight), at.wqkv, None, self.dim, A)
+            attention(at, A, ns)
+            ns = gemm(i, 1, PrefillIn(mode=IN_XT, xt=self.yt.data_ptr()), at.wo, None, self.dim, B)
+            self._resid(None, B, ns, n, st)
+            ns = gemm(i, 2, self._norm_in(layer.ffn_norm.weight), ff.w1, ff.w3, self.dim, A)
+            ns = gemm(i, 3, PrefillIn(mode=IN_SILU_MUL, gu_slabs=A.data_ptr(), gu_split=ns), ff.w2, None, self.inter, B)
+            self._resid(None, B, ns, n, st, final_norm=final_norm if i + 1 == len(layers) else None)
+
+
+class PrefillEngine(SlabChain):
+    @staticmethod
+    def supports(model: Transformer) -> Optional[str]:
+        """None if the fused prompt pass can run `model` as it stands, else the reason (the caller keeps the module path)."""
+        return PrefillEngine._supports(model, any_batch=False)
+
+    @staticmethod
+    def _supports(model: Transformer, any_batch: bool) -> Optional[str]:
+        if int(getattr(model, "tp_world", 1)) > 1:
+            return "tensor-parallel models prefill through the module path (its all-reduce hooks)"
+        why = dense_16bit_refusal(model, lambda lin: hasattr(lin, "scales_and_zeros") or hasattr(lin, "scales"),
+                                  "quantised weights prefill through the module path")
+        if why is not None:
+            return why
+        caches_why = "KV caches must be contiguous with max_batch_size == 1"
+        return slab_chain_refusal(
+            model, "shape outside the prompt-pass kernels' contract (head_dim 64 / 128, dim = n_head * head_dim <= 16384, widths % 256)",
+            caches_why, then="vocab_size must be a multiple of 8" if model.config.vocab_size % 8 else None,
+            cache_rule=lambda kc: caches_why if kc.k_cache.shape[0] != 1 and not any_batch else None)
+
+    def __init__(self, model: Transformer):
+        why = type(self).supports(model)
+        if why is not None:
+            raise ValueError(f"{type(self).__name__} cannot run this model: {why}")
+        super().__init__(model, MAX_T)
+        dev, dt = model.output.weight.device, model.output.weight.dtype
+        self.tokens = torch.zeros(MAX_T, device=dev, dtype=torch.int32)
+        self.x_last = torch.zeros(self.dim, device=dev, dtype=dt)
+        self.logits = torch.zeros(1, 1, model.config.vocab_size, device=dev, dtype=dt)
 
     def key(self):
         """everything the launches hold raw pointers to: a re-laid-out weight or a re-allocated KV cache needs a new engine"""
@@ -116,19 +147,9 @@ class PrefillEngine:
             _lib.check(rc, "teal_prefill_gemm")
         return self._split.value
 
-    def _resid(self, tokens: bool, slabs: Optional[torch.Tensor], split: int, T, st, final_norm=None):
-        """h (+)= round(sum slabs); leaves the per-workgroup sums of squares for the normalising consumer.  final_norm: also
-        the normalised vector of the LAST token as a plain vector (the lm_head's input)."""
-        rc = self.L.teal_prefill_resid_norm(self.model.tok_embeddings.weight.data_ptr() if tokens else None,
-                                            self.tokens.data_ptr() if tokens else None, T, None if tokens else self.ht.data_ptr(),
-                                            slabs.data_ptr() if slabs is not None else None, split,
-                                            final_norm.data_ptr() if final_norm is not None else None, self.eps, self.dim, self.ht.data_ptr(),
-                                            None, self.x_last.data_ptr() if final_norm is not None else None, self.sumsq.data_ptr(), self.code, st)
-        if rc != 0:
-            _lib.check(rc, "teal_prefill_resid_norm")
-
-    def _norm_in(self, norm_w) -> PrefillIn:
-        return PrefillIn(mode=IN_NORM, xt=self.ht.data_ptr(), sumsq=self.sumsq.data_ptr(), nwg=self.nwg, norm_w=norm_w.data_ptr(), eps=self.eps)
+    def _dense_walk(self, T: int, token_ptr: int, attention, st, final_norm=None):
+        """the chain through the dense GEMM at T tokens"""
+        self._walk(T, token_ptr, lambda i, j, gin, lin0, lin1, Z, out: self._gemm(gin, lin0, lin1, Z, T, out, st), attention, st, final_norm)
 
     @torch.no_grad()
     def __call__(self, prompt: torch.Tensor) -> torch.Tensor:
@@ -138,22 +159,15 @@ class PrefillEngine:
         assert 1 <= T <= MAX_T and T <= self.max_seq
         m, cfg, L, st = self.model, self.model.config, self.L, runtime.stream_ptr()
         self.tokens[:T].copy_(prompt.view(-1))
-        layers = list(m.layers)
-        A, B = self.slabs
-        self._resid(True, None, 0, T, st)
-        for i, layer in enumerate(layers):
-            at, ff = layer.attention, layer.feed_forward
-            ns = self._gemm(self._norm_in(layer.attention_norm.weight), at.wqkv, None, self.dim, T, A, st)
+
+        def attention(at, A, ns):
             kc, vc = self._caches(at)
             rc = L.teal_prefill_attention(A.data_ptr(), ns, self.rope.data_ptr(), kc, vc, self.yt.data_ptr(), T,
                                           cfg.n_head, cfg.n_local_heads, cfg.head_dim, self.max_seq, self.code, st)
             if rc != 0:
                 _lib.check(rc, "teal_prefill_attention")
-            ns = self._gemm(PrefillIn(mode=IN_XT, xt=self.yt.data_ptr()), at.wo, None, self.dim, T, B, st)
-            self._resid(False, B, ns, T, st)
-            ns = self._gemm(self._norm_in(layer.ffn_norm.weight), ff.w1, ff.w3, self.dim, T, A, st)
-            ns = self._gemm(PrefillIn(mode=IN_SILU_MUL, gu_slabs=A.data_ptr(), gu_split=ns), ff.w2, None, self.inter, T, B, st)
-            self._resid(False, B, ns, T, st, final_norm=m.norm.weight if i + 1 == len(layers) else None)
+
+        self._dense_walk(T, self.tokens.data_ptr(), attention, st, final_norm=m.norm.weight)
         w = m.output.weight
         rc = L.teal_sparse_qkv_gemv_ld(self.x_last.data_ptr(), w.data_ptr(), w.stride(1), self.logits.data_ptr(), float("-inf"), float("-inf"),
                                        float("-inf"), self.dim, cfg.vocab_size, cfg.vocab_size, 0, self.code, self.ws.data_ptr(),

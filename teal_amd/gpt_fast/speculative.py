@@ -24,7 +24,7 @@ import torch
 from .. import _lib, runtime
 from .engine import DecodeEngine
 from .model import Transformer
-from .prefill import IN_SILU_MUL, IN_XT, MAX_T, PrefillEngine, PrefillIn
+from .prefill import MAX_T, PrefillEngine
 
 MAX_K = MAX_T - 1  # T = k + 1 verified rows per pass
 
@@ -60,25 +60,16 @@ class VerifyPass(PrefillEngine):
         split (slices of `lm_slabs` to sum)."""
         assert 1 <= T <= MAX_T and tokens.dtype == torch.int32 and pos.dtype == torch.int32
         m, cfg, L, st = self.model, self.model.config, self.L, runtime.stream_ptr()
-        A, B = self.slabs
-        rc = L.teal_prefill_resid_norm(m.tok_embeddings.weight.data_ptr(), tokens.data_ptr(), T, None, None, 0, None, self.eps, self.dim,
-                                       self.ht.data_ptr(), None, None, self.sumsq.data_ptr(), self.code, st)
-        if rc != 0:
-            _lib.check(rc, "teal_prefill_resid_norm")
-        for layer in m.layers:
-            at, ff = layer.attention, layer.feed_forward
-            ns = self._gemm(self._norm_in(layer.attention_norm.weight), at.wqkv, None, self.dim, T, A, st)
+
+        def attention(at, A, ns):
             kc, vc = self._caches(at)
             rc = L.teal_verify_attention(A.data_ptr(), ns, self.rope.data_ptr(), pos.data_ptr(), kc, vc, self.yt.data_ptr(),
                                          self.partials.data_ptr(), self.partials.numel() * 4, T, cfg.n_head, cfg.n_local_heads, cfg.head_dim,
                                          self.max_seq, self.code, st)
             if rc != 0:
                 _lib.check(rc, "teal_verify_attention")
-            ns = self._gemm(PrefillIn(mode=IN_XT, xt=self.yt.data_ptr()), at.wo, None, self.dim, T, B, st)
-            self._resid(False, B, ns, T, st)
-            ns = self._gemm(self._norm_in(layer.ffn_norm.weight), ff.w1, ff.w3, self.dim, T, A, st)
-            ns = self._gemm(PrefillIn(mode=IN_SILU_MUL, gu_slabs=A.data_ptr(), gu_split=ns), ff.w2, None, self.inter, T, B, st)
-            self._resid(False, B, ns, T, st)
+
+        self._dense_walk(T, tokens.data_ptr(), attention, st)
         return self._gemm(self._norm_in(m.norm.weight), m.output, None, self.dim, T, self.lm_slabs, st)
 
     @torch.no_grad()
