@@ -329,7 +329,22 @@ __global__ __launch_bounds__(1024) void gemv_fast_kernel(const void* in0, const 
     for (int j = 0; j < (PAIR ? 8 : 1); ++j) acc2[j] = 0.0f;
     {
         constexpr int STEP = U * RPW;
-        auto full = [&](const int e) { return e + STEP <= nloc; };
+        // List padding: once the wave's last chunk is compacted, lanes 0 .. npad - nloc - 1 append (last kept row << 16 | +0.0)
+        // until the list is a whole number of batches (npad = nloc rounded up to STEP; a.cap is a multiple of STEP — the launcher
+        // checks it — so no pad lands past the wave's list).  The stream loop then runs on npad and there is no tail batch: a
+        // partial last batch used to be REQUESTED only after the last full one had been consumed, two serial memory round trips at
+        // the end of every wave.  Pad loads address the row segment the last real entry addresses (lanes of one instruction
+        // coalesce).
+        // Bit identity with the guarded tail (and with sparse_gemv_kernel, which keeps it): a lane's accumulation chain is
+        // unchanged for every real entry; the pads follow them and add w * (+0.0) with w a weight of a KEPT row, i.e. +-0.0 for
+        // finite w.  An accumulator that starts at +0.0 and is updated by round-to-nearest fmas is never -0.0 (x + y = -0.0 only
+        // for x = y = -0.0), so acc + (+-0.0) = acc to the bit, NaN accumulators included.  int8: (q + 1152) * 0 and xs += 0.
+        // two_tau: |0| > tau is false, the weight is zeroed as for any row outside a keep set; with tau < 0 it stays and is
+        // multiplied by 0.  The one difference: a NON-FINITE weight in a wave's last kept row meets 0 in the pad lanes (NaN) where
+        // the tail zeroed the weight.  Model weights are finite; should that ever have to hold, peel the last consume and zero the
+        // pad lanes' weights there (a compare inside the steady-state loop costs every batch).
+        int npad = 0, last_row = 0;
+        auto full = [&](const int e) { return e + STEP <= npad; };
         auto issue = [&](wvec (&w)[U], wvec (&w2)[PAIR ? U : 1], float (&xv)[U], const int e0) {
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -373,17 +388,20 @@ __global__ __launch_bounds__(1024) void gemv_fast_kernel(const void* in0, const 
                 }
                 if ((mask >> lane) & 1ull) list[nloc + lane_rank(mask)] = (((uint32_t)cidx[k] * 64u + lane) << 16) | xr[k];
                 nloc += __popcll(mask);
+                if (mask) last_row = cidx[k] * 64 + 63 - __builtin_clzll(mask);  // from the scalar mask: no LDS read-back
             }
             if (k == 0 && KR > 1) {
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                if (full(0)) {
+                if (STEP <= nloc) {  // (real entries only: pads are appended after the last chunk)
                     issue(wa, w2a, xa, 0);
                     early = true;
                 }
             }
         }
+        npad = (nloc + STEP - 1) & ~(STEP - 1);
+        if (lane < npad - nloc) list[nloc + lane] = (uint32_t)last_row << 16;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -418,24 +436,6 @@ __global__ __launch_bounds__(1024) void gemv_fast_kernel(const void* in0, const 
             if (fa) issue(wa, w2a, xa, ebn);
             consume(wbb, w2b, xb);
             eb = ebn;
-        }
-        if (eb < nloc) {  // tail: clamp the entry index, zero the weights of clamped lanes
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int e = eb + u * RPW + g;
-                const bool ok = e < nloc;
-                const uint32_t ent = list[ok ? e : nloc - 1];
-                xa[u] = ok ? bits_to_float(ent & 0xFFFFu, BF16) : 0.0f;
-                wvec t = __builtin_nontemporal_load(reinterpret_cast<const wvec*>(wp + (size_t)(ent >> 16) * ldb));
-                if (!ok) t = wvec(0u);  // (int8: the zero activation alone drops the row and keeps it out of the bias sum)
-                wa[u] = t;
-                if constexpr (PAIR) {
-                    wvec t2 = __builtin_nontemporal_load(reinterpret_cast<const wvec*>(wp2 + (size_t)(ent >> 16) * ldb2));
-                    if (!ok) t2 = wvec(0u);
-                    w2a[u] = t2;
-                }
-            }
-            consume(wa, w2a, xa);
         }
     }
     stamp(5);
@@ -603,6 +603,8 @@ __global__ __launch_bounds__(1024) void gemv_fast_kernel(const void* in0, const 
 template <bool BF16, int MODE, bool PAIR, int LPR, int KR, bool EXACT, bool W8 = false>
 hipError_t launch_fast_e(const FastLaunch& f, hipStream_t st) {
     const dim3 grid(f.ntiles, f.split), block(1024);
+    // list padding rounds a wave's list up to whole batches of STEP = U * (64 / LPR) entries: the capacity must hold them
+    if (f.a.cap <= 0 || f.a.cap % (4 * (64 / LPR))) return hipErrorInvalidValue;
 #ifdef TEAL_DIAGNOSTICS
     if constexpr (!W8) {
         if (f.a.phase) {  // stamped instantiations (libteal_hip_diag.so: teal_set_phase_buffer), both activation dtypes
