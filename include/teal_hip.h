@@ -189,7 +189,12 @@ int teal_sparse_gateup_silu(const void* x, const void* w1T, const void* w3T, voi
                               * Otherwise (general kernel only: more slices than rounds, or lists beyond the LDS) the kept rows
                               * of a column tile form ONE ascending list of `total` entries and slice k sums entries
                               * [total * k / split, total * (k + 1) / split) (integer division).
-                              * Slab k holds the fp32 sum of its kept rows only; a slice that keeps nothing writes +0.0. */
+                              * Slab k holds the fp32 sum of its kept rows only; a slice that keeps nothing writes +0.0.
+                              * int4 weights (weight_bits = 4) cut the vector into UNITS of 32 activations instead, unit u =
+                              * elements 32 u .. 32 u + 31, whatever the producer: unit u belongs to slice u mod split and,
+                              * inside its workgroup, to wave (u div split) mod 16, so a wave's j-th unit is
+                              * slice + split * (wave + 16 j); a wave walks its units in passes of 2 (when it owns at most two)
+                              * or 4 consecutive j.  Scale and zero of unit u are those of group (32 u) div groupsize. */
 #define TEAL_OUT_QKV_ROPE 3  /* nseg == 3 = q | k | v of ONE fused wqkv image, RESID_NORM input: when the launch needs no
                               * split-K (and the lean kernel takes it: *nslabs_out = 0), its epilogue applies RoPE to q and
                               * to the new k row and appends k, v to the caches (gpt-fast/model.py:170-178): y[0] = rotated

@@ -341,9 +341,12 @@ __global__ __launch_bounds__(1024) void sparse_gemv_int4_kernel(const I4Args a) 
                     }
                     float Ls = (t[0] + t[1]) + (t[2] + t[3]);
                     if constexpr (NS == 8) Ls = Ls + ((t[7] + t[6]) + (t[5] + t[4]));
+                    // An empty split (sum 0) is skipped whatever its o holds, NaN included, as merge_head does (teal_attention.hip:
+                    // `if (ls > 0)`) and include/teal_hip.h promises: its o enters as 0 under the compare that already zeroes its
+                    // weight (for a finite o, o * 0 added nothing either)
                     float Os = 0.0f;
 #pragma unroll
-                    for (int q = 0; q < NS; ++q) Os = fmaf(ov[j][q], f[q] / Ls, Os);
+                    for (int q = 0; q < NS; ++q) Os = fmaf(st[j][q].y > 0.0f ? ov[j][q] : 0.0f, f[q] / Ls, Os);
                     xb[I0 + j] = float_to_bits<BF16>(Os);
                 }
             };
