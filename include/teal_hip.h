@@ -776,9 +776,20 @@ int teal_probe_row_reduce(const void* in_u32, void* scatter_u32, void* shuffle_u
 
 /* ---- introspection (pure functions of their arguments; teal_get_config also of the device's CU count) - */
 
-/* The geometry a GEMV of this shape would use: out[0..5) = {lanes_per_row, waves, split, unroll,
- * workgroups}. */
+/* The geometry of a plain rounded 16-bit GEMV of this shape BEFORE any adjustment for the output kind or the weight width
+ * (slab, pair and int8 launches choose their own: ask teal_fused_gemv_plan): out[0..5) = {lanes_per_row, waves, split,
+ * unroll, workgroups}.  `nseg` is ignored. */
 int teal_get_config(int Z, int N, int nseg, int* out);
+
+/* What teal_fused_gemv(in, out, Z, dtype, ws, ws_bytes, nslabs_out, stream) returns, reports in *nslabs_out and writes to
+ * out->desc on a device with num_cu CUs — from the launch's own plan (teal_amd/csrc/teal_gemv_plan.h), host only: no device is
+ * needed, nothing is launched and no data pointer is dereferenced (their nullness, alignment and identities are all that
+ * matters, so any values with those properties serve).  The caller's workspace is described instead of passed: ws_bytes (0 =
+ * none) and ws_prepared (it went through teal_workspace_init); it counts as 16-byte aligned.  out->slabs counts as plain
+ * memory.  Never TEAL_ERR_NO_DEVICE or TEAL_ERR_LAUNCH; TEAL_ERR_ARG also for num_cu <= 0.  The diagnostics build honours its
+ * switches as a launch does. */
+int teal_fused_gemv_plan(const teal_gemv_in_t* in, const teal_gemv_out_t* out, int Z, int dtype, int ws_prepared,
+                         size_t ws_bytes, int num_cu, int* nslabs_out);
 
 /* The launch teal_decode_attention_split* makes for this shape (teal_amd/csrc/teal_attention.hip; host only, no device needed):
  * out[0] = 1: the shape takes the grouped-query kernel (n_head / n_kv_head = 8 or 4 from its cache length on; never when

@@ -64,7 +64,7 @@ OPTIONAL_WITH_OVERRIDE = ("teal_decode_attention_split_roped", "teal_prefill_gem
                           "teal_batched_decode_attention", "teal_batched_sparse_gemm_slots", "teal_batched_decode_attention_slots",
                           "teal_batched_retire", "teal_sample_topk_slot", "teal_kv_copy_rows", "teal_decode_attention_split_plan",
                           "teal_token_logprobs", "teal_score_step", "teal_logit_adjust", "teal_sample_rows",
-                          "teal_batched_retire_stops", "teal_constrain_logits")
+                          "teal_batched_retire_stops", "teal_constrain_logits", "teal_fused_gemv_plan")
 
 # every symbol include/teal_hip.h declares
 EXPORTS = (
@@ -78,7 +78,7 @@ EXPORTS = (
     "teal_batched_sparse_gemm", "teal_batched_round_rows", "teal_batched_decode_attention_ws_bytes", "teal_batched_decode_attention",
     "teal_batched_sparse_gemm_slots", "teal_batched_decode_attention_slots", "teal_batched_retire", "teal_sample_topk_slot",
     "teal_kv_copy_rows", "teal_decode_attention_split_plan", "teal_token_logprobs", "teal_score_step",
-    "teal_logit_adjust", "teal_sample_rows", "teal_batched_retire_stops", "teal_constrain_logits",
+    "teal_logit_adjust", "teal_sample_rows", "teal_batched_retire_stops", "teal_constrain_logits", "teal_fused_gemv_plan",
 )
 
 # what libteal_hip_diag.so exports on top (include/teal_hip.h, #ifdef TEAL_DIAGNOSTICS); libteal_hip.so must export NONE of them
@@ -203,6 +203,8 @@ def _open(path: str, diag: bool) -> ctypes.CDLL:
     L.teal_get_config.argtypes = [ci, ci, ci, ctypes.POINTER(ci)]
     if hasattr(L, "teal_decode_attention_split_plan"):
         L.teal_decode_attention_split_plan.argtypes = [ci, ci, ci, ci, ci, ci, ctypes.POINTER(ci)]
+    if hasattr(L, "teal_fused_gemv_plan"):
+        L.teal_fused_gemv_plan.argtypes = [vp, vp, ci, ci, ci, sz, ci, ctypes.POINTER(ci)]
     if hasattr(L, "teal_prefill_gemm"):
         L.teal_prefill_gemm.argtypes = [vp, vp, ci, ci, vp, ci, ci, vp, sz, ci, ci, ci, ctypes.POINTER(ci), vp]  # (teal_prefill_in_t*, ...)
         L.teal_prefill_resid_norm.argtypes = [vp, vp, ci, vp, vp, ci, vp, cf, ci, vp, vp, vp, vp, ci, vp]

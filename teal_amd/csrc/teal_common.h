@@ -97,10 +97,6 @@ inline int num_cu_or(int dflt) {           // CU count of the current device, or
     return c && c->num_cu > 0 ? c->num_cu : dflt;
 }
 bool attention_device_init();              // teal_attention.hip: per-kernel attributes of the current device
-// teal_fused_gemv over int4 group-quantised weights (out->weight_bits == 4): teal_gemv_int4.hip
-int fused_gemv_i4(const teal_gemv_in_t* in, const teal_gemv_out_t* out, int Z, int dtype, void* ws, size_t ws_bytes,
-                  int* nslabs_out, hipStream_t st);
-
 // Diagnostics / tuning switches.  The PRODUCT library (libteal_hip.so) has none: the values below are compile-time
 // constants, no entry point can change how a launch is configured, and the only host-side state is the per-device
 // properties and the workspace registry (SURVEY 8(b) "Ownership").  libteal_hip_diag.so (the same sources with
@@ -123,6 +119,7 @@ inline unsigned long long* phase_next_region() {
     if (g_phase_stride) ++g_phase_seq;
     return p;
 }
+inline bool phase_stamping() { return g_phase != nullptr; }
 inline unsigned long long* phase_start_only() { return g_phase_stride ? nullptr : g_phase; }              // single-launch probes
 inline unsigned long long* phase_strided_only() { return (g_phase && g_phase_stride) ? phase_next_region() : nullptr; }
 #else
@@ -131,15 +128,19 @@ constexpr Config g_override = {0, 0, 0, 0};
 constexpr int g_wave_local = 1;
 constexpr int g_fast = 1;
 inline unsigned long long* phase_next_region() { return nullptr; }
+inline bool phase_stamping() { return false; }
 inline unsigned long long* phase_start_only() { return nullptr; }
 inline unsigned long long* phase_strided_only() { return nullptr; }
 #endif
 // the description of the launch a call made (kernel instantiation + grid, as rocprofv3 prints it) goes to the CALLER's
 // buffer (teal_gemv_out_t.desc); the diagnostics build also keeps the last one for teal_last_launch_desc
-inline void publish_desc(const char* s, char* dst, int dst_bytes) {
+// (`launched` false — a host-only query — leaves the last one alone)
+inline void publish_desc(const char* s, char* dst, int dst_bytes, bool launched = true) {
     if (dst && dst_bytes > 0) snprintf(dst, (size_t)dst_bytes, "%s", s);
 #ifdef TEAL_DIAGNOSTICS
-    snprintf(g_last_desc, sizeof g_last_desc, "%s", s);
+    if (launched) snprintf(g_last_desc, sizeof g_last_desc, "%s", s);
+#else
+    (void)launched;
 #endif
 }
 
@@ -164,11 +165,12 @@ inline float* ws_slabs(void* ws) { return reinterpret_cast<float*>(reinterpret_c
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // GEMV launchers, one translation unit per (weight width, activation dtype) so that the ~290 kernel
-// instantiations compile in parallel: teal_gemv_{w16,w8}_{f16,bf16}.hip
-hipError_t launch_gemv_w16_f16(const Params& p, size_t lds, const Config& c, hipStream_t st);
-hipError_t launch_gemv_w16_bf16(const Params& p, size_t lds, const Config& c, hipStream_t st);
-hipError_t launch_gemv_w8_f16(const Params& p, size_t lds, const Config& c, hipStream_t st);
-hipError_t launch_gemv_w8_bf16(const Params& p, size_t lds, const Config& c, hipStream_t st);
+// instantiations compile in parallel: teal_gemv_{w16,w8}_{f16,bf16}.hip.  lpr, krt: the tile width (lanes per row) and the
+// register-cache depth of the plan (teal_gemv_plan.h)
+hipError_t launch_gemv_w16_f16(const Params& p, size_t lds, int lpr, int krt, hipStream_t st);
+hipError_t launch_gemv_w16_bf16(const Params& p, size_t lds, int lpr, int krt, hipStream_t st);
+hipError_t launch_gemv_w8_f16(const Params& p, size_t lds, int lpr, int krt, hipStream_t st);
+hipError_t launch_gemv_w8_bf16(const Params& p, size_t lds, int lpr, int krt, hipStream_t st);
 
 __device__ __forceinline__ float bits_to_float(uint32_t b16, bool bf16) {
     if (bf16) return __uint_as_float(b16 << 16);

@@ -36,7 +36,8 @@ struct FastArgs {
     int sum32;                      // TEAL_OUT_SLAB_SUM: y is fp32 [ncols] and receives the unrounded sum over the row slices (slice order)
 };
 
-// Launch description filled by run_gemv when the shape qualifies (teal_kernels.hip: fast_eligible)
+// Launch description, part of the launch plan: filled from the plan's facts when the shape qualifies (teal_gemv_plan.h:
+// lean_shape, fill_fast); run_gemv adds the stamp buffer and launches it
 struct FastLaunch {
     const void* in0; const void* in1; const void* in2; const int* row_index;
     int Z, nslabs; float eps;

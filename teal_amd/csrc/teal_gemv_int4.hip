@@ -29,6 +29,7 @@
 // leaves either rounded outputs or its fp32 split-K partials as slabs for the next launch's producer, so an int4 layer is
 // 5 launches too.
 #include "teal_common.h"
+#include "teal_gemv_plan.h"
 
 #include <limits.h>
 
@@ -535,20 +536,25 @@ static hipError_t launch_i4(const I4Args& a, int mode, dim3 grid, size_t lds, hi
     return hipGetLastError();
 }
 
-// One launch over int4 weights: [producer] -> mask + compaction -> gathered GEMV over every segment (teal_fused_gemv with
-// weight_bits = 4, and the plain entry point below).  split-K factor: enough slices to cover the CUs, at most 8, every
-// wave of every slice owning at least one unit; without a destination for the partials (no prepared workspace and no
-// slabs requested) the launch keeps every unit of a tile in one workgroup.
-int fused_gemv_i4(const teal_gemv_in_t* in, const teal_gemv_out_t* out, int Z, int dtype, void* ws, size_t ws_bytes,
-                  int* nslabs_out, hipStream_t st) {
+// The plan of one launch over int4 weights (teal_fused_gemv with weight_bits = 4, and the plain entry point below): pure host
+// arithmetic on the request, the CU count and whether the caller's workspace is a prepared one — no HIP call.  split-K factor:
+// enough slices to cover the CUs, at most 8, every wave of every slice owning at least one unit; without a destination for the
+// partials (no prepared workspace and no slabs requested) the launch keeps every unit of a tile in one workgroup.
+struct I4Plan {
+    I4Args a;        // complete but for the stamp buffer
+    int ntiles, split, kind;
+    size_t lds;
+    char desc[160];
+};
+
+static int plan_i4(const teal_gemv_in_t* in, const teal_gemv_out_t* out, int Z, int dtype, const GemvMemory& mem, int num_cu,
+                   I4Plan& pl) {
     const int G = out->groupsize;
     if (G != 32 && G != 64 && G != 128 && G != 256) return TEAL_ERR_ARG;
     if (Z <= 0 || (Z % G) || Z > 65536) return TEAL_ERR_SHAPE;
     if (out->nseg < 1 || out->nseg > 3) return TEAL_ERR_ARG;
     if (out->mode != TEAL_OUT_ROUNDED && out->mode != TEAL_OUT_SLABS) return TEAL_ERR_ARG;  // no paired gate|up form
-    DeviceCtx* dc = device_ctx();
-    if (!dc) return TEAL_ERR_NO_DEVICE;
-    I4Args a = {};
+    I4Args& a = pl.a = {};
     a.nseg = out->nseg; a.Z = Z; a.gshift = G == 32 ? 5 : (G == 64 ? 6 : (G == 128 ? 7 : 8));
     int ntiles = 0, N = 0;
     for (int i = 0; i < out->nseg; ++i) {
@@ -566,29 +572,16 @@ int fused_gemv_i4(const teal_gemv_in_t* in, const teal_gemv_out_t* out, int Z, i
         ntiles += nc / 128;
         N += nc;
     }
-    size_t lds = 0;
+    const int rc = check_producer(in, Z, kProducerInt4);
+    if (rc != TEAL_OK) return rc;
+    pl.lds = 0;
     switch (in->mode) {
-        case TEAL_IN_PLAIN:
-            if (!in->x) return TEAL_ERR_ARG;
-            a.x = reinterpret_cast<const uint16_t*>(in->x);
-            break;
-        case TEAL_IN_SILU_MUL:
-            if (!in->x) return TEAL_ERR_ARG;
-            a.x = reinterpret_cast<const uint16_t*>(in->x);
-            break;
         case TEAL_IN_ATTN_MERGE:
-            if (!in->x || (in->att_head_dim != 64 && in->att_head_dim != 128) || Z % in->att_head_dim ||
-                (in->att_nsplit != 0 && in->att_nsplit != 4 && in->att_nsplit != 8))
-                return TEAL_ERR_ARG;
             a.att = reinterpret_cast<const float*>(in->x);
             a.att_hd = in->att_head_dim;
             a.att_ns = in->att_nsplit ? in->att_nsplit : 4;
             break;
         case TEAL_IN_RESID_NORM:
-            if (!in->resid_in || !in->norm_weight || in->nslabs < 0 || (in->nslabs > 0 && !in->slabs)) return TEAL_ERR_ARG;
-            if (in->resid_out == in->resid_in && !in->row_index) return TEAL_ERR_ARG;  // must ping-pong
-            if (in->nslabs > 0 && (!in->slabs_interleaved || in->nslabs > 8 || !aligned16(in->slabs))) return TEAL_ERR_ARG;
-            if (Z > 16384) return TEAL_ERR_SHAPE;  // 16 elements per thread, 32 KB of LDS
             a.x = reinterpret_cast<const uint16_t*>(in->resid_in);
             a.row_index = in->row_index;
             a.slabs = in->slabs;
@@ -596,57 +589,73 @@ int fused_gemv_i4(const teal_gemv_in_t* in, const teal_gemv_out_t* out, int Z, i
             a.norm_w = reinterpret_cast<const uint16_t*>(in->norm_weight);
             a.eps = in->eps;
             a.resid_out = reinterpret_cast<uint16_t*>(in->resid_out);
-            lds = (size_t)Z * 2;
+            pl.lds = (size_t)Z * 2;
             break;
-        default: return TEAL_ERR_ARG;  // TEAL_IN_MASKED: no int4 form
+        default:  // PLAIN, SILU_MUL
+            a.x = reinterpret_cast<const uint16_t*>(in->x);
+            break;
     }
     const int nunits = Z / 32;
-    int split = dc->num_cu / ntiles;
+    int split = num_cu / ntiles;
     if (split > 8) split = 8;
     if (split * 16 > nunits) split = nunits / 16;  // every wave of every slice owns at least one 32-row unit
     if (split < 1) split = 1;
     if (out->mode == TEAL_OUT_SLABS) {
-        if (!out->slabs || !aligned16(out->slabs) || ws_prepared(out->slabs, out->slabs_bytes)) return TEAL_ERR_ARG;
+        if (!out->slabs || !aligned16(out->slabs) || mem.slabs_prepared) return TEAL_ERR_ARG;
         a.ws = out->slabs;
         if (out->slabs_interleaved) { a.ws_es = (split + 3) & ~3; a.ws_ss = 1; }
         else { a.ws_es = 1; a.ws_ss = N; }
         if (out->slabs_bytes < (size_t)(out->slabs_interleaved ? a.ws_es : split) * N * sizeof(float)) return TEAL_ERR_WORKSPACE;
     } else if (split > 1) {
-        if (!ws_prepared(ws, ws_bytes) || ntiles > kTicketTiles) split = 1;
+        if (!mem.ws_prepared || ntiles > kTicketTiles) split = 1;
         else {
             a.ws_es = (split + 3) & ~3; a.ws_ss = 1;
-            if (ws_bytes - kWsHeaderBytes < (size_t)a.ws_es * N * sizeof(float)) return TEAL_ERR_WORKSPACE;
-            a.ws = ws_slabs(ws);
-            a.ticket = ws_tickets(ws);
+            if (mem.ws_bytes - kWsHeaderBytes < (size_t)a.ws_es * N * sizeof(float)) return TEAL_ERR_WORKSPACE;
+            a.ws = ws_slabs(mem.ws);
+            a.ticket = ws_tickets(mem.ws);
         }
     }
-    const dim3 grid(ntiles, split);
     // a wave's units: up to two -> its lane groups share each unit; more -> passes of four, a unit per lane group
     const int upw = (nunits + split * 16 - 1) / (split * 16);
-    const int kind = upw <= 2 ? kI4Share : kI4Group;
-    hipError_t e;
-#define TEAL_I4_LAUNCH(BF, PH) \
-    (kind == kI4Share ? launch_i4<BF, kI4Share, PH>(a, in->mode, grid, lds, st) : launch_i4<BF, kI4Group, PH>(a, in->mode, grid, lds, st))
+    pl.ntiles = ntiles;
+    pl.split = split;
+    pl.kind = upw <= 2 ? kI4Share : kI4Group;
+    pl.desc[0] = 0;
+    if (out->desc || kDiagnostics)
+        snprintf(pl.desc, sizeof pl.desc, "sparse_gemv_int4_kernel<%s,%d,%d,false> grid (%d,%d) x 1024", dtype == TEAL_BF16 ? "true" : "false",
+                 in->mode, pl.kind, ntiles, split);
+    return TEAL_OK;
+}
+
+// plan, then launch what the plan says (not at a launch site: the plan alone)
+int fused_gemv_i4(const teal_gemv_in_t* in, const teal_gemv_out_t* out, int Z, int dtype, const GemvMemory& mem, int* nslabs_out,
+                  const GemvSite& site) {
+    I4Plan pl;
+    const int rc = plan_i4(in, out, Z, dtype, mem, site.num_cu, pl);
+    if (rc != TEAL_OK) return rc;
+    if (site.launch) {
+        const dim3 grid(pl.ntiles, pl.split);
+        I4Args& a = pl.a;
+        hipError_t e;
+#define TEAL_I4_LAUNCH(BF, PH)                                                                    \
+    (pl.kind == kI4Share ? launch_i4<BF, kI4Share, PH>(a, in->mode, grid, pl.lds, site.st) \
+                         : launch_i4<BF, kI4Group, PH>(a, in->mode, grid, pl.lds, site.st))
 #ifdef TEAL_DIAGNOSTICS
-    if (g_phase && dtype == TEAL_F16) {  // measurement: the stamping instantiation (fp16 only; libteal_hip_diag.so)
-        a.phase = phase_next_region();
-        e = TEAL_I4_LAUNCH(false, true);
-    } else
+        if (g_phase && dtype == TEAL_F16) {  // measurement: the stamping instantiation (fp16 only; libteal_hip_diag.so)
+            a.phase = phase_next_region();
+            e = TEAL_I4_LAUNCH(false, true);
+        } else
 #endif
-    if (dtype == TEAL_BF16) {
-        e = TEAL_I4_LAUNCH(true, false);
-    } else {
-        e = TEAL_I4_LAUNCH(false, false);
-    }
+        if (dtype == TEAL_BF16) {
+            e = TEAL_I4_LAUNCH(true, false);
+        } else {
+            e = TEAL_I4_LAUNCH(false, false);
+        }
 #undef TEAL_I4_LAUNCH
-    if (e != hipSuccess) return TEAL_ERR_LAUNCH;
-    if (out->desc || kDiagnostics) {
-        char d[160];
-        snprintf(d, sizeof d, "sparse_gemv_int4_kernel<%s,%d,%d,false> grid (%d,%d) x 1024", dtype == TEAL_BF16 ? "true" : "false",
-                 in->mode, kind, ntiles, split);
-        publish_desc(d, out->desc, out->desc_bytes);
+        if (e != hipSuccess) return TEAL_ERR_LAUNCH;
     }
-    if (nslabs_out) *nslabs_out = split;
+    if (pl.desc[0]) publish_desc(pl.desc, out->desc, out->desc_bytes, site.launch);
+    if (nslabs_out) *nslabs_out = pl.split;
     return TEAL_OK;
 }
 
@@ -678,5 +687,7 @@ extern "C" int teal_sparse_qkv_gemv_i4(const void* x, const void* wq, const void
     out.mode = TEAL_OUT_ROUNDED;
     out.weight_bits = 4;
     out.groupsize = groupsize;
-    return fused_gemv_i4(&in, &out, Z, dtype, ws, ws_bytes, nullptr, reinterpret_cast<hipStream_t>(stream));
+    GemvSite site;
+    if (!gemv_site(reinterpret_cast<hipStream_t>(stream), site)) return TEAL_ERR_NO_DEVICE;
+    return fused_gemv_i4(&in, &out, Z, dtype, {ws, ws_bytes, ws_prepared(ws, ws_bytes), nullptr, 0, false}, nullptr, site);
 }

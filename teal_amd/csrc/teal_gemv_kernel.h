@@ -715,75 +715,47 @@ __global__ __launch_bounds__(WAVES * 64) void sparse_gemv_kernel(const Params p)
 }
 
 
-// ---- launch dispatch: runtime (lanes per row, waves, unroll, producer mode, register-cache depth) -> template
-//      instantiation, for one (activation dtype, weight width) quadrant -------------------------------------
+// ---- launch dispatch: the plan's (lanes per row, producer mode, register-cache depth) -> template instantiation, for one
+//      (activation dtype, weight width) quadrant.  Every instantiation is a 16-wave workgroup with unroll 4 (the production
+//      geometry; the 8-wave and unroll-8 variants of round 1 were sweep-only and are no longer built); int8 weights stop at
+//      256-column tiles.  Nothing here decides: a combination the plan cannot name is hipErrorInvalidValue. ----------------
 
-// which instantiations exist: 16-wave workgroups, unroll 4 (the production geometry), every tile width / producer /
-// cache depth.  The 8-wave and unroll-8 variants of round 1 were sweep-only (measured no better; 4-wave workgroups
-// worse: the launch is bound by HBM and by instruction issue in the prologue, not by dispatch) and are no longer built.
-template <bool W8, int LPR, int WAVES, int U, int MODE, int KRT, bool PAIR>
-constexpr bool variant_built() {
-    if (WAVES != 16 || U != 4) return false;
-    return W8 ? LPR <= 32 : true;
-}
-
-template <bool BF16, bool W8, int LPR, int WAVES, int U, int MODE, int KRT, bool PAIR>
-hipError_t launch_gemv_k(const Params& p, size_t lds, hipStream_t st) {
-    const dim3 grid(p.ntiles * p.split), block(WAVES * 64);
-    if constexpr (variant_built<W8, LPR, WAVES, U, MODE, KRT, PAIR>()) {
-        hipLaunchKernelGGL((sparse_gemv_kernel<LPR, WAVES, U, BF16, MODE, KRT, PAIR, W8>), grid, block, lds, st, p);
-        return hipGetLastError();
-    } else {
+template <bool BF16, bool W8, int LPR, int MODE, bool PAIR>
+hipError_t launch_gemv_k(const Params& p, size_t lds, int krt, hipStream_t st) {
+    const dim3 grid(p.ntiles * p.split), block(16 * 64);
+    if constexpr (W8 && LPR > 32) {
         return hipErrorInvalidValue;
-    }
-}
-
-// register-cache depth: smallest KRT with KRT * WAVES * 64 >= Z, or what the wave-local slice needs (p.krt);
-// longer vectors use KRT = 16 plus the reload path
-template <bool BF16, bool W8, int LPR, int WAVES, int U, int MODE, bool PAIR>
-hipError_t launch_gemv_m(const Params& p, size_t lds, hipStream_t st) {
-    if constexpr (WAVES == 16) {
-        const int owned = p.krt ? p.krt : (((p.Z + 63) >> 6) + WAVES - 1) / WAVES;
-        if (owned <= 4) return launch_gemv_k<BF16, W8, LPR, WAVES, U, MODE, 4, PAIR>(p, lds, st);
-        if (owned <= 8) return launch_gemv_k<BF16, W8, LPR, WAVES, U, MODE, 8, PAIR>(p, lds, st);
-    }
-    return launch_gemv_k<BF16, W8, LPR, WAVES, U, MODE, 16, PAIR>(p, lds, st);
-}
-
-template <bool BF16, bool W8, int LPR, int WAVES, int U>
-hipError_t launch_gemv_t(const Params& p, size_t lds, hipStream_t st) {
-    if (p.in.mode == 0 && !p.pair) return launch_gemv_m<BF16, W8, LPR, WAVES, U, 0, false>(p, lds, st);
-    if (p.pair) return p.in.mode == 1 ? launch_gemv_m<BF16, W8, LPR, WAVES, U, 1, true>(p, lds, st) : hipErrorInvalidValue;
-    if (p.in.mode == 1) return launch_gemv_m<BF16, W8, LPR, WAVES, U, 1, false>(p, lds, st);
-    if (p.in.mode == 2) return launch_gemv_m<BF16, W8, LPR, WAVES, U, 2, false>(p, lds, st);
-    if (p.in.mode == 3) return launch_gemv_m<BF16, W8, LPR, WAVES, U, 3, false>(p, lds, st);
-    if (p.in.mode == 4) return launch_gemv_m<BF16, W8, LPR, WAVES, U, 4, false>(p, lds, st);
-    return hipErrorInvalidValue;
-}
-
-template <bool BF16, bool W8, int LPR, int WAVES>
-hipError_t launch_gemv_u(const Params& p, size_t lds, int unroll, hipStream_t st) {
-    switch (unroll) {
-        case 4: return launch_gemv_t<BF16, W8, LPR, WAVES, 4>(p, lds, st);
-        default: return hipErrorInvalidValue;
+    } else {
+        switch (krt) {
+            case 4: hipLaunchKernelGGL((sparse_gemv_kernel<LPR, 16, 4, BF16, MODE, 4, PAIR, W8>), grid, block, lds, st, p); break;
+            case 8: hipLaunchKernelGGL((sparse_gemv_kernel<LPR, 16, 4, BF16, MODE, 8, PAIR, W8>), grid, block, lds, st, p); break;
+            case 16: hipLaunchKernelGGL((sparse_gemv_kernel<LPR, 16, 4, BF16, MODE, 16, PAIR, W8>), grid, block, lds, st, p); break;
+            default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
     }
 }
 
 template <bool BF16, bool W8, int LPR>
-hipError_t launch_gemv_w(const Params& p, size_t lds, const Config& c, hipStream_t st) {
-    switch (c.waves) {
-        case 16: return launch_gemv_u<BF16, W8, LPR, 16>(p, lds, c.unroll, st);
+hipError_t launch_gemv_m(const Params& p, size_t lds, int krt, hipStream_t st) {
+    if (p.in.mode == 0 && !p.pair) return launch_gemv_k<BF16, W8, LPR, 0, false>(p, lds, krt, st);
+    if (p.pair) return p.in.mode == 1 ? launch_gemv_k<BF16, W8, LPR, 1, true>(p, lds, krt, st) : hipErrorInvalidValue;
+    switch (p.in.mode) {  // (the order of the instantiations is the order of the kernels in the code object)
+        case 1: return launch_gemv_k<BF16, W8, LPR, 1, false>(p, lds, krt, st);
+        case 2: return launch_gemv_k<BF16, W8, LPR, 2, false>(p, lds, krt, st);
+        case 3: return launch_gemv_k<BF16, W8, LPR, 3, false>(p, lds, krt, st);
+        case 4: return launch_gemv_k<BF16, W8, LPR, 4, false>(p, lds, krt, st);
         default: return hipErrorInvalidValue;
     }
 }
 
 template <bool BF16, bool W8>
-hipError_t launch_gemv_q(const Params& p, size_t lds, const Config& c, hipStream_t st) {
-    switch (c.lpr) {
-        case 8: return launch_gemv_w<BF16, W8, 8>(p, lds, c, st);
-        case 16: return launch_gemv_w<BF16, W8, 16>(p, lds, c, st);
-        case 32: return launch_gemv_w<BF16, W8, 32>(p, lds, c, st);
-        case 64: return launch_gemv_w<BF16, W8, 64>(p, lds, c, st);
+hipError_t launch_gemv_q(const Params& p, size_t lds, int lpr, int krt, hipStream_t st) {
+    switch (lpr) {
+        case 8: return launch_gemv_m<BF16, W8, 8>(p, lds, krt, st);
+        case 16: return launch_gemv_m<BF16, W8, 16>(p, lds, krt, st);
+        case 32: return launch_gemv_m<BF16, W8, 32>(p, lds, krt, st);
+        case 64: return launch_gemv_m<BF16, W8, 64>(p, lds, krt, st);
         default: return hipErrorInvalidValue;
     }
 }
