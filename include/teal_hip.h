@@ -497,6 +497,15 @@ int teal_batched_decode_attention(const float* qkv_slabs, int split, const void*
 int teal_batched_sparse_gemm_slots(const teal_prefill_in_t* in, const teal_batched_segs_t* segs, const void* w0T, int ld0, int n0,
                                    const void* w1T, int ld1, int n1, float* slabs, size_t slabs_bytes, int Z, int B, const int32_t* active,
                                    int32_t* counts, int dtype, int* split_out, void* stream);
+/* teal_batched_sparse_gemm_slots with a threshold per slot: taus (device fp32 [3][8], segment-major and slot-minor, 32-byte
+ * aligned) — slot b keeps row m under segment s iff its bit of active[0] is set and float32(|x_b[m]|) > taus[s][b].  segs->tau is
+ * ignored; segs->col_end and nseg hold as before, rows of taus past nseg - 1 are not consulted.  Read once per workgroup together
+ * with active[0].  An inactive slot's column is never consulted: whatever it holds (a finished request's level, NaN) changes
+ * nothing.  The union, the dealing of rows, the sums' order and the counts are those of teal_batched_sparse_gemm_slots: with every
+ * column equal to segs->tau the outputs are the same words.  taus null: TEAL_ERR_ARG; misaligned: TEAL_ERR_ALIGN. */
+int teal_batched_sparse_gemm_slot_taus(const teal_prefill_in_t* in, const teal_batched_segs_t* segs, const void* w0T, int ld0, int n0,
+                                       const void* w1T, int ld1, int n1, float* slabs, size_t slabs_bytes, int Z, int B,
+                                       const int32_t* active, const float* taus, int32_t* counts, int dtype, int* split_out, void* stream);
 /* teal_batched_decode_attention where the workgroups of a slot whose bit of active[0] is clear exit at once: no cache row written,
  * no partials, yt slot zero.  Same grid and nsplit as the unmasked launch at the same B (nsplit never depends on the active set). */
 int teal_batched_decode_attention_slots(const float* qkv_slabs, int split, const void* rope, const int32_t* pos, const int32_t* active,

@@ -64,7 +64,8 @@ OPTIONAL_WITH_OVERRIDE = ("teal_decode_attention_split_roped", "teal_prefill_gem
                           "teal_batched_decode_attention", "teal_batched_sparse_gemm_slots", "teal_batched_decode_attention_slots",
                           "teal_batched_retire", "teal_sample_topk_slot", "teal_kv_copy_rows", "teal_decode_attention_split_plan",
                           "teal_token_logprobs", "teal_score_step", "teal_logit_adjust", "teal_sample_rows",
-                          "teal_batched_retire_stops", "teal_constrain_logits", "teal_fused_gemv_plan")
+                          "teal_batched_retire_stops", "teal_constrain_logits", "teal_fused_gemv_plan",
+                          "teal_batched_sparse_gemm_slot_taus")
 
 # every symbol include/teal_hip.h declares
 EXPORTS = (
@@ -79,6 +80,7 @@ EXPORTS = (
     "teal_batched_sparse_gemm_slots", "teal_batched_decode_attention_slots", "teal_batched_retire", "teal_sample_topk_slot",
     "teal_kv_copy_rows", "teal_decode_attention_split_plan", "teal_token_logprobs", "teal_score_step",
     "teal_logit_adjust", "teal_sample_rows", "teal_batched_retire_stops", "teal_constrain_logits", "teal_fused_gemv_plan",
+    "teal_batched_sparse_gemm_slot_taus",
 )
 
 # what libteal_hip_diag.so exports on top (include/teal_hip.h, #ifdef TEAL_DIAGNOSTICS); libteal_hip.so must export NONE of them
@@ -227,6 +229,8 @@ def _open(path: str, diag: bool) -> ctypes.CDLL:
         L.teal_batched_decode_attention_slots.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, ci, ci, ci, vp]
         L.teal_batched_retire.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp]
         L.teal_sample_topk_slot.argtypes = [vp, ci, ci, ci, cf, vp, vp, vp, vp, ci, vp, sz, vp, ci, vp]
+    if hasattr(L, "teal_batched_sparse_gemm_slot_taus"):
+        L.teal_batched_sparse_gemm_slot_taus.argtypes = [vp, vp, vp, ci, ci, vp, ci, ci, vp, sz, ci, ci, vp, vp, vp, ci, ctypes.POINTER(ci), vp]
     if hasattr(L, "teal_kv_copy_rows"):
         L.teal_kv_copy_rows.argtypes = [vp, vp, ci, ci, ci, ci, sz, sz, vp]
     if hasattr(L, "teal_token_logprobs"):

@@ -24,6 +24,7 @@ constexpr int kBatchMax = 8;           // sequences per launch: one 16-byte word
 constexpr int kBPhaseRows = 2048;      // rows a workgroup stages per phase (128 groups of 16)
 constexpr int kBChunks = kBPhaseRows / 64;
 constexpr int kBCountStride = 9;       // counts[slice][segment][9]: kept per sequence (0 .. 7), union (8)
+constexpr int kBTauOff = (kBPhaseRows * 28 + (2 * kBChunks + 1 + 16 * 3 * kBCountStride) * 4 + 15) & ~15;  // LDS: the parked thresholds
 constexpr int kBAttnChunk = 32;        // context rows a workgroup stages per round
 constexpr int kBAttnMaxQ = 16;         // query heads of one KV head per workgroup
 constexpr int kBAttnMaxSplit = 64;
@@ -32,6 +33,11 @@ struct BSegs {
     int nseg;
     int end[3];   // exclusive end column of each segment over [0, n_total)
     float tau[3];
+};
+struct BSegsTaus {  // the per-slot form: the threshold table in the place of the three thresholds
+    int nseg;
+    int end[3];
+    const float* taus;  // device fp32 [3][8]: segment-major, slot-minor
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -48,11 +54,16 @@ struct BSegs {
 // SLOTS: `active` (device int32, bit b = slot b runs) is read once per workgroup; an inactive slot's activation is +0 and never
 // kept, so it adds nothing to the union, the counts or any slab (its own columns are exactly 0).  SLOTS = false is the code of
 // teal_batched_sparse_gemm.
-template <bool BF16, int NP, int PROD, bool SLOTS>
-__global__ __launch_bounds__(1024) void batched_gemm_kernel(const SlabProd pr, const BSegs sg, const uint16_t* __restrict__ w0, const int ld0,
+// TAUS (with SLOTS only): slot b's threshold under segment s is taus[s][b] (device fp32 [3][8]); sg.tau is not read.  An inactive
+// slot's column is never consulted (`live` is false before the compare).  The table's address travels in the segments argument
+// (BSegsTaus), so the other instantiations keep their arguments and their code.
+template <bool BF16, int NP, int PROD, bool TAUS, bool SLOTS>
+__global__ __launch_bounds__(1024) void batched_gemm_kernel(const SlabProd pr, const std::conditional_t<TAUS, BSegsTaus, BSegs> sg,
+                                                            const uint16_t* __restrict__ w0, const int ld0,
                                                             const uint16_t* __restrict__ w1, const int ld1, const int tiles0,
                                                             float* __restrict__ slabs, int* __restrict__ counts, const int Z, const int n_total,
                                                             const int* __restrict__ active) {
+    static_assert(SLOTS || !TAUS, "per-slot thresholds need the slot form");
     constexpr int WAVES = 16, CPL = 4, BN = 256, U = NP <= 2 ? 8 : 4, PHASE_GROUPS = kBPhaseRows / 16;
     extern __shared__ __align__(16) unsigned char smem[];
     u32x4* xs = reinterpret_cast<u32x4*>(smem);                                     // [kBPhaseRows] activations of the phase's rows
@@ -73,10 +84,12 @@ __global__ __launch_bounds__(1024) void batched_gemm_kernel(const SlabProd pr, c
     const int sfirst = (c0 >= e0 ? 1 : 0) + (c0 >= e1 ? 1 : 0);
     const int slast = (c0 + BN - 1 >= e0 ? 1 : 0) + (c0 + BN - 1 >= e1 ? 1 : 0);
     const int nls = slast - sfirst + 1;
-    const float tau_s[3] = {sg.tau[0], sg.tau[1], sg.tau[2]};
-    float tau[3];
+    [[maybe_unused]] float tau[3];
+    if constexpr (!TAUS) {
+        const float tau_s[3] = {sg.tau[0], sg.tau[1], sg.tau[2]};
 #pragma unroll
-    for (int i = 0; i < 3; ++i) tau[i] = sfirst + i == 0 ? tau_s[0] : (sfirst + i == 1 ? tau_s[1] : tau_s[2]);
+        for (int i = 0; i < 3; ++i) tau[i] = sfirst + i == 0 ? tau_s[0] : (sfirst + i == 1 ? tau_s[1] : tau_s[2]);
+    }
     const int lc = c0 + lane * CPL;  // this lane's four columns: one segment (boundaries are multiples of 8 columns)
     const uint32_t lshift = 8u * (uint32_t)((lc >= e0 ? 1 : 0) + (lc >= e1 ? 1 : 0) - sfirst);
     // segments whose kept counts this tile reports: those that start in it
@@ -91,7 +104,27 @@ __global__ __launch_bounds__(1024) void batched_gemm_kernel(const SlabProd pr, c
     if (count_segs && lane < 3 * kBCountStride) mycnt[lane] = 0;
 
     uint32_t on = 0xFFu;  // slots that run
-    if constexpr (SLOTS) on = (uint32_t)__builtin_amdgcn_readfirstlane(active[0]) & 0xFFu;
+    if constexpr (TAUS) {
+        // the threshold rows of the tile's segments: three 32-byte scalar loads whose addresses come from the arguments alone, so
+        // they are in flight together with the active word's and one wait serves all four.  They are then parked in LDS — a copy
+        // per wave, written and read back by the same lanes, so no barrier — and fetched again by each phase's staging: 24 scalar
+        // registers held across the streaming loop are registers its pipeline needs.
+        float t[3][8];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const float* __restrict__ row = sg.taus + 8 * min(sfirst + i, 2);
+#pragma unroll
+            for (int b = 0; b < 8; ++b) t[i][b] = row[b];
+        }
+        on = (uint32_t)__builtin_amdgcn_readfirstlane(active[0]) & 0xFFu;
+        float* park = reinterpret_cast<float*>(smem + kBTauOff) + wave * 24;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int b = 0; b < 8; ++b) park[i * 8 + b] = t[i][b];
+    } else if constexpr (SLOTS) {
+        on = (uint32_t)__builtin_amdgcn_readfirstlane(active[0]) & 0xFFu;
+    }
     const int ngroups = Z >> 4;
     const int nj = (ngroups - slice + split - 1) / split;  // row groups of this slice
     const uint16_t* wbase = (second ? w1 : w0) + (size_t)(second ? tile - tiles0 : tile) * BN;
@@ -132,6 +165,14 @@ __global__ __launch_bounds__(1024) void batched_gemm_kernel(const SlabProd pr, c
             for (int s = 0; s < 8; ++s) rstd[s] = rsqrtf(wave_sum_f(pw[s >> 2][s & 3]) / (float)Z + pr.eps);
         }
         // ---- staging: the rows' activations (16-bit, what the module path holds) and their keep masks
+        [[maybe_unused]] float tslot[3][8];  // TAUS: [local segment][slot]
+        if constexpr (TAUS) {
+            const float* park = reinterpret_cast<const float*>(smem + kBTauOff) + wave * 24;
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int b = 0; b < 8; ++b) tslot[i][b] = park[i * 8 + b];
+        }
         for (int r = tid; r < nrows; r += 1024) {
             const uint32_t m = (uint32_t)(slice + split * (jb + (r >> 4))) * 16u + (uint32_t)(r & 15);
             float x[8];
@@ -163,7 +204,7 @@ __global__ __launch_bounds__(1024) void batched_gemm_kernel(const SlabProd pr, c
                     x[s] = live ? x[s] : 0.0f;  // slots of absent or inactive sequences: zero, never kept
 #pragma unroll
                     for (int i = 0; i < 3; ++i)
-                        if (i < nls && live && keep_rule(x[s], tau[i])) mk |= 1u << (8 * i + s);
+                        if (i < nls && live && keep_rule(x[s], TAUS ? tslot[i][s] : tau[i])) mk |= 1u << (8 * i + s);
                 } else {
                     x[s] = s < pr.rows ? x[s] : 0.0f;  // slots of absent sequences: zero, never kept
 #pragma unroll
@@ -521,10 +562,10 @@ __global__ __launch_bounds__(64) void batched_retire_kernel(int* __restrict__ st
 using namespace teal;
 
 namespace {
-// teal_batched_sparse_gemm (active == nullptr) and teal_batched_sparse_gemm_slots
+// teal_batched_sparse_gemm (active == nullptr), teal_batched_sparse_gemm_slots and teal_batched_sparse_gemm_slot_taus (taus != nullptr)
 int batched_gemm_launch(const teal_prefill_in_t* in, const teal_batched_segs_t* segs, const void* w0T, int ld0, int n0, const void* w1T,
-                        int ld1, int n1, float* slabs, size_t slabs_bytes, int Z, int B, const int32_t* active, int32_t* counts, int dtype,
-                        int* split_out, void* stream) {
+                        int ld1, int n1, float* slabs, size_t slabs_bytes, int Z, int B, const int32_t* active, const float* taus, int32_t* counts,
+                        int dtype, int* split_out, void* stream) {
     if (!in || !segs || !w0T || !slabs || !split_out || Z <= 0 || n0 <= 0 || n1 < 0 || (n1 > 0 && !w1T)) return TEAL_ERR_ARG;
     if (dtype != TEAL_F16 && dtype != TEAL_BF16) return TEAL_ERR_DTYPE;
     if (B < 1 || B > kBatchMax || (Z & 255) || Z > 65536 || (ld0 & 7) || (ld1 & 7) || ld0 < n0 || (n1 > 0 && ld1 < n1)) return TEAL_ERR_SHAPE;
@@ -541,24 +582,29 @@ int batched_gemm_launch(const teal_prefill_in_t* in, const teal_batched_segs_t* 
     }
     if (sg.end[sg.nseg - 1] != ntot) return TEAL_ERR_SHAPE;
     for (int s = sg.nseg; s < 3; ++s) { sg.end[s] = ntot; sg.tau[s] = sg.tau[sg.nseg - 1]; }
+    const BSegsTaus sgt = {sg.nseg, {sg.end[0], sg.end[1], sg.end[2]}, taus};
     SlabProd pr;
     if (const int rc = slab_prod_fill(in, slabs, kSlabMaxSplit, B, &pr)) return rc;
     if (!aligned16(w0T) || (w1T && !aligned16(w1T)) || !aligned16(slabs)) return TEAL_ERR_ALIGN;
+    if (taus && (reinterpret_cast<uintptr_t>(taus) & 31)) return TEAL_ERR_ALIGN;  // each row is one 32-byte scalar load
     DeviceCtx* ctx = device_ctx();
     if (!ctx) return TEAL_ERR_NO_DEVICE;
     constexpr int bn = 256;
     const int tiles = ntot / bn, split = slab_gemm_split(ctx->num_cu, tiles, Z, kSlabMaxSplit);
     if (slabs_bytes < (size_t)split * ntot * 8 * sizeof(float)) return TEAL_ERR_WORKSPACE;
     const dim3 grid(tiles, split), block(1024);
-    const size_t lds = (size_t)kBPhaseRows * 28 + (size_t)(2 * kBChunks + 1) * sizeof(int) + (size_t)16 * 3 * kBCountStride * sizeof(int);
+    const size_t lds = taus ? (size_t)kBTauOff + 16 * 24 * sizeof(float)
+                            : (size_t)kBPhaseRows * 28 + (size_t)(2 * kBChunks + 1) * sizeof(int) + (size_t)16 * 3 * kBCountStride * sizeof(int);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int np = (B + 1) / 2, tiles0 = n0 / bn;
     auto* a = reinterpret_cast<const uint16_t*>(w0T);
     auto* b = reinterpret_cast<const uint16_t*>(w1T);
     int* cnt = reinterpret_cast<int*>(counts);
-#define TEAL_BG(BF, NPV, PR) do { if (active) hipLaunchKernelGGL((batched_gemm_kernel<BF, NPV, PR, true>), grid, block, lds, st, pr, sg, a, ld0, b, \
+#define TEAL_BG(BF, NPV, PR) do { if (taus) hipLaunchKernelGGL((batched_gemm_kernel<BF, NPV, PR, true, true>), grid, block, lds, st, pr, sgt, \
+        a, ld0, b, ld1, tiles0, slabs, cnt, Z, ntot, active); \
+    else if (active) hipLaunchKernelGGL((batched_gemm_kernel<BF, NPV, PR, false, true>), grid, block, lds, st, pr, sg, a, ld0, b, \
         ld1, tiles0, slabs, cnt, Z, ntot, active); \
-    else hipLaunchKernelGGL((batched_gemm_kernel<BF, NPV, PR, false>), grid, block, lds, st, pr, sg, a, ld0, b, ld1, tiles0, slabs, cnt, Z, ntot, \
+    else hipLaunchKernelGGL((batched_gemm_kernel<BF, NPV, PR, false, false>), grid, block, lds, st, pr, sg, a, ld0, b, ld1, tiles0, slabs, cnt, Z, ntot, \
                             nullptr); } while (0)
 #define TEAL_BG_PR(BF, NPV) do { if (in->mode == TEAL_PREFILL_IN_NORM) TEAL_BG(BF, NPV, 1); else if (in->mode == TEAL_PREFILL_IN_SILU_MUL) TEAL_BG(BF, NPV, 2); else TEAL_BG(BF, NPV, 0); } while (0)
 #define TEAL_BG_NP(BF) do { switch (np) { case 1: TEAL_BG_PR(BF, 1); break; case 2: TEAL_BG_PR(BF, 2); break; case 3: TEAL_BG_PR(BF, 3); break; \
@@ -577,14 +623,21 @@ extern "C" {
 int teal_batched_sparse_gemm(const teal_prefill_in_t* in, const teal_batched_segs_t* segs, const void* w0T, int ld0, int n0, const void* w1T,
                              int ld1, int n1, float* slabs, size_t slabs_bytes, int Z, int B, int32_t* counts, int dtype, int* split_out,
                              void* stream) {
-    return batched_gemm_launch(in, segs, w0T, ld0, n0, w1T, ld1, n1, slabs, slabs_bytes, Z, B, nullptr, counts, dtype, split_out, stream);
+    return batched_gemm_launch(in, segs, w0T, ld0, n0, w1T, ld1, n1, slabs, slabs_bytes, Z, B, nullptr, nullptr, counts, dtype, split_out, stream);
 }
 
 int teal_batched_sparse_gemm_slots(const teal_prefill_in_t* in, const teal_batched_segs_t* segs, const void* w0T, int ld0, int n0,
                                    const void* w1T, int ld1, int n1, float* slabs, size_t slabs_bytes, int Z, int B, const int32_t* active,
                                    int32_t* counts, int dtype, int* split_out, void* stream) {
     if (!active) return TEAL_ERR_ARG;
-    return batched_gemm_launch(in, segs, w0T, ld0, n0, w1T, ld1, n1, slabs, slabs_bytes, Z, B, active, counts, dtype, split_out, stream);
+    return batched_gemm_launch(in, segs, w0T, ld0, n0, w1T, ld1, n1, slabs, slabs_bytes, Z, B, active, nullptr, counts, dtype, split_out, stream);
+}
+
+int teal_batched_sparse_gemm_slot_taus(const teal_prefill_in_t* in, const teal_batched_segs_t* segs, const void* w0T, int ld0, int n0,
+                                       const void* w1T, int ld1, int n1, float* slabs, size_t slabs_bytes, int Z, int B,
+                                       const int32_t* active, const float* taus, int32_t* counts, int dtype, int* split_out, void* stream) {
+    if (!active || !taus) return TEAL_ERR_ARG;
+    return batched_gemm_launch(in, segs, w0T, ld0, n0, w1T, ld1, n1, slabs, slabs_bytes, Z, B, active, taus, counts, dtype, split_out, stream);
 }
 
 int teal_batched_round_rows(const float* slabs, int split, int N, int B, void* y, int dtype, void* stream) {

@@ -18,6 +18,7 @@ each with its own rng_state / token / position / history, so one hipGraph replay
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Dict, List, Optional
 
 import torch
@@ -34,6 +35,7 @@ from .prefill import MAX_T, PrefillEngine, PrefillIn, SlabChain
 from .speculative import VerifyPass
 
 PROJ_LAUNCHES = (("qkv", ("q", "k", "v")), ("o", ("o",)), ("gateup", ("gate", "up")), ("down", ("down",)))
+PROJ_KEYS = tuple(p for _, projs in PROJ_LAUNCHES for p in projs)  # the keys of one layer's thresholds dict
 NINF = float("-inf")
 
 
@@ -117,13 +119,17 @@ class BatchedDecodeEngine(SlabChain, SamplerFeatures):
         self._lm_segs = batched_segs([V], [NINF])
 
     # ---- launches: with `_active` (SlotDecodeEngine: the address of its active word) the slot-predicated entry points --------
-    def _gemm(self, gin: PrefillIn, segs, lin0, lin1, Z: int, out: torch.Tensor, counts: Optional[torch.Tensor], st) -> int:
+    def _gemm(self, gin: PrefillIn, segs, lin0, lin1, Z: int, out: torch.Tensor, counts: Optional[torch.Tensor], st,
+              taus: Optional[int] = None) -> int:
+        """taus (a slot engine with per-request sparsity on): the address of the launch's [3][8] threshold table"""
         w0, w1 = lin0.weight, lin1.weight if lin1 is not None else None
         head = (ctypes.byref(gin), ctypes.byref(segs), w0.data_ptr(), w0.stride(1), w0.shape[0], w1.data_ptr() if lin1 is not None else None,
                 w1.stride(1) if lin1 is not None else 0, w1.shape[0] if lin1 is not None else 0, out.data_ptr(), out.numel() * 4, Z, self.B)
         tail = (counts.data_ptr() if counts is not None else None, self.code, ctypes.byref(self._split), st)
         if self._active is None:
             rc, what = self.L.teal_batched_sparse_gemm(*head, *tail), "teal_batched_sparse_gemm"
+        elif taus is not None:
+            rc, what = self.L.teal_batched_sparse_gemm_slot_taus(*head, self._active, taus, *tail), "teal_batched_sparse_gemm_slot_taus"
         else:
             rc, what = self.L.teal_batched_sparse_gemm_slots(*head, self._active, *tail), "teal_batched_sparse_gemm_slots"
         if rc != 0:
@@ -158,7 +164,8 @@ class BatchedDecodeEngine(SlabChain, SamplerFeatures):
         m, cfg, L, st = self.model, self.cfg, self.L, runtime.stream_ptr()
 
         def gemm(i, j, gin, lin0, lin1, Z, out):
-            self.splits[i][j] = ns = self._gemm(gin, self._segs[i][PROJ_LAUNCHES[j][0]], lin0, lin1, Z, out, self.counts[i, j], st)
+            self.splits[i][j] = ns = self._gemm(gin, self._segs[i][PROJ_LAUNCHES[j][0]], lin0, lin1, Z, out, self.counts[i, j], st,
+                                                self._tau_row(i, j))
             return ns
 
         self._walk(self.B, self.tok_buf.data_ptr(), gemm, lambda at, A, ns: self._attention(at, A, ns, st), st)
@@ -167,6 +174,10 @@ class BatchedDecodeEngine(SlabChain, SamplerFeatures):
         if rc != 0:
             _lib.check(rc, "teal_batched_round_rows (lm_head)")
         return self.logits
+
+    def _tau_row(self, i: int, j: int) -> Optional[int]:
+        """the address of layer i, launch j's per-slot threshold table, or None: the launch takes its segments' thresholds"""
+        return None
 
     @torch.no_grad()
     def __call__(self, tokens: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
@@ -364,6 +375,7 @@ class SlotDecodeEngine(BatchedDecodeEngine):
     steps each slot's token automaton and masks the row it draws from (constraints.py)."""
 
     _stops: Optional[ST.StopConditions] = None   # set_stop_conditions
+    tau_table: Optional[torch.Tensor] = None     # set_slot_sparsity: fp32 [n_layer][4 launches][3][8] (None while it is off)
 
     def __init__(self, model: Transformer, thresholds: List[Dict[str, float]], batch: int):
         super().__init__(model, thresholds, batch)
@@ -406,7 +418,8 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         return super()._loop_state() + [self.slot_state] + (list(self._stops.loop_tensors()) if self._stops is not None else [])
 
     def _feature_key(self):
-        return super()._feature_key() + (("stops",) if self._stops is not None else ())
+        return super()._feature_key() + (("stops",) if self._stops is not None else ()) + \
+               (("slot sparsity",) if self.tau_table is not None else ())
 
     # ---- stop conditions ---------------------------------------------------------------------------------------------------
     def set_stop_conditions(self, on: bool):
@@ -433,6 +446,57 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         if not 0 <= int(slot) < self.B:
             raise ValueError(f"slot {slot} outside 0..{self.B - 1}")
         return self._stop_conditions().read()[int(slot)]
+
+    # ---- per-request sparsity ----------------------------------------------------------------------------------------------
+    def set_slot_sparsity(self, on: bool):
+        """off (the default): every step and every admission issues exactly the launches it issues without this feature.  on: the
+        layers' GEMM launches are teal_batched_sparse_gemm_slot_taus — slot b keeps a row under its OWN threshold, column b of the
+        launch's table [segment][slot] — and admit(..., thresholds=) writes a request's column; every column starts at the engine's
+        own thresholds.  The lm_head launch keeps every row either way.  A step streams the union of the rows its active slots keep,
+        each under its own thresholds.  Allowed on an idle engine only (a running slot's column would be reset); drops the captured
+        graphs."""
+        if int(self.slot_state[SLOT_ACTIVE].item()) != 0:
+            raise RuntimeError("set_slot_sparsity needs an idle engine: a slot is active")
+        self.tau_table = None
+        if on:
+            cols = torch.tensor([self._tau_column(self.ths)] * 8, dtype=torch.float32)   # [slot][layer][launch][segment]
+            self.tau_table = cols.permute(1, 2, 3, 0).contiguous().to(self.logits.device)
+            assert self.tau_table.data_ptr() % 32 == 0
+        self._graph = None
+
+    @staticmethod
+    def _tau_column(ths) -> List[List[List[float]]]:
+        """[layer][launch][segment] of one slot's column: the launch's thresholds in segment order, absent segments at +inf"""
+        return [[[float(t[p]) for p in projs] + [math.inf] * (3 - len(projs)) for _, projs in PROJ_LAUNCHES] for t in ths]
+
+    def _check_thresholds(self, thresholds) -> List[Dict[str, float]]:
+        """a request's thresholds, refused (ValueError with the reason) unless one dict per layer holds a number that is not NaN
+        under every key of the constructor's"""
+        ths = list(thresholds)
+        if len(ths) != len(self.ths):
+            raise ValueError(f"thresholds: {len(ths)} dicts for {len(self.ths)} layers (one per layer)")
+        for i, t in enumerate(ths):
+            for p in PROJ_KEYS:
+                if p not in t:
+                    raise ValueError(f"thresholds: layer {i} has no {p!r} (keys {', '.join(PROJ_KEYS)})")
+                if math.isnan(float(t[p])):
+                    raise ValueError(f"thresholds: layer {i} {p!r} is NaN")
+        return ths
+
+    def _tau_row(self, i: int, j: int) -> Optional[int]:
+        return None if self.tau_table is None else self.tau_table[i, j].data_ptr()
+
+    def kept_by_slot(self) -> Dict[str, List[float]]:
+        """of the last step: per projection, for each slot the fraction of rows it kept, the mean over layers (0 for a slot that
+        did not run) — the counts kept_fractions() averages over the slots"""
+        c = self.counts.view(len(self.model.layers), len(PROJ_LAUNCHES), 16, 3, 9).cpu()
+        out = {}
+        for j, (_, projs) in enumerate(PROJ_LAUNCHES):
+            Z = self.inter if projs == ("down",) else self.dim
+            for s, proj in enumerate(projs):
+                tot = sum(c[i, j, :self.splits[i][j], s].sum(0)[:self.B].double() for i in range(len(self.model.layers)))
+                out[proj] = (tot / (Z * len(self.model.layers))).tolist()
+        return out
 
     # ---- constraints -------------------------------------------------------------------------------------------------------
     def set_constraints(self, on: bool, capacity_words: int = 1 << 20):
@@ -587,7 +651,8 @@ class SlotDecodeEngine(BatchedDecodeEngine):
     def admit(self, slot: int, tokens, budget: int, eos_id: Optional[int], seed: int, temperature: float = 0.8,
               top_k: Optional[int] = 200, prefix: Optional[str] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
               frequency_penalty: float = 0.0, logit_bias: Optional[Dict] = None, top_p: float = 1.0, min_p: float = 0.0,
-              stop_token_ids=(), stop_sequences=(), min_new_tokens: int = 0, constraint: Optional[str] = None):
+              stop_token_ids=(), stop_sequences=(), min_new_tokens: int = 0, constraint: Optional[str] = None,
+              thresholds: Optional[List[Dict[str, float]]] = None):
         """Request -> slot `slot` (free): the dense prompt pass into that slot's caches, the first token drawn from the last row's
         logits (draw 0 of the stream `seed`), the slot's token, position, history, rng state, budget and EOS set on the device and
         its bit set.  A request whose first token ends it (budget 1, EOS) is switched off again by the same retire rule.
@@ -604,7 +669,9 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         neither they nor `eos_id` end it before min_new_tokens tokens.  The stopping tokens stay in its output.
         constraint: a registered constraint's name (it needs set_constraints(True)) — every token of the request, the first
         included, is drawn from the tokens its automaton allows, and `eos_id` only in an accepting state.  The automaton is checked
-        against this request's `eos_id` here; a temperature above 100 is refused (a banned token's weight must be exactly 0)."""
+        against this request's `eos_id` here; a temperature above 100 is refused (a banned token's weight must be exactly 0).
+        thresholds: the request's own sparsity level, one dict per layer with the constructor's keys (it needs
+        set_slot_sparsity(True)); None: the engine's own.  With the feature on every admission writes the slot's whole column."""
         s, B = int(slot), self.B
         prompt = torch.as_tensor(tokens, dtype=torch.int32).view(-1).to(self.logits.device)
         T = int(prompt.numel())
@@ -632,6 +699,13 @@ class SlotDecodeEngine(BatchedDecodeEngine):
             if float(temperature) > CN.MAX_TEMPERATURE:
                 raise ValueError(f"a constrained request needs temperature <= {CN.MAX_TEMPERATURE:g} (above it a banned token's weight "
                                  f"is no longer exactly 0), got {temperature}")
+        if thresholds is not None:
+            if self.tau_table is None:
+                raise RuntimeError("per-request sparsity is off (set_slot_sparsity)")
+            thresholds = self._check_thresholds(thresholds)
+        if self.tau_table is not None:  # (every admission: the slot's next occupant never inherits a level)
+            col = torch.tensor(self._tau_column(self.ths if thresholds is None else thresholds), dtype=torch.float32)
+            self.tau_table[..., s].copy_(col.to(self.tau_table.device))
         if self._con is not None:  # (every admission: the slot's next occupant never inherits a constraint)
             self._con.set_row(s, constraint)
         if self._samp is not None:  # (every admission: the slot's last request left its settings)

@@ -23,6 +23,10 @@ says why each request ended ("finish_reason") and what matched ("stop_match").
 Constraints: a request may follow a token automaton (constraints.py) — a registered one by name, one of a list of `choices`, or any
 sequence over `allowed_token_ids`.  The automaton advances on the device inside the step, so every token is drawn under it whatever
 sync_every is; the match is on token ids, not text.
+
+Per-request sparsity: a request may carry its own sparsity level.  The engine then keeps one threshold per slot on the device and
+an admission writes the slot's column (set_slot_sparsity), so one captured step serves any mix of levels.  A step reads the union
+of the rows its active slots keep, each under its own thresholds: a low-sparsity request widens what the whole batch reads.
 """
 from __future__ import annotations
 
@@ -40,6 +44,7 @@ from .stopping import MAX_IDS, MAX_SEQ_LEN, MAX_SEQS
 
 REFILL = ("free", "all")
 SAMPLING = ("temperature", "top_k", "top_p", "min_p")
+MAX_LEVELS = 8  # distinct sparsity levels of one run: each is resolved to thresholds before anything runs
 
 
 @dataclass
@@ -73,6 +78,8 @@ class Request:
     constraint: Optional[str] = None
     choices: Optional[List[List[int]]] = None
     allowed_token_ids: Optional[List[int]] = None
+    # its own sparsity level in [0, 1) (None: the run's): the thresholds its slot keeps rows under
+    sparsity: Optional[float] = None
 
     def __post_init__(self):
         if sum(v is not None for v in (self.constraint, self.choices, self.allowed_token_ids)) > 1:
@@ -182,6 +189,48 @@ def parse_sampling(d: dict, where: str) -> Dict:
             raise ValueError(f"{where}: \"seed\" must be a non-negative integer below 2^63")
         out["seed"] = int(d["seed"])
     return out
+
+
+def parse_sparsity(d: dict, where: str) -> Dict:
+    """the "sparsity" field of one request object, validated; {} if absent"""
+    if "sparsity" not in d:
+        return {}
+    v = d["sparsity"]
+    if not _number(v) or not 0 <= v < 1:
+        raise ValueError(f"{where}: \"sparsity\" must be a number in [0, 1) (0: every row kept)")
+    return {"sparsity": float(v)}
+
+
+def sparsity_levels_of(requests) -> List[float]:
+    """the distinct levels the requests carry, ascending; more than MAX_LEVELS are refused"""
+    levels = sorted({float(r.sparsity) for r in requests if getattr(r, "sparsity", None) is not None})
+    if len(levels) > MAX_LEVELS:
+        raise ValueError(f"{len(levels)} distinct \"sparsity\" levels: at most {MAX_LEVELS} in one run (each is resolved to its own "
+                         "thresholds before anything runs)")
+    return levels
+
+
+def check_sparsity_fields(request_lines: Sequence[str], servable=None) -> List[float]:
+    """the distinct "sparsity" levels of the request lines, ascending — needs no tokenizer, so it runs before anything is loaded:
+    a level outside [0, 1), more than MAX_LEVELS levels and a level `servable(level)` gives a reason against are refused
+    (malformed lines are left to parse_requests, which names them)"""
+    levels = set()
+    for i, line in enumerate(request_lines):
+        try:
+            d = json.loads(line) if line.strip() else None
+        except json.JSONDecodeError:
+            d = None
+        if isinstance(d, dict):
+            lv = parse_sparsity(d, f"request line {i + 1}").get("sparsity")
+            if lv is not None:
+                why = servable(lv) if servable is not None else None
+                if why is not None:
+                    raise ValueError(f"request line {i + 1}: \"sparsity\" {lv:g}: {why}")
+                levels.add(lv)
+    if len(levels) > MAX_LEVELS:
+        raise ValueError(f"{len(levels)} distinct \"sparsity\" levels: at most {MAX_LEVELS} in one run (each is resolved to its own "
+                         "thresholds before anything runs)")
+    return sorted(levels)
 
 
 def parse_stops(d: dict, where: str, tokenizer=None) -> Dict:
@@ -308,6 +357,9 @@ def parse_prefixes(lines: Sequence[str], tokenizer=None) -> Dict[str, List[int]]
             raise ValueError(f"prefix line {i + 1}: not JSON ({e})") from None
         if not isinstance(d, dict) or not isinstance(d.get("id"), str) or not d["id"]:
             raise ValueError(f"prefix line {i + 1}: needs an \"id\" (a non-empty string)")
+        if "sparsity" in d:
+            raise ValueError(f"prefix line {i + 1}: \"sparsity\" belongs to a request line: a prefix's rows are computed once, by the "
+                             "dense prompt pass")
         if ("tokens" in d) == ("prompt" in d):
             raise ValueError(f"prefix line {i + 1}: needs exactly one of \"tokens\" and \"prompt\"")
         if d["id"] in out:
@@ -355,7 +407,8 @@ def parse_requests(lines: Sequence[str], default_max_new_tokens: int, tokenizer=
     WITHOUT a BOS into one more stop sequence.  The match is on token ids against the tokens the request generates: a string the
     model spells with other tokens (another split, a leading-space variant) is not caught.  A line may carry ONE constraint:
     "constraint" (an id of `constraints`), "choices" (token id lists, or strings — each encoded alone WITHOUT a BOS, with the same
-    caveat; the request produces exactly one of them and then the EOS id, so it needs `eos_id`) or "allowed_token_ids"."""
+    caveat; the request produces exactly one of them and then the EOS id, so it needs `eos_id`) or "allowed_token_ids".  A line may
+    carry its own "sparsity" (in [0, 1); at most 8 distinct levels in one file)."""
     out = []
     for i, line in enumerate(lines):
         if not line.strip():
@@ -387,9 +440,11 @@ def parse_requests(lines: Sequence[str], default_max_new_tokens: int, tokenizer=
             raise ValueError(f"request line {i + 1}: \"choices\" needs an EOS id (--eos_id): a finished choice ends on it, and without "
                              "one its last state is a dead end")
         out.append(Request([int(t) for t in toks], n, eos_id, prefix=pid, **parse_controls(d, f"request line {i + 1}"),
-                           **parse_sampling(d, f"request line {i + 1}"), **parse_stops(d, f"request line {i + 1}", tokenizer), **con))
+                           **parse_sampling(d, f"request line {i + 1}"), **parse_stops(d, f"request line {i + 1}", tokenizer), **con,
+                           **parse_sparsity(d, f"request line {i + 1}")))
     if not out:
         raise ValueError("no requests")
+    sparsity_levels_of(out)
     return out
 
 
@@ -441,13 +496,19 @@ class ContinuousBatcher:
     Constraints: `constraints` (id -> Automaton) are what requests may name.  Exactly when some request carries a constraint, choices
     or allowed_token_ids the engine also offers set_constraints(True), called once before the first admission, has_constraint(id),
     register_constraint(id, automaton) — one per distinct content — and admit(..., constraint=id); only those requests are admitted
-    with the keyword."""
+    with the keyword.
+    Per-request sparsity: `sparsity` is the level the engine was built at (None: unknown) and `sparsity_levels` maps each level a
+    request may carry to its per-layer thresholds.  Exactly when some request's level differs from `sparsity` the engine also offers
+    set_slot_sparsity(True), called once before the first admission, admit(..., thresholds=) — only requests at another level
+    than the run's are admitted with the keyword — and kept_by_slot(); the result gains "kept_by_request": per request the mean
+    over the sync points it ran up to, and over the projections, of the fraction of rows it kept."""
 
     def __init__(self, engine, sync_every: int = 8, refill: str = "free", temperature: float = 0.8, top_k: Optional[int] = 200,
                  seed: int = 1234, use_graph: bool = True, prefixes: Optional[Dict[str, List[int]]] = None,
                  logprobs: Optional[int] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                  frequency_penalty: float = 0.0, top_p: float = 1.0, min_p: float = 0.0, stop_token_ids=(), min_new_tokens: int = 0,
-                 finish_reason: bool = False, constraints: Optional[Dict[str, Automaton]] = None):
+                 finish_reason: bool = False, constraints: Optional[Dict[str, Automaton]] = None, sparsity: Optional[float] = None,
+                 sparsity_levels: Optional[Dict[float, List[Dict[str, float]]]] = None):
         if refill not in REFILL:
             raise ValueError(f"refill must be one of {REFILL}")
         if int(sync_every) < 1:
@@ -466,6 +527,9 @@ class ContinuousBatcher:
         self.stop_defaults = parse_stops({"stop_token_ids": list(stop_token_ids or ()), "min_new_tokens": min_new_tokens}, "ContinuousBatcher")
         self.finish_reason, self._stops_set = bool(finish_reason), False
         self.constraints, self._constraints_set = dict(constraints or {}), False
+        self.sparsity = None if sparsity is None else parse_sparsity({"sparsity": sparsity}, "ContinuousBatcher")["sparsity"]
+        self.sparsity_levels = {float(k): v for k, v in (sparsity_levels or {}).items()}
+        self._sparsity_set = False
 
     def _clock(self):
         try:
@@ -539,6 +603,19 @@ class ContinuousBatcher:
             for name, a in automata.items():
                 if not eng.has_constraint(name):
                     eng.register_constraint(name, a)
+        levels: List[Optional[float]] = [None] * len(requests)  # None: the run's own
+        for i, r in enumerate(requests):  # refused before anything runs
+            lv = getattr(r, "sparsity", None)
+            if lv is None or (self.sparsity is not None and float(lv) == self.sparsity):
+                continue
+            if float(lv) not in self.sparsity_levels:
+                raise ValueError(f"request {i}: no thresholds for sparsity {float(lv):g} (sparsity_levels)")
+            levels[i] = float(lv)
+        sparsity_levels_of(requests)
+        if any(lv is not None for lv in levels) and not self._sparsity_set:  # once: it drops the engine's captured step
+            eng.set_slot_sparsity(True)
+            self._sparsity_set = True
+        kept_sum, kept_n = [0.0] * len(requests), [0] * len(requests)
         reasons: List[Optional[str]] = [None] * len(requests)
         matches: List[int] = [-1] * len(requests)
         pending = deque(range(len(requests)))
@@ -572,6 +649,8 @@ class ContinuousBatcher:
                         kw.update(stops[r])
                     if cons[r] is not None:
                         kw["constraint"] = cons[r]
+                    if levels[r] is not None:
+                        kw["thresholds"] = self.sparsity_levels[levels[r]]
                     eng.admit(s, q.tokens, q.max_new_tokens, q.eos_id, self.seed + r if q.seed is None else q.seed, T, k, **kw)
                     prefix_admissions += 1 if plen[r] else 0
                     prefix_rows += plen[r]
@@ -581,6 +660,14 @@ class ContinuousBatcher:
             eng.run_steps(self.K, self.temperature, self.top_k, self.use_graph)
             steps += self.K
             state = eng.read_state()
+            if self._sparsity_set:  # the burst's last step: the slots that ran it (still active, or stopped by it)
+                kept = eng.kept_by_slot()
+                for s in range(B):
+                    r = slot_req[s]
+                    ran = (state[SLOT_ACTIVE] >> s) & 1 or (state[SLOT_FINISH + s] == state[SLOT_STEP] - 1 and state[SLOT_PRODUCED + s] >= 2)
+                    if r is not None and ran:
+                        kept_sum[r] += sum(v[s] for v in kept.values()) / len(kept)
+                        kept_n[r] += 1
             for s in range(B):
                 r = slot_req[s]
                 if r is None or (state[SLOT_ACTIVE] >> s) & 1:
@@ -608,6 +695,8 @@ class ContinuousBatcher:
                 extra["top_logprobs"] = tops
         if self._stops_set:
             extra["finish_reason"], extra["stop_match"] = reasons, matches
+        if self._sparsity_set:  # (None: the request ran no step that a sync point saw)
+            extra["kept_by_request"] = [kept_sum[r] / kept_n[r] if kept_n[r] else None for r in range(len(requests))]
         return {
             **extra,
             "tokens": out, "slots": slots_used, "steps": steps, "admissions": admissions, "wall_s": wall,

@@ -190,6 +190,13 @@ class SamplerFeatures:
             raise NotImplementedError(f"{type(self).__name__} has no constrained decoding: a constraint starts at an admission and ends on "
                                       "the request's EOS word, which only SlotDecodeEngine has")
 
+    def set_slot_sparsity(self, on: bool):
+        """per-request sparsity belongs to the slot engine: a request's thresholds are written at its admission, and this engine
+        has none — switching it on is refused with that reason (off is what it is)"""
+        if on:
+            raise NotImplementedError(f"{type(self).__name__} has no per-request sparsity: a request's thresholds are written at its "
+                                      "admission, which only SlotDecodeEngine has")
+
     def _constraints(self) -> CN.Constraints:
         if self._con is None:
             raise RuntimeError("constraints are off (set_constraints)")

@@ -844,8 +844,51 @@ def check_requests_args(args) -> int:
     return int(getattr(args, "batch_size", 1) or 1)
 
 
+def check_request_sparsity(args) -> List[float]:
+    """the distinct "sparsity" levels the --requests lines carry, ascending; every refusal is raised here, before anything is loaded:
+    a level outside [0, 1), more than 8 distinct levels, and a level the run's threshold source cannot serve (a --greedy_lookup
+    .json table holds its own list of targets; histograms and --synthetic calibration serve any level)"""
+    from teal_amd.gpt_fast.continuous import check_sparsity_fields
+    servable = None
+    lookup = getattr(args, "greedy_lookup", None)
+    if lookup and str(lookup).endswith(".json"):
+        with open(lookup) as f:
+            targets = set(json.load(f)["targets"])
+
+        def servable(level):
+            if level == 0.0 or repr(float(level)) in targets:
+                return None
+            return f"--greedy_lookup {lookup} has no such target (it holds {', '.join(sorted(targets))})"
+    try:
+        return check_sparsity_fields(Path(args.requests).read_text().splitlines(), servable)
+    except (OSError, ValueError) as e:
+        raise SystemExit(f"--requests: {e}")
+
+
+def resolve_sparsity_levels(args, model: Transformer, levels) -> Dict[float, List[Dict[str, float]]]:
+    """each level -> its per-layer thresholds, through apply_sparsity — the function that resolves --sparsity — on the model's
+    dense forward (a level is what a run at that --sparsity would use); level 0 keeps every row.  The caller patches the model at
+    the run's own level afterwards."""
+    out = {}
+    for level in levels:
+        if level == 0.0:
+            continue
+        for layer in model.layers:  # back to the dense forward: calibration must not see the last level's masks
+            for m in (layer.attention, layer.feed_forward):
+                m.__dict__.pop("forward", None)
+        out[level] = apply_sparsity(model, sparsity=level, hist_path=args.hist_path, greedy_lookup=args.greedy_lookup,
+                                    synthetic=bool(args.synthetic))
+    if out:
+        for layer in model.layers:
+            for m in (layer.attention, layer.feed_forward):
+                m.__dict__.pop("forward", None)
+    if 0.0 in levels:
+        out[0.0] = None  # (filled in by the caller from the run's thresholds: dense_thresholds needs their keys)
+    return out
+
+
 @torch.no_grad()
-def run_continuous(args, model: Transformer, thresholds, tokenizer) -> Dict:
+def run_continuous(args, model: Transformer, thresholds, tokenizer, sparsity_levels=None) -> Dict:
     """--requests FILE through ContinuousBatcher on a SlotDecodeEngine of --batch_size slots (one hipGraph replay per step under
     --compile, with one warm-up run first)"""
     from teal_amd.gpt_fast.batched import SlotDecodeEngine
@@ -893,7 +936,8 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer) -> Dict:
     batcher = ContinuousBatcher(eng, sync_every=args.sync_every, temperature=args.temperature, top_k=args.top_k, seed=1234,
                                 use_graph=bool(args.compile), prefixes=prefixes, logprobs=getattr(args, "logprobs", None),
                                 **check_processor_args(args), **check_sampling_args(args), **check_stop_args(args),
-                                **({"constraints": constraints} if constraints else {}))
+                                **({"constraints": constraints} if constraints else {}),
+                                sparsity=float(args.sparsity), sparsity_levels=sparsity_levels or {})
     try:
         for name, toks in prefixes.items():  # once, before the warm-up run
             eng.register_prefix(name, toks)
@@ -919,6 +963,10 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer) -> Dict:
     print(f"{len(reqs)} requests, {res['useful_tokens']} useful tokens in {res['wall_s']:.2f} s: {tps:.2f} tokens/sec; "
           f"{res['steps']} steps, {res['mean_active_slots']:.2f} active slots of {B} on average, "
           f"{100 * res['admission_share']:.1f} % of the time in {res['admissions']} admissions")
+    if "kept_by_request" in res:
+        for i, k in enumerate(res["kept_by_request"]):
+            lv = args.sparsity if reqs[i].sparsity is None else reqs[i].sparsity
+            print(f"    request {i}: sparsity {lv:g}, kept " + ("-" if k is None else f"{100 * k:.1f} %") + " of the rows on average")
     if prefixes:
         print(f"{res['prefix_admissions']} admissions on a shared prefix reused {res['prefix_rows_reused']} rows; suffix passes: "
               f"{res['prefix_paths']}")
@@ -928,7 +976,7 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer) -> Dict:
             "admission_share": res["admission_share"], "mean_active_slots": res["mean_active_slots"], "union_kept": res["union_kept"],
             "sync_every": res["sync_every"], "prefix_admissions": res["prefix_admissions"],
             "prefix_rows_reused": res["prefix_rows_reused"], "prefix_paths": res["prefix_paths"],
-            **{k: res[k] for k in ("logprobs", "top_logprobs", "finish_reason", "stop_match") if k in res}}
+            **{k: res[k] for k in ("logprobs", "top_logprobs", "finish_reason", "stop_match", "kept_by_request") if k in res}}
 
 
 def sample_batch(logits: torch.Tensor, temperature: float, top_k: Optional[int]) -> torch.Tensor:
@@ -965,6 +1013,7 @@ def main(args) -> Dict:
             check_prefix_ids(Path(args.requests).read_text().splitlines(), Path(pf).read_text().splitlines() if pf is not None else [])
         except (OSError, ValueError) as e:
             raise SystemExit(f"--requests: {e}")
+        levels = check_request_sparsity(args)
     if getattr(args, "interactive", False) and args.synthetic:
         raise SystemExit("--interactive needs a tokenizer (a checkpoint directory), not --synthetic")
     dtype = {"fp16": torch.float16, "bf16": torch.bfloat16}[args.precision]
@@ -995,6 +1044,10 @@ def main(args) -> Dict:
         tokenizer = get_tokenizer(args.checkpoint_path.parent / "tokenizer.model", args.checkpoint_path)
         prompt = torch.tensor([tokenizer.bos_id()] + tokenizer.encode(args.prompt), dtype=torch.int, device=device)
     thresholds = None
+    level_ths = None
+    if getattr(args, "requests", None) is not None and any(lv != float(args.sparsity) for lv in levels):
+        print(f"Resolving the requests' sparsity levels {levels} ...")
+        level_ths = resolve_sparsity_levels(args, model, [lv for lv in levels if lv != float(args.sparsity)])
     if not args.dense and (args.hist_path is not None or args.synthetic):
         # like the reference, patching is gated on hist_path, not on sparsity (generate.py:328)
         print("Monkeypatching with activation sparsity...")
@@ -1008,7 +1061,10 @@ def main(args) -> Dict:
     if spec is not None:
         return run_speculative(args, model, thresholds, prompt, tokenizer, spec, device, dtype)
     if getattr(args, "requests", None) is not None:
-        return run_continuous(args, model, thresholds, tokenizer)
+        if level_ths is not None and 0.0 in level_ths:
+            from teal_amd.gpt_fast.score import dense_thresholds
+            level_ths[0.0] = dense_thresholds(thresholds)
+        return run_continuous(args, model, thresholds, tokenizer, level_ths)
     if batch > 1:
         if args.synthetic:  # B distinct seeded prompts of equal length
             prompts = torch.randint(0, model.config.vocab_size, (batch, prompt.numel()), device=device, dtype=torch.int,
