@@ -703,6 +703,13 @@ class SlotDecodeEngine(BatchedDecodeEngine):
             if self.tau_table is None:
                 raise RuntimeError("per-request sparsity is off (set_slot_sparsity)")
             thresholds = self._check_thresholds(thresholds)
+        if self._samp is not None:
+            SM.check_sampling(temperature, top_k, top_p, min_p)
+        elif SM.check_sampling(top_p=top_p, min_p=min_p)["top_p"] < 1.0 or min_p > 0.0:
+            raise RuntimeError("per-request sampling is off (set_sampling_params)")
+        # Every refusal is above, every write to a device table below: a refused admission leaves the slot as it found it.  (But
+        # for LogitProcessors.set_row's own: a bias that is not finite in the model dtype — it needs the device dtype — and a prompt
+        # token outside the vocabulary are refused there, after the rows before it are written.)
         if self.tau_table is not None:  # (every admission: the slot's next occupant never inherits a level)
             col = torch.tensor(self._tau_column(self.ths if thresholds is None else thresholds), dtype=torch.float32)
             self.tau_table[..., s].copy_(col.to(self.tau_table.device))
@@ -710,8 +717,6 @@ class SlotDecodeEngine(BatchedDecodeEngine):
             self._con.set_row(s, constraint)
         if self._samp is not None:  # (every admission: the slot's last request left its settings)
             self._samp.set_row(s, temperature, top_k, top_p, min_p)
-        elif SM.check_sampling(top_p=top_p, min_p=min_p)["top_p"] < 1.0 or min_p > 0.0:
-            raise RuntimeError("per-request sampling is off (set_sampling_params)")
         if self._stops is not None:  # (every admission: the slot's last request left its row, and its reason)
             self._stops.set_row(s, **stops)
         if self._proc is not None:  # (every admission: the slot's last request left its counts and its parameters)

@@ -11,22 +11,10 @@ refill="free" admits into every free slot; refill="all" only when every slot is 
 so its tokens do not depend on its slot, on the requests beside it or on sync_every (where the union does not either: every
 row kept).
 
-Shared prefixes: a request may name a prefix — a token sequence registered with the engine once, whose K / V rows stay in a device
-store.  Its own tokens are then the suffix: it is served as prompt = prefix + suffix, but its admission copies the prefix's rows
-into the slot and runs the prompt pass over the suffix alone.  Prefixes are named, never detected: what a request computes does
-not depend on what happened to be cached when it was admitted.
-
-Stop conditions: a request may carry stop token ids, stop sequences of token ids and a minimum length (stopping.py).  They are
-matched on the device inside the step, so a request ends on the very step its stop appears whatever sync_every is, and the result
-says why each request ended ("finish_reason") and what matched ("stop_match").
-
-Constraints: a request may follow a token automaton (constraints.py) — a registered one by name, one of a list of `choices`, or any
-sequence over `allowed_token_ids`.  The automaton advances on the device inside the step, so every token is drawn under it whatever
-sync_every is; the match is on token ids, not text.
-
-Per-request sparsity: a request may carry its own sparsity level.  The engine then keeps one threshold per slot on the device and
-an admission writes the slot's column (set_slot_sparsity), so one captured step serves any mix of levels.  A step reads the union
-of the rows its active slots keep, each under its own thresholds: a low-sparsity request widens what the whole batch reads.
+What a request may carry beyond that — a shared prefix, logprobs, logit processors, its own sampling, stop conditions, a constraint,
+its own sparsity — is one object each (Prefixes ... Sparsity below; ContinuousBatcher.features): the batcher's defaults, what
+is refused before anything runs, whether the engine feature is switched on, the keywords of the request's admission, and what the
+result gains.  A new per-request feature is one more such object; the scheduling loop names none of them.
 """
 from __future__ import annotations
 
@@ -136,8 +124,21 @@ class Request:
         return out
 
 
-def _token_list(toks) -> bool:
-    return isinstance(toks, list) and bool(toks) and all(isinstance(t, int) and not isinstance(t, bool) and t >= 0 for t in toks)
+def _token_ids(v, empty: bool = False) -> bool:
+    """a list of token ids: integers >= 0, no booleans (JSON's true is no token 1); `empty`: the list may hold none"""
+    return isinstance(v, list) and (empty or bool(v)) and all(isinstance(t, int) and not isinstance(t, bool) and t >= 0 for t in v)
+
+
+def _json_objects(lines: Sequence[str]):
+    """(index, object) of every line that holds a JSON object.  Blank and malformed lines and other JSON values are skipped: the
+    checks that run before anything is loaded leave them to parse_requests / parse_prefixes, which name them"""
+    for i, line in enumerate(lines):
+        try:
+            d = json.loads(line) if line.strip() else None
+        except json.JSONDecodeError:
+            d = None
+        if isinstance(d, dict):
+            yield i, d
 
 
 def _number(v) -> bool:
@@ -201,54 +202,47 @@ def parse_sparsity(d: dict, where: str) -> Dict:
     return {"sparsity": float(v)}
 
 
-def sparsity_levels_of(requests) -> List[float]:
-    """the distinct levels the requests carry, ascending; more than MAX_LEVELS are refused"""
-    levels = sorted({float(r.sparsity) for r in requests if getattr(r, "sparsity", None) is not None})
-    if len(levels) > MAX_LEVELS:
-        raise ValueError(f"{len(levels)} distinct \"sparsity\" levels: at most {MAX_LEVELS} in one run (each is resolved to its own "
-                         "thresholds before anything runs)")
-    return levels
-
-
-def check_sparsity_fields(request_lines: Sequence[str], servable=None) -> List[float]:
-    """the distinct "sparsity" levels of the request lines, ascending — needs no tokenizer, so it runs before anything is loaded:
-    a level outside [0, 1), more than MAX_LEVELS levels and a level `servable(level)` gives a reason against are refused
-    (malformed lines are left to parse_requests, which names them)"""
-    levels = set()
-    for i, line in enumerate(request_lines):
-        try:
-            d = json.loads(line) if line.strip() else None
-        except json.JSONDecodeError:
-            d = None
-        if isinstance(d, dict):
-            lv = parse_sparsity(d, f"request line {i + 1}").get("sparsity")
-            if lv is not None:
-                why = servable(lv) if servable is not None else None
-                if why is not None:
-                    raise ValueError(f"request line {i + 1}: \"sparsity\" {lv:g}: {why}")
-                levels.add(lv)
+def _capped(levels: set) -> List[float]:
+    """the distinct levels of one run, ascending; more than MAX_LEVELS are refused"""
     if len(levels) > MAX_LEVELS:
         raise ValueError(f"{len(levels)} distinct \"sparsity\" levels: at most {MAX_LEVELS} in one run (each is resolved to its own "
                          "thresholds before anything runs)")
     return sorted(levels)
 
 
+def sparsity_levels_of(requests) -> List[float]:
+    """the distinct levels the requests carry, ascending; more than MAX_LEVELS are refused"""
+    return _capped({float(r.sparsity) for r in requests if r.sparsity is not None})
+
+
+def check_sparsity_fields(request_lines: Sequence[str], servable=None) -> List[float]:
+    """the distinct "sparsity" levels of the request lines, ascending — needs no tokenizer, so it runs before anything is loaded:
+    a level outside [0, 1), more than MAX_LEVELS levels and a level `servable(level)` gives a reason against are refused"""
+    levels = set()
+    for i, d in _json_objects(request_lines):
+        lv = parse_sparsity(d, f"request line {i + 1}").get("sparsity")
+        if lv is not None:
+            why = servable(lv) if servable is not None else None
+            if why is not None:
+                raise ValueError(f"request line {i + 1}: \"sparsity\" {lv:g}: {why}")
+            levels.add(lv)
+    return _capped(levels)
+
+
 def parse_stops(d: dict, where: str, tokenizer=None) -> Dict:
     """the stop-condition fields of one request object, validated; only those present.  "stop": strings, each encoded without a BOS
     into one more stop sequence (needs a tokenizer) — the match stays on token ids: a text the model spells with other tokens than
     the tokenizer gave for the string alone is not caught."""
-    def ids(v):
-        return isinstance(v, list) and all(isinstance(t, int) and not isinstance(t, bool) and t >= 0 for t in v)
     out = {}
     if "stop_token_ids" in d:
         v = d["stop_token_ids"]
-        if not ids(v) or len(set(v)) > MAX_IDS:
+        if not _token_ids(v, empty=True) or len(set(v)) > MAX_IDS:
             raise ValueError(f"{where}: \"stop_token_ids\" must be a list of at most {MAX_IDS} token ids")
         out["stop_token_ids"] = [int(t) for t in v]
     seqs = []
     if "stop_sequences" in d:
         v = d["stop_sequences"]
-        if not isinstance(v, list) or not all(ids(q) and 1 <= len(q) <= MAX_SEQ_LEN for q in v):
+        if not isinstance(v, list) or not all(_token_ids(q) and len(q) <= MAX_SEQ_LEN for q in v):
             raise ValueError(f"{where}: \"stop_sequences\" must be a list of lists of 1..{MAX_SEQ_LEN} token ids")
         seqs += [[int(t) for t in q] for q in v]
     if "stop" in d:
@@ -280,9 +274,6 @@ def parse_constraint_fields(d: dict, where: str, tokenizer=None, constraints: Op
     kinds = [k for k in ("constraint", "choices", "allowed_token_ids") if k in d]
     if len(kinds) > 1:
         raise ValueError(f"{where}: at most one of \"constraint\", \"choices\" and \"allowed_token_ids\", got " + " and ".join(f'"{k}"' for k in kinds))
-
-    def ids(v):
-        return isinstance(v, list) and bool(v) and all(isinstance(t, int) and not isinstance(t, bool) and t >= 0 for t in v)
     if "constraint" in d:
         c = d["constraint"]
         if not isinstance(c, str) or c not in (constraints or {}):
@@ -290,7 +281,7 @@ def parse_constraint_fields(d: dict, where: str, tokenizer=None, constraints: Op
         return {"constraint": c}
     if "choices" in d:
         v = d["choices"]
-        if not isinstance(v, list) or not v or not (all(ids(q) for q in v) or all(isinstance(q, str) and q for q in v)):
+        if not isinstance(v, list) or not v or not (all(_token_ids(q) for q in v) or all(isinstance(q, str) and q for q in v)):
             raise ValueError(f"{where}: \"choices\" must be a non-empty list of non-empty token id lists, or of non-empty strings")
         if isinstance(v[0], str):
             if tokenizer is None:
@@ -304,7 +295,7 @@ def parse_constraint_fields(d: dict, where: str, tokenizer=None, constraints: Op
             v = enc
         return {"choices": [[int(t) for t in q] for q in v]}
     if "allowed_token_ids" in d:
-        if not ids(d["allowed_token_ids"]):
+        if not _token_ids(d["allowed_token_ids"]):
             raise ValueError(f"{where}: \"allowed_token_ids\" must be a non-empty list of token ids")
         return {"allowed_token_ids": [int(t) for t in d["allowed_token_ids"]]}
     return {}
@@ -333,14 +324,9 @@ def parse_constraints(lines: Sequence[str]) -> Dict[str, Automaton]:
 
 
 def check_constraint_ids(request_lines: Sequence[str], constraints: Dict) -> None:
-    """every "constraint" a request line names is an id of `constraints` — needs no tokenizer, so it runs before anything is loaded
-    (malformed lines are left to parse_requests, which names them)"""
-    for i, line in enumerate(request_lines):
-        try:
-            d = json.loads(line) if line.strip() else None
-        except json.JSONDecodeError:
-            d = None
-        if isinstance(d, dict) and d.get("constraint") is not None and d["constraint"] not in constraints:
+    """every "constraint" a request line names is an id of `constraints` — needs no tokenizer, so it runs before anything is loaded"""
+    for i, d in _json_objects(request_lines):
+        if d.get("constraint") is not None and d["constraint"] not in constraints:
             raise ValueError(f"request line {i + 1}: unknown constraint {d['constraint']!r}")
 
 
@@ -366,7 +352,7 @@ def parse_prefixes(lines: Sequence[str], tokenizer=None) -> Dict[str, List[int]]
             raise ValueError(f"prefix line {i + 1}: duplicate id {d['id']!r}")
         if "tokens" in d:
             toks = d["tokens"]
-            if not _token_list(toks):
+            if not _token_ids(toks):
                 raise ValueError(f"prefix line {i + 1}: \"tokens\" must be a non-empty list of token ids")
         else:
             if tokenizer is None:
@@ -379,18 +365,9 @@ def parse_prefixes(lines: Sequence[str], tokenizer=None) -> Dict[str, List[int]]
 
 
 def check_prefix_ids(request_lines: Sequence[str], prefix_lines: Sequence[str]) -> None:
-    """every "prefix" a request line names is an "id" of a prefix line — needs no tokenizer, so it runs before anything is loaded
-    (malformed lines are left to parse_prefixes / parse_requests, which name them)"""
-    def objs(lines):
-        for i, line in enumerate(lines):
-            try:
-                d = json.loads(line) if line.strip() else None
-            except json.JSONDecodeError:
-                d = None
-            if isinstance(d, dict):
-                yield i, d
-    ids = {d.get("id") for _, d in objs(prefix_lines)}
-    for i, d in objs(request_lines):
+    """every "prefix" a request line names is an "id" of a prefix line — needs no tokenizer, so it runs before anything is loaded"""
+    ids = {d.get("id") for _, d in _json_objects(prefix_lines)}
+    for i, d in _json_objects(request_lines):
         if d.get("prefix") is not None and d["prefix"] not in ids:
             raise ValueError(f"request line {i + 1}: unknown prefix {d['prefix']!r}" + ("" if ids else " (no prefixes were given)"))
 
@@ -424,7 +401,7 @@ def parse_requests(lines: Sequence[str], default_max_new_tokens: int, tokenizer=
             raise ValueError(f"request line {i + 1}: unknown prefix {pid!r}" + ("" if prefixes else " (no prefixes were given)"))
         if "tokens" in d:
             toks = d["tokens"]
-            if not isinstance(toks, list) or not toks or not all(isinstance(t, int) and t >= 0 for t in toks):
+            if not _token_ids(toks):
                 raise ValueError(f"request line {i + 1}: \"tokens\" must be a non-empty list of token ids")
         else:
             if tokenizer is None:
@@ -450,7 +427,7 @@ def parse_requests(lines: Sequence[str], default_max_new_tokens: int, tokenizer=
 
 def _prefix_len(i: int, r: Request, prefixes) -> int:
     """rows of request i's prefix (0: none); `prefixes` maps an id to its tokens"""
-    if getattr(r, "prefix", None) is None:
+    if r.prefix is None:
         return 0
     if not prefixes or r.prefix not in prefixes:
         raise ValueError(f"request {i}: unknown prefix {r.prefix!r}")
@@ -470,38 +447,243 @@ def cache_rows(requests: Sequence[Request], block_size: int, prefixes: Optional[
     return min(max(rows), block_size)
 
 
+# ---- the per-request features: one object each ------------------------------------------------------------------------------------
+class _Feature:
+    """What the batcher asks of a per-request feature; every feature below overrides what it needs and nothing else.
+
+    __init__ takes the batcher's defaults for the feature and validates them with the feature's parser.
+    plan(eng, requests), before anything runs: refuses what must be refused, switches the engine feature on if the run wants it —
+    once per batcher (`on`): the switch drops the engine's captured step, and a later run() keeps it — registers what the engine
+    must hold, and keeps per request the keywords its admission gets (`kw`; "temperature" and "top_k" are the admission's two
+    positionals).  Then, per sync point, sync(eng, state, slot_req); per finished request r in slot s with n tokens,
+    harvest(eng, s, r, n); and result(eng): the keys the feature adds to the result."""
+
+    on = False   # switched on at the engine
+    kw = ()      # per request of the planned run: its admission's keywords (empty: none for any request)
+
+    def switch_on(self, set_feature, *args):
+        if not self.on:
+            set_feature(*args)
+            self.on = True
+
+    def admit_kw(self, r: int) -> Dict:
+        return self.kw[r] if self.kw else {}
+
+    def sync(self, eng, state, slot_req):
+        pass
+
+    def harvest(self, eng, s: int, r: int, n: int):
+        pass
+
+    def result(self, eng) -> Dict:
+        return {}
+
+
+class Prefixes(_Feature):
+    """Shared prefixes: a request may name a prefix — a token sequence registered with the engine once, whose K / V rows stay in a
+    device store.  Its own tokens are then the suffix: it is served as prompt = prefix + suffix, but its admission copies the
+    prefix's rows into the slot and runs the prompt pass over the suffix alone.  Prefixes are named, never detected: what a request
+    computes does not depend on what happened to be cached when it was admitted.
+    `prefixes` (id -> tokens): the engine also offers has_prefix(id), register_prefix(id, tokens) and admit(..., prefix=id); every
+    prefix the engine does not hold yet is registered before the first admission (the engine is idle), named by a request or not,
+    and only requests that name one are admitted with `prefix=`."""
+
+    def __init__(self, prefixes):
+        self.prefixes = {k: [int(t) for t in v] for k, v in (prefixes or {}).items()}
+
+    def plan(self, eng, requests):
+        for name, toks in self.prefixes.items():
+            if not eng.has_prefix(name):
+                eng.register_prefix(name, toks)
+        self.rows = [_prefix_len(i, r, self.prefixes) for i, r in enumerate(requests)]
+        self.kw = [{"prefix": r.prefix} if P else {} for r, P in zip(requests, self.rows)]
+
+    def result(self, eng):  # (every request was admitted once)
+        return {"prefix_admissions": sum(1 for P in self.rows if P), "prefix_rows_reused": sum(self.rows),
+                "prefix_paths": dict(getattr(eng, "prefix_paths", {}))}
+
+
+class Logprobs(_Feature):
+    """`logprobs` (None: off; 0: each token's logprob under the model's own distribution — temperature 1, no top-k filter; 1..8:
+    and that many most likely alternates): the engine also offers set_logprobs(n) and read_logprobs(slot, n) -> (lp, top_ids,
+    top_lp) lists aligned with read_history(slot, n); the result gains "logprobs" and, for n > 0, "top_logprobs"."""
+
+    def __init__(self, logprobs):
+        if logprobs is not None and (isinstance(logprobs, bool) or not isinstance(logprobs, int) or not 0 <= logprobs <= 8):
+            raise ValueError("logprobs must be None or an integer in 0..8")
+        self.n = logprobs
+
+    def plan(self, eng, requests):
+        if self.n is not None:
+            self.switch_on(eng.set_logprobs, self.n)
+        self.lps: List[Optional[List[float]]] = [None] * len(requests)
+        self.tops: List[Optional[List]] = [None] * len(requests)
+
+    def harvest(self, eng, s, r, n):
+        if self.on:
+            lp, ids, tlp = eng.read_logprobs(s, n)
+            self.lps[r] = [float(v) for v in lp]
+            self.tops[r] = [[(int(i), float(v)) for i, v in zip(ii, vv)] for ii, vv in zip(ids, tlp)]
+
+    def result(self, eng):
+        if not self.on:
+            return {}
+        return {"logprobs": self.lps, **({"top_logprobs": self.tops} if self.n > 0 else {})}
+
+
+class Processors(_Feature):
+    """Logit processors: `repetition_penalty`, `presence_penalty` and `frequency_penalty` are the defaults of requests that set
+    none of their own (Request.controls).  When any request (or a default) asks for a processor the engine also offers
+    set_logit_processors(True) and admit(..., repetition_penalty=, presence_penalty=, frequency_penalty=, logit_bias=); only
+    requests that ask for one are admitted with those keywords."""
+
+    def __init__(self, repetition_penalty, presence_penalty, frequency_penalty):
+        self.defaults = parse_controls({"repetition_penalty": repetition_penalty, "presence_penalty": presence_penalty,
+                                        "frequency_penalty": frequency_penalty}, "ContinuousBatcher")
+
+    def plan(self, eng, requests):
+        self.kw = [r.controls(self.defaults) for r in requests]
+        if any(self.kw):
+            self.switch_on(eng.set_logit_processors, True)
+
+
+class Sampling(_Feature):
+    """Sampling: `temperature`, `top_k`, `top_p` and `min_p` are the defaults of requests that set none of their own
+    (Request.sampling).  When a default or some request differs from (temperature, top_k, 1, 0) — what the fused top-k samplers
+    serve from the batcher's two scalars — the engine also offers set_sampling_params(True) and admit(..., top_p=, min_p=); every
+    request is then admitted with its own four settings, in this run and in every later one, which hold for all of its draws, and
+    run_steps' temperature and top_k no longer matter."""
+
+    def __init__(self, temperature, top_k, top_p, min_p):
+        parse_sampling({"top_p": top_p, "min_p": min_p}, "ContinuousBatcher")
+        self.temperature = temperature
+        self.base = {"temperature": temperature, "top_k": int(top_k or 0), "top_p": float(top_p), "min_p": float(min_p)}
+
+    def plan(self, eng, requests):
+        sampling = [r.sampling(self.base) for r in requests]
+        plain = dict(self.base, top_p=1.0, min_p=0.0)
+        if any(s != plain for s in sampling):
+            self.switch_on(eng.set_sampling_params, True)
+        self.kw = sampling if self.on else ()
+
+
+class Stops(_Feature):
+    """Stop conditions: a request may carry stop token ids, stop sequences of token ids and a minimum length (stopping.py).  They
+    are matched on the device inside the step, so a request ends on the very step its stop appears whatever sync_every is.
+    `stop_token_ids` and `min_new_tokens` are the defaults of requests that set none of their own (Request.stops).  When a default
+    or some request asks for a stop id, a stop sequence or a minimum, or `finish_reason` is set, the engine also offers
+    set_stop_conditions(True), admit(..., stop_token_ids=, stop_sequences=, min_new_tokens=) — only requests that ask for one are
+    admitted with those keywords — and read_finish(slot) -> (reason, match); the result gains "finish_reason" ("stop_token" /
+    "stop_sequence" / "length" / "cache" per request, in input order) and "stop_match" (the token id, the sequence's index, or -1).
+    "tokens" stays every token drawn, the stopping ones included."""
+
+    def __init__(self, stop_token_ids, min_new_tokens, finish_reason):
+        self.defaults = parse_stops({"stop_token_ids": list(stop_token_ids or ()), "min_new_tokens": min_new_tokens}, "ContinuousBatcher")
+        self.finish_reason = bool(finish_reason)
+
+    def plan(self, eng, requests):
+        self.kw = [r.stops(self.defaults) for r in requests]
+        if self.finish_reason or any(self.kw):
+            self.switch_on(eng.set_stop_conditions, True)
+        self.reasons: List[Optional[str]] = [None] * len(requests)
+        self.matches: List[int] = [-1] * len(requests)
+
+    def harvest(self, eng, s, r, n):
+        if self.on:
+            self.reasons[r], self.matches[r] = eng.read_finish(s)
+
+    def result(self, eng):
+        return {"finish_reason": self.reasons, "stop_match": self.matches} if self.on else {}
+
+
+class Constraints(_Feature):
+    """Constraints: a request may follow a token automaton (constraints.py) — a registered one by name, one of a list of `choices`,
+    or any sequence over `allowed_token_ids` (Request.constraint_spec).  The automaton advances on the device inside the step, so
+    every token is drawn under it whatever sync_every is; the match is on token ids, not text.
+    `constraints` (id -> Automaton) are what requests may name.  Exactly when some request carries one of the three the engine also
+    offers set_constraints(True), has_constraint(id), register_constraint(id, automaton) — one per distinct content — and
+    admit(..., constraint=id); only those requests are admitted with the keyword.  `sampling`: the batcher's Sampling, which knows
+    the temperature a request is admitted at."""
+
+    def __init__(self, constraints, sampling: Sampling):
+        self.constraints, self.sampling = dict(constraints or {}), sampling
+
+    def plan(self, eng, requests):
+        self.kw = [{} for _ in requests]
+        automata: Dict[str, Automaton] = {}
+        for i, r in enumerate(requests):
+            spec = r.constraint_spec()
+            if spec is None:
+                continue
+            name, a = spec
+            if a is None:
+                if name not in self.constraints:
+                    raise ValueError(f"request {i}: unknown constraint {name!r}")
+                a = self.constraints[name]
+            if r.choices is not None and r.eos_id is None:
+                raise ValueError(f"request {i}: choices need an EOS id: a finished choice ends on it")
+            try:
+                a.check(eng.cfg.vocab_size, r.eos_id)
+            except ValueError as e:
+                raise ValueError(f"request {i}: {e}") from None
+            T = self.sampling.admit_kw(i).get("temperature", self.sampling.temperature)  # what request i is admitted at
+            if float(T) > MAX_TEMPERATURE:
+                raise ValueError(f"request {i}: a constrained request needs temperature <= {MAX_TEMPERATURE:g}, got {T}")
+            self.kw[i]["constraint"], automata[name] = name, a
+        if automata:
+            self.switch_on(eng.set_constraints, True)
+            for name, a in automata.items():
+                if not eng.has_constraint(name):
+                    eng.register_constraint(name, a)
+
+
+class Sparsity(_Feature):
+    """Per-request sparsity: a request may carry its own sparsity level.  The engine then keeps one threshold per slot on the device
+    and an admission writes the slot's column, so one captured step serves any mix of levels.  A step reads the union of the rows
+    its active slots keep, each under its own thresholds: a low-sparsity request widens what the whole batch reads.
+    `sparsity` is the level the engine was built at (None: unknown) and `sparsity_levels` maps each level a request may carry to
+    its per-layer thresholds.  Exactly when some request's level differs from `sparsity` the engine also offers
+    set_slot_sparsity(True), admit(..., thresholds=) — only requests at another level than the run's are admitted with the keyword
+    — and kept_by_slot(); the result gains "kept_by_request": per request the mean over the sync points it ran up to, and over the
+    projections, of the fraction of rows it kept (None: it ran no step that a sync point saw)."""
+
+    def __init__(self, sparsity, sparsity_levels):
+        self.sparsity = None if sparsity is None else parse_sparsity({"sparsity": sparsity}, "ContinuousBatcher")["sparsity"]
+        self.levels = {float(k): v for k, v in (sparsity_levels or {}).items()}
+
+    def plan(self, eng, requests):
+        self.kw = [{} for _ in requests]
+        for i, r in enumerate(requests):
+            if r.sparsity is None or (self.sparsity is not None and float(r.sparsity) == self.sparsity):
+                continue  # the run's own level
+            if float(r.sparsity) not in self.levels:
+                raise ValueError(f"request {i}: no thresholds for sparsity {float(r.sparsity):g} (sparsity_levels)")
+            self.kw[i]["thresholds"] = self.levels[float(r.sparsity)]
+        sparsity_levels_of(requests)
+        if any(self.kw):
+            self.switch_on(eng.set_slot_sparsity, True)
+        self.kept_sum, self.kept_n = [0.0] * len(requests), [0] * len(requests)
+
+    def sync(self, eng, state, slot_req):
+        if not self.on:
+            return
+        kept = eng.kept_by_slot()  # of the burst's last step: the slots that ran it (still active, or stopped by it)
+        for s, r in enumerate(slot_req):
+            ran = (state[SLOT_ACTIVE] >> s) & 1 or (state[SLOT_FINISH + s] == state[SLOT_STEP] - 1 and state[SLOT_PRODUCED + s] >= 2)
+            if r is not None and ran:
+                self.kept_sum[r] += sum(v[s] for v in kept.values()) / len(kept)
+                self.kept_n[r] += 1
+
+    def result(self, eng):
+        return {"kept_by_request": [t / n if n else None for t, n in zip(self.kept_sum, self.kept_n)]} if self.on else {}
+
+
 class ContinuousBatcher:
     """Runs requests through an engine with B slots.  The engine offers B, max_seq, admit(slot, tokens, budget, eos_id, seed,
     temperature, top_k), run_steps(k, temperature, top_k, use_graph), read_state() (the slot state words, one copy),
-    read_history(slot, n) and union_kept().  `prefixes` (id -> tokens): the engine also offers has_prefix(id),
-    register_prefix(id, tokens) and admit(..., prefix=id); run() registers every prefix the engine does not hold yet before its
-    first admission, and only requests that name a prefix are admitted with `prefix=`.  `logprobs` (None: off; 0: each token's
-    logprob under the model's own distribution — temperature 1, no top-k filter; 1..8: and that many most likely alternates): the
-    engine also offers set_logprobs(n), called once before the first admission, and read_logprobs(slot, n) -> (lp, top_ids,
-    top_lp) lists aligned with read_history(slot, n); the result gains "logprobs" and, for n > 0, "top_logprobs".
-    Logit processors: `repetition_penalty`, `presence_penalty` and `frequency_penalty` here are the defaults of requests that set
-    none of their own.  When any request (or a default) asks for a processor the engine also offers set_logit_processors(True),
-    called once before the first admission, and admit(..., repetition_penalty=, presence_penalty=, frequency_penalty=,
-    logit_bias=); only requests that ask for one are admitted with those keywords.
-    Sampling: `temperature`, `top_k`, `top_p` and `min_p` here are the defaults of requests that set none of their own.  When a
-    default or some request differs from (temperature, top_k, 1, 0) the engine also offers set_sampling_params(True), called once
-    before the first admission, and admit(..., top_p=, min_p=); every request is then admitted with its own four settings, which
-    hold for all of its draws, and run_steps' temperature and top_k no longer matter.  Otherwise every call is today's.
-    Stop conditions: `stop_token_ids` and `min_new_tokens` here are the defaults of requests that set none of their own.  When a
-    default or some request asks for a stop id, a stop sequence or a minimum, or `finish_reason` is set, the engine also offers
-    set_stop_conditions(True), called once before the first admission, admit(..., stop_token_ids=, stop_sequences=,
-    min_new_tokens=) — only requests that ask for one are admitted with those keywords — and read_finish(slot) -> (reason, match);
-    the result gains "finish_reason" ("stop_token" / "stop_sequence" / "length" / "cache" per request, in input order) and
-    "stop_match" (the token id, the sequence's index, or -1).  "tokens" stays every token drawn, the stopping ones included.
-    Constraints: `constraints` (id -> Automaton) are what requests may name.  Exactly when some request carries a constraint, choices
-    or allowed_token_ids the engine also offers set_constraints(True), called once before the first admission, has_constraint(id),
-    register_constraint(id, automaton) — one per distinct content — and admit(..., constraint=id); only those requests are admitted
-    with the keyword.
-    Per-request sparsity: `sparsity` is the level the engine was built at (None: unknown) and `sparsity_levels` maps each level a
-    request may carry to its per-layer thresholds.  Exactly when some request's level differs from `sparsity` the engine also offers
-    set_slot_sparsity(True), called once before the first admission, admit(..., thresholds=) — only requests at another level
-    than the run's are admitted with the keyword — and kept_by_slot(); the result gains "kept_by_request": per request the mean
-    over the sync points it ran up to, and over the projections, of the fraction of rows it kept."""
+    read_history(slot, n) and union_kept().  Every other keyword belongs to one of `features` — Prefixes, Logprobs, Processors,
+    Sampling, Stops, Constraints and Sparsity above, which say what they add to this protocol: while none is asked for, an engine
+    needs none of their methods and every call is the one above.  run() may be called again: what a feature switched on stays on."""
 
     def __init__(self, engine, sync_every: int = 8, refill: str = "free", temperature: float = 0.8, top_k: Optional[int] = 200,
                  seed: int = 1234, use_graph: bool = True, prefixes: Optional[Dict[str, List[int]]] = None,
@@ -515,21 +697,11 @@ class ContinuousBatcher:
             raise ValueError("sync_every must be >= 1")
         self.eng, self.K, self.refill = engine, int(sync_every), refill
         self.temperature, self.top_k, self.seed, self.use_graph = temperature, top_k, int(seed), use_graph
-        self.prefixes = {k: [int(t) for t in v] for k, v in (prefixes or {}).items()}
-        if logprobs is not None and (isinstance(logprobs, bool) or not isinstance(logprobs, int) or not 0 <= logprobs <= 8):
-            raise ValueError("logprobs must be None or an integer in 0..8")
-        self.logprobs, self._logprobs_set = logprobs, False
-        self.defaults = parse_controls({"repetition_penalty": repetition_penalty, "presence_penalty": presence_penalty,
-                                        "frequency_penalty": frequency_penalty}, "ContinuousBatcher")
-        self._processors_set = False
-        parse_sampling({"top_p": top_p, "min_p": min_p}, "ContinuousBatcher")
-        self.top_p, self.min_p, self._sampling_set = float(top_p), float(min_p), False
-        self.stop_defaults = parse_stops({"stop_token_ids": list(stop_token_ids or ()), "min_new_tokens": min_new_tokens}, "ContinuousBatcher")
-        self.finish_reason, self._stops_set = bool(finish_reason), False
-        self.constraints, self._constraints_set = dict(constraints or {}), False
-        self.sparsity = None if sparsity is None else parse_sparsity({"sparsity": sparsity}, "ContinuousBatcher")["sparsity"]
-        self.sparsity_levels = {float(k): v for k, v in (sparsity_levels or {}).items()}
-        self._sparsity_set = False
+        sampling = Sampling(temperature, top_k, top_p, min_p)
+        self.features = [Prefixes(prefixes), Logprobs(logprobs), Processors(repetition_penalty, presence_penalty, frequency_penalty),
+                         sampling, Stops(stop_token_ids, min_new_tokens, finish_reason), Constraints(constraints, sampling),
+                         Sparsity(sparsity, sparsity_levels)]
+        self.prefixes = self.features[0].prefixes  # (the fit check counts a prefix's rows)
 
     def _clock(self):
         try:
@@ -548,84 +720,19 @@ class ContinuousBatcher:
 
     def run(self, requests: Sequence[Request]) -> Dict:
         eng, B = self.eng, self.eng.B
-        plen = []
         for i, r in enumerate(requests):  # refused before anything runs
             P = _prefix_len(i, r, self.prefixes)
             if len(r.tokens) < 1 or r.max_new_tokens < 1 or P + len(r.tokens) + r.max_new_tokens > eng.max_seq:
                 raise ValueError(f"request {i}: " + (f"{P} prefix tokens + " if P else "") + f"{len(r.tokens)} prompt tokens + "
                                  f"{r.max_new_tokens} new tokens do not fit a cache of {eng.max_seq} rows")
-            plen.append(P)
-        for name, toks in self.prefixes.items():  # once per prefix, before the first admission (the engine is idle)
-            if not eng.has_prefix(name):
-                eng.register_prefix(name, toks)
-        if self.logprobs is not None and not self._logprobs_set:  # once: it drops the engine's captured step
-            eng.set_logprobs(self.logprobs)
-            self._logprobs_set = True
-        controls = [r.controls(self.defaults) if hasattr(r, "controls") else {} for r in requests]
-        if any(controls) and not self._processors_set:  # once: it drops the engine's captured step
-            eng.set_logit_processors(True)
-            self._processors_set = True
-        base = {"temperature": self.temperature, "top_k": int(self.top_k or 0), "top_p": self.top_p, "min_p": self.min_p}
-        sampling = [r.sampling(base) if hasattr(r, "sampling") else dict(base) for r in requests]
-        plain = dict(base, top_p=1.0, min_p=0.0)  # what the fused top-k samplers serve: the batcher's two scalars
-        if any(s != plain for s in sampling) and not self._sampling_set:  # once: it drops the engine's captured step
-            eng.set_sampling_params(True)
-            self._sampling_set = True
-        stops = [r.stops(self.stop_defaults) if hasattr(r, "stops") else {} for r in requests]
-        if (self.finish_reason or any(stops)) and not self._stops_set:  # once: it drops the engine's captured step
-            eng.set_stop_conditions(True)
-            self._stops_set = True
-        cons: List[Optional[str]] = [None] * len(requests)
-        automata: Dict[str, Automaton] = {}
-        for i, r in enumerate(requests):  # refused before anything runs
-            spec = r.constraint_spec() if hasattr(r, "constraint_spec") else None
-            if spec is None:
-                continue
-            name, a = spec
-            if a is None:
-                if name not in self.constraints:
-                    raise ValueError(f"request {i}: unknown constraint {name!r}")
-                a = self.constraints[name]
-            if r.choices is not None and r.eos_id is None:
-                raise ValueError(f"request {i}: choices need an EOS id: a finished choice ends on it")
-            try:
-                a.check(eng.cfg.vocab_size, r.eos_id)
-            except ValueError as e:
-                raise ValueError(f"request {i}: {e}") from None
-            T = sampling[i]["temperature"] if self._sampling_set else self.temperature
-            if float(T) > MAX_TEMPERATURE:
-                raise ValueError(f"request {i}: a constrained request needs temperature <= {MAX_TEMPERATURE:g}, got {T}")
-            cons[i], automata[name] = name, a
-        if automata:
-            if not self._constraints_set:  # once: it drops the engine's captured step
-                eng.set_constraints(True)
-                self._constraints_set = True
-            for name, a in automata.items():
-                if not eng.has_constraint(name):
-                    eng.register_constraint(name, a)
-        levels: List[Optional[float]] = [None] * len(requests)  # None: the run's own
-        for i, r in enumerate(requests):  # refused before anything runs
-            lv = getattr(r, "sparsity", None)
-            if lv is None or (self.sparsity is not None and float(lv) == self.sparsity):
-                continue
-            if float(lv) not in self.sparsity_levels:
-                raise ValueError(f"request {i}: no thresholds for sparsity {float(lv):g} (sparsity_levels)")
-            levels[i] = float(lv)
-        sparsity_levels_of(requests)
-        if any(lv is not None for lv in levels) and not self._sparsity_set:  # once: it drops the engine's captured step
-            eng.set_slot_sparsity(True)
-            self._sparsity_set = True
-        kept_sum, kept_n = [0.0] * len(requests), [0] * len(requests)
-        reasons: List[Optional[str]] = [None] * len(requests)
-        matches: List[int] = [-1] * len(requests)
+        for f in self.features:
+            f.plan(eng, requests)
         pending = deque(range(len(requests)))
-        lps: List[Optional[List[float]]] = [None] * len(requests)
-        tops: List[Optional[List]] = [None] * len(requests)
         slot_req: List[Optional[int]] = [None] * B
         admitted_at = [0] * B
         out: List[Optional[List[int]]] = [None] * len(requests)
         slots_used: List[int] = [-1] * len(requests)
-        steps = admissions = slot_steps = prefix_admissions = prefix_rows = 0
+        steps = admissions = slot_steps = 0
         step0 = eng.read_state()[SLOT_STEP]  # the engine's step counter (finish steps are on its scale)
         admit_spans = []
         t0 = time.perf_counter()
@@ -639,46 +746,26 @@ class ContinuousBatcher:
                         break
                     r = pending.popleft()
                     q = requests[r]
-                    kw = {"prefix": q.prefix} if plen[r] else {}
-                    kw.update(controls[r])
-                    T, k = self.temperature, self.top_k
-                    if self._sampling_set:
-                        T, k = sampling[r]["temperature"], sampling[r]["top_k"]
-                        kw.update(top_p=sampling[r]["top_p"], min_p=sampling[r]["min_p"])
-                    if self._stops_set:
-                        kw.update(stops[r])
-                    if cons[r] is not None:
-                        kw["constraint"] = cons[r]
-                    if levels[r] is not None:
-                        kw["thresholds"] = self.sparsity_levels[levels[r]]
-                    eng.admit(s, q.tokens, q.max_new_tokens, q.eos_id, self.seed + r if q.seed is None else q.seed, T, k, **kw)
-                    prefix_admissions += 1 if plen[r] else 0
-                    prefix_rows += plen[r]
+                    kw = {"temperature": self.temperature, "top_k": self.top_k}
+                    for f in self.features:
+                        kw.update(f.admit_kw(r))
+                    eng.admit(s, q.tokens, q.max_new_tokens, q.eos_id, self.seed + r if q.seed is None else q.seed,
+                              kw.pop("temperature"), kw.pop("top_k"), **kw)
                     slot_req[s], admitted_at[s], slots_used[r] = r, step0 + steps, s
                     admissions += 1
                 admit_spans.append((a0, self._clock()))
             eng.run_steps(self.K, self.temperature, self.top_k, self.use_graph)
             steps += self.K
             state = eng.read_state()
-            if self._sparsity_set:  # the burst's last step: the slots that ran it (still active, or stopped by it)
-                kept = eng.kept_by_slot()
-                for s in range(B):
-                    r = slot_req[s]
-                    ran = (state[SLOT_ACTIVE] >> s) & 1 or (state[SLOT_FINISH + s] == state[SLOT_STEP] - 1 and state[SLOT_PRODUCED + s] >= 2)
-                    if r is not None and ran:
-                        kept_sum[r] += sum(v[s] for v in kept.values()) / len(kept)
-                        kept_n[r] += 1
+            for f in self.features:
+                f.sync(eng, state, slot_req)
             for s in range(B):
                 r = slot_req[s]
                 if r is None or (state[SLOT_ACTIVE] >> s) & 1:
                     continue
                 out[r] = eng.read_history(s, state[SLOT_PRODUCED + s])
-                if self.logprobs is not None:
-                    lp, ids, tlp = eng.read_logprobs(s, state[SLOT_PRODUCED + s])
-                    lps[r] = [float(v) for v in lp]
-                    tops[r] = [[(int(i), float(v)) for i, v in zip(ii, vv)] for ii, vv in zip(ids, tlp)]
-                if self._stops_set:
-                    reasons[r], matches[r] = eng.read_finish(s)
+                for f in self.features:
+                    f.harvest(eng, s, r, state[SLOT_PRODUCED + s])
                 slot_steps += state[SLOT_FINISH + s] - admitted_at[s]
                 slot_req[s] = None
         c1 = self._clock()
@@ -688,22 +775,14 @@ class ContinuousBatcher:
         wall_dev = self._seconds(c0, c1)
         t_admit = sum(self._seconds(a, b) for a, b in admit_spans)
         useful = sum(len(o) for o in out)
-        extra = {}
-        if self.logprobs is not None:
-            extra["logprobs"] = lps
-            if self.logprobs > 0:
-                extra["top_logprobs"] = tops
-        if self._stops_set:
-            extra["finish_reason"], extra["stop_match"] = reasons, matches
-        if self._sparsity_set:  # (None: the request ran no step that a sync point saw)
-            extra["kept_by_request"] = [kept_sum[r] / kept_n[r] if kept_n[r] else None for r in range(len(requests))]
-        return {
-            **extra,
+        res = {
             "tokens": out, "slots": slots_used, "steps": steps, "admissions": admissions, "wall_s": wall,
             "admission_s": t_admit, "admission_share": t_admit / wall_dev if wall_dev > 0 else 0.0,
             "mean_active_slots": slot_steps / steps if steps else 0.0, "useful_tokens": useful,
             "useful_tokens_per_sec": useful / wall if wall > 0 else 0.0, "union_kept": eng.union_kept(),
             "refill": self.refill, "sync_every": self.K, "batch_size": B,
-            "prefix_admissions": prefix_admissions, "prefix_rows_reused": prefix_rows,
-            "prefix_paths": dict(getattr(eng, "prefix_paths", {})),
         }
+        for f in self.features:
+            res.update(f.result(eng))
+        return res
+

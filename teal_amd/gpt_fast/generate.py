@@ -670,11 +670,14 @@ def check_processor_args(args) -> Dict:
     the flags need an engine path: --compile / --engine (one sequence or --batch_size) or --requests, where they are the
     defaults of requests that carry none of their own."""
     from teal_amd.gpt_fast.continuous import parse_controls
-    given = {k: getattr(args, k, None) for k in ("repetition_penalty", "presence_penalty", "frequency_penalty")}
-    try:
-        c = parse_controls({k: v for k, v in given.items() if v is not None}, "generate")
-    except ValueError as e:
-        raise SystemExit(str(e).replace('generate: "', "--").replace('" must', " must"))
+    c = {}
+    for name, rule in (("repetition_penalty", "a finite number > 0 (1: off)"), ("presence_penalty", "a finite number"),
+                       ("frequency_penalty", "a finite number")):
+        if getattr(args, name, None) is not None:
+            try:
+                c.update(parse_controls({name: getattr(args, name)}, "generate"))
+            except ValueError:
+                raise SystemExit(f"--{name} must be {rule}") from None
     c = {k: v for k, v in c.items() if v != (1.0 if k == "repetition_penalty" else 0.0)}
     if not c:
         return {}
@@ -844,10 +847,36 @@ def check_requests_args(args) -> int:
     return int(getattr(args, "batch_size", 1) or 1)
 
 
-def check_request_sparsity(args) -> List[float]:
-    """the distinct "sparsity" levels the --requests lines carry, ascending; every refusal is raised here, before anything is loaded:
-    a level outside [0, 1), more than 8 distinct levels, and a level the run's threshold source cannot serve (a --greedy_lookup
-    .json table holds its own list of targets; histograms and --synthetic calibration serve any level)"""
+def _read_lines(path) -> List[str]:
+    return Path(path).read_text().splitlines()
+
+
+def check_request_files(args):
+    """--requests, --prefixes and --constraints, each read once -> (request lines, prefix lines, the constraints parsed, the
+    requests' sparsity levels).  What needs neither the model nor a tokenizer is refused here, before anything is loaded, in this
+    order: a malformed automaton or a request on a constraint nobody defined, a request on a prefix nobody defined, and
+    check_request_sparsity's refusals"""
+    from teal_amd.gpt_fast.continuous import check_constraint_ids, check_prefix_ids, parse_constraints
+    cf, pf = getattr(args, "constraints", None), getattr(args, "prefixes", None)
+    try:
+        request_lines = _read_lines(args.requests)
+        constraints = parse_constraints(_read_lines(cf)) if cf is not None else {}
+        check_constraint_ids(request_lines, constraints)
+    except (OSError, ValueError) as e:
+        raise SystemExit(f"--constraints: {e}" if cf is not None else f"--requests: {e}")
+    try:
+        prefix_lines = _read_lines(pf) if pf is not None else []
+        check_prefix_ids(request_lines, prefix_lines)
+    except (OSError, ValueError) as e:
+        raise SystemExit(f"--requests: {e}")
+    return request_lines, prefix_lines, constraints, check_request_sparsity(args, request_lines)
+
+
+def check_request_sparsity(args, request_lines: Optional[List[str]] = None) -> List[float]:
+    """the distinct "sparsity" levels the --requests lines carry (request_lines: the file's, where the caller has read it),
+    ascending; every refusal is raised here, before anything is loaded: a level outside [0, 1), more than 8 distinct levels, and a
+    level the run's threshold source cannot serve (a --greedy_lookup .json table holds its own list of targets; histograms and
+    --synthetic calibration serve any level)"""
     from teal_amd.gpt_fast.continuous import check_sparsity_fields
     servable = None
     lookup = getattr(args, "greedy_lookup", None)
@@ -860,7 +889,7 @@ def check_request_sparsity(args) -> List[float]:
                 return None
             return f"--greedy_lookup {lookup} has no such target (it holds {', '.join(sorted(targets))})"
     try:
-        return check_sparsity_fields(Path(args.requests).read_text().splitlines(), servable)
+        return check_sparsity_fields(_read_lines(args.requests) if request_lines is None else request_lines, servable)
     except (OSError, ValueError) as e:
         raise SystemExit(f"--requests: {e}")
 
@@ -888,45 +917,36 @@ def resolve_sparsity_levels(args, model: Transformer, levels) -> Dict[float, Lis
 
 
 @torch.no_grad()
-def run_continuous(args, model: Transformer, thresholds, tokenizer, sparsity_levels=None) -> Dict:
+def run_continuous(args, model: Transformer, thresholds, tokenizer, request_lines, prefix_lines=(), constraints=None,
+                   sparsity_levels=None) -> Dict:
     """--requests FILE through ContinuousBatcher on a SlotDecodeEngine of --batch_size slots (one hipGraph replay per step under
-    --compile, with one warm-up run first)"""
+    --compile, with one warm-up run first).  request_lines / prefix_lines / constraints: what check_request_files read"""
     from teal_amd.gpt_fast.batched import SlotDecodeEngine
-    from teal_amd.gpt_fast.continuous import ContinuousBatcher, cache_rows, parse_constraints, parse_prefixes, parse_requests
+    from teal_amd.gpt_fast.continuous import ContinuousBatcher, cache_rows, parse_prefixes, parse_requests
+    from teal_amd.gpt_fast.stopping import check_stops
     B = int(args.batch_size)
-    constraints = {}
-    if getattr(args, "constraints", None) is not None:
+    constraints = constraints or {}
+    for name, a in constraints.items():  # a token outside this model's vocabulary: refused before anything runs
         try:
-            with open(args.constraints) as f:
-                constraints = parse_constraints(f.read().splitlines())
-            for name, a in constraints.items():  # a token outside this model's vocabulary: refused before anything runs
-                try:
-                    a.check(model.config.vocab_size, args.eos_id, eos_known=args.eos_id is not None)
-                except ValueError as e:
-                    raise ValueError(f"constraint {name!r}: {e}") from None
-        except (OSError, ValueError) as e:
-            raise SystemExit(f"--constraints: {e}")
-    prefixes = {}
-    if getattr(args, "prefixes", None) is not None:
-        try:
-            with open(args.prefixes) as f:
-                prefixes = parse_prefixes(f.read().splitlines(), tokenizer)
-        except (OSError, ValueError) as e:
-            raise SystemExit(f"--prefixes: {e}")
+            a.check(model.config.vocab_size, args.eos_id, eos_known=args.eos_id is not None)
+        except ValueError as e:
+            raise SystemExit(f"--constraints: constraint {name!r}: {e}")
     try:
-        with open(args.requests) as f:
-            reqs = parse_requests(f.read().splitlines(), args.max_new_tokens, tokenizer, args.eos_id, prefixes=prefixes,
-                                  constraints=constraints)
+        prefixes = parse_prefixes(prefix_lines, tokenizer)
+    except ValueError as e:
+        raise SystemExit(f"--prefixes: {e}")
+    stop_kw = check_stop_args(args)
+    try:
+        reqs = parse_requests(request_lines, args.max_new_tokens, tokenizer, args.eos_id, prefixes=prefixes, constraints=constraints)
         max_seq = cache_rows(reqs, model.config.block_size, prefixes)
         if prefixes:  # (a prefix no request names is registered too: it needs room for a one-token suffix)
             max_seq = max(max_seq, min(max(len(t) for t in prefixes.values()) + 2, model.config.block_size))
-        from teal_amd.gpt_fast.stopping import check_stops
         for i, r in enumerate(reqs):  # an id outside this model's vocabulary: refused before anything runs
             try:
-                check_stops(model.config.vocab_size, **r.stops(check_stop_args(args)))
+                check_stops(model.config.vocab_size, **r.stops(stop_kw))
             except ValueError as e:
                 raise ValueError(f"request {i}: {e}") from None
-    except (OSError, ValueError) as e:
+    except ValueError as e:
         raise SystemExit(f"--requests: {e}")
     model.setup_caches(max_batch_size=B, max_seq_length=max_seq)
     why = SlotDecodeEngine.supports(model)
@@ -935,7 +955,7 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer, sparsity_lev
     eng = SlotDecodeEngine(model, thresholds, B)
     batcher = ContinuousBatcher(eng, sync_every=args.sync_every, temperature=args.temperature, top_k=args.top_k, seed=1234,
                                 use_graph=bool(args.compile), prefixes=prefixes, logprobs=getattr(args, "logprobs", None),
-                                **check_processor_args(args), **check_sampling_args(args), **check_stop_args(args),
+                                **check_processor_args(args), **check_sampling_args(args), **stop_kw,
                                 **({"constraints": constraints} if constraints else {}),
                                 sparsity=float(args.sparsity), sparsity_levels=sparsity_levels or {})
     try:
@@ -1000,20 +1020,7 @@ def main(args) -> Dict:
                          "admission and ends on the request's EOS id)")
     if getattr(args, "requests", None) is not None:
         check_requests_args(args)
-        from teal_amd.gpt_fast.continuous import check_constraint_ids, parse_constraints
-        try:  # a malformed automaton, or a request on a constraint nobody defined: refused before anything is loaded, too
-            cf = getattr(args, "constraints", None)
-            check_constraint_ids(Path(args.requests).read_text().splitlines(),
-                                 parse_constraints(Path(cf).read_text().splitlines()) if cf is not None else {})
-        except (OSError, ValueError) as e:
-            raise SystemExit(f"--constraints: {e}" if cf is not None else f"--requests: {e}")
-        from teal_amd.gpt_fast.continuous import check_prefix_ids
-        try:  # a request on a prefix nobody defined: refused before anything is loaded, too
-            pf = getattr(args, "prefixes", None)
-            check_prefix_ids(Path(args.requests).read_text().splitlines(), Path(pf).read_text().splitlines() if pf is not None else [])
-        except (OSError, ValueError) as e:
-            raise SystemExit(f"--requests: {e}")
-        levels = check_request_sparsity(args)
+        request_lines, prefix_lines, constraints, levels = check_request_files(args)
     if getattr(args, "interactive", False) and args.synthetic:
         raise SystemExit("--interactive needs a tokenizer (a checkpoint directory), not --synthetic")
     dtype = {"fp16": torch.float16, "bf16": torch.bfloat16}[args.precision]
@@ -1064,7 +1071,7 @@ def main(args) -> Dict:
         if level_ths is not None and 0.0 in level_ths:
             from teal_amd.gpt_fast.score import dense_thresholds
             level_ths[0.0] = dense_thresholds(thresholds)
-        return run_continuous(args, model, thresholds, tokenizer, level_ths)
+        return run_continuous(args, model, thresholds, tokenizer, request_lines, prefix_lines, constraints, level_ths)
     if batch > 1:
         if args.synthetic:  # B distinct seeded prompts of equal length
             prompts = torch.randint(0, model.config.vocab_size, (batch, prompt.numel()), device=device, dtype=torch.int,

@@ -200,7 +200,8 @@ def test_parse_requests():
             return [ord(c) for c in s]
     assert parse_requests(['{"prompt": "hi"}'], 5, Tok())[0].tokens == [1, ord("h"), ord("i")]
     for bad, msg in [('{"prompt": "hi"}', "tokenizer"), ('{"tokens": []}', "non-empty"), ('{"tokens": [1], "prompt": "x"}', "exactly one"),
-                     ('{"tokens": [1], "max_new_tokens": 0}', "positive"), ("not json", "not JSON"), ('{"tokens": [-1]}', "token ids")]:
+                     ('{"tokens": [1], "max_new_tokens": 0}', "positive"), ("not json", "not JSON"), ('{"tokens": [-1]}', "token ids"),
+                     ('{"tokens": [1, true]}', "token ids")]:
         with pytest.raises(ValueError, match=msg):
             parse_requests([bad], 5)
     with pytest.raises(ValueError, match="no requests"):

@@ -10,7 +10,8 @@ threshold sets of the same weights.  Prompts have 2..16 tokens: their prompt pas
   5. a slot re-admitted without `thresholds` runs at the default: its whole column is rewritten;
   6. with the feature off a step launches what it launched before; on, the layers' GEMMs are the new entry and the lm_head is not;
   7. the setter's and the admission's refusals;
-  8. generate.py --requests end to end on a file that mixes levels.
+  8. a refused admission has written nothing: the threshold table, the constraint rows and the stop table are bit-equal;
+  9. generate.py --requests end to end on a file that mixes levels.
 """
 import functools
 import math
@@ -19,6 +20,7 @@ import pytest
 import torch
 
 from teal_amd.gpt_fast.batched import PROJ_KEYS, SLOT_ACTIVE, SLOT_PRODUCED, BatchedDecodeEngine, SlotDecodeEngine
+from teal_amd.gpt_fast.constraints import Automaton
 from teal_amd.gpt_fast.engine import DecodeEngine
 from teal_amd.gpt_fast.score import dense_thresholds
 from test_logit_engine_gpu import _calls_of, _main, _model
@@ -177,6 +179,36 @@ def test_refusals():
         other.set_slot_sparsity(False)
         with pytest.raises(NotImplementedError, match="admission"):
             other.set_slot_sparsity(True)
+
+
+def test_a_refused_admission_leaves_the_slot_as_it_found_it():
+    """admit refuses before its first write to a device table: with slot sparsity, constraints, stop conditions and logit
+    processors on and per-request sampling off, neither the "sampling is off" refusal (it used to come after the slot's threshold
+    column and constraint row were written) nor one of the logit processors' changes the threshold table, the constraint rows or
+    the stop table by a bit, and the slot stays free"""
+    _, _, ths_a, _ = _setup("tiny-test")
+    m, ths = _model("tiny-test", None, 2, max_seq=MAX_SEQ, sparsity=0.5)
+    eng = SlotDecodeEngine(m, ths, 2)
+    eng.set_slot_sparsity(True)
+    eng.set_constraints(True)
+    eng.set_stop_conditions(True)
+    eng.set_logit_processors(True)
+    eng.register_constraint("yn", Automaton.from_allowed([1, 2]))
+    assert eng._samp is None
+
+    def snapshot():
+        return eng.tau_table.clone(), list(eng._con.row_names), eng.stop_table.clone()
+    before = snapshot()
+    prompt, budget, seed = REQS[0]
+    refused = ((RuntimeError, "per-request sampling is off", dict(thresholds=ths_a, constraint="yn", top_p=0.9)),
+               (ValueError, "logit_bias: token id", dict(stop_token_ids=[1], logit_bias={str(eng.cfg.vocab_size): 1.0})))
+    for exc, why, kw in refused:
+        with pytest.raises(exc, match=why):
+            eng.admit(1, prompt, budget, None, seed, **KW, **kw)
+        after = snapshot()
+        assert torch.equal(after[0].view(torch.int32), before[0].view(torch.int32)) and after[1] == before[1]
+        assert torch.equal(after[2], before[2])
+        assert eng.read_state()[SLOT_ACTIVE] == 0
 
 
 def test_generate_requests_end_to_end_with_mixed_levels(tmp_path):
