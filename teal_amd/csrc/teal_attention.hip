@@ -1,7 +1,7 @@
 // teal_attention.hip — batch-1 decode attention (single-workgroup and split-KV / flash-decoding forms) with its C-ABI
 // entry points (include/teal_hip.h).  (The fused top-k sampler is teal_sampler.hip.)
 //   gpt-fast/model.py:170-186   RoPE + kv_cache.update + SDPA at S = 1   -> decode_attention*_kernel
-#include "teal_common.h"
+#include "teal_producers.h"
 
 namespace teal {
 
@@ -296,7 +296,6 @@ __global__ __launch_bounds__(NT) void decode_attention_split_kernel(
     }
     // q, k, v of this head: the rounded projection, or its fp32 split-K slabs, interleaved [col][(nslabs + 3) & ~3],
     // summed in slice order and rounded once here (what the ordered reduce launch would have written)
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     const int sstride = (qkv_nslabs + 3) & ~3;
     auto raw_at = [&](const int col, f32x4& a, f32x4& b, uint16_t& r) {
         if (qkv_slabs) {
@@ -601,7 +600,6 @@ __global__ __launch_bounds__(NT) void decode_attention_gqa_kernel(
     constexpr int PF = 4, RD = 8, STEP = NW * RW;  // blind prefetch depth; depth of the stream once *pos is known
     constexpr int NPAIR = (REP + 2) * (HD / 2), NITEM = (NPAIR + NT - 1) / NT;  // q pairs of REP heads, k pairs, v pairs
     typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     static_assert(NT % REP == 0 && (REP == 4 || REP == 8), "softmax pass assigns head tid % REP to a thread");
     extern __shared__ __align__(16) unsigned char smem[];
     uint32_t* qsb = reinterpret_cast<uint32_t*>(smem);  // [REP][hd / 2] rotated, rounded q (packed pairs)

@@ -157,13 +157,7 @@ __global__ __launch_bounds__(1024) void batched_gemm_kernel(const SlabProd pr, c
         const int nrows = min(PHASE_GROUPS, nj - jb) * 16;
         if (jb) __syncthreads();  // the previous phase's list and rows are consumed
         [[maybe_unused]] float rstd[8];
-        if constexpr (PROD == 1) {
-            f32x4 pw[2];
-#pragma unroll
-            for (int w = 0; w < 2; ++w) pw[w] = lane < pr.nwg ? *reinterpret_cast<const f32x4*>(pr.sumsq + (size_t)lane * 8 + 4 * w) : (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s = 0; s < 8; ++s) rstd[s] = rsqrtf(wave_sum_f(pw[s >> 2][s & 3]) / (float)Z + pr.eps);
-        }
+        if constexpr (PROD == 1) rstd_rows<8>(pr.sumsq, pr.nwg, lane, Z, pr.eps, rstd);
         // ---- staging: the rows' activations (16-bit, what the module path holds) and their keep masks
         [[maybe_unused]] float tslot[3][8];  // TAUS: [local segment][slot]
         if constexpr (TAUS) {
@@ -182,19 +176,13 @@ __global__ __launch_bounds__(1024) void batched_gemm_kernel(const SlabProd pr, c
                 const float nw = bits_to_float(pr.norm_w[m], BF16);
                 unpack_row<BF16>(*reinterpret_cast<const u32x4*>(pr.xt + (size_t)m * 8), x);
 #pragma unroll
-                for (int s = 0; s < 8; ++s) {
-                    const float xn = bits_to_float(float_to_bits<BF16>(x[s] * rstd[s]), BF16);
-                    x[s] = bits_to_float(float_to_bits<BF16>(xn * nw), BF16);
-                }
+                for (int s = 0; s < 8; ++s) x[s] = bits_to_float(norm_bits<BF16>(x[s], rstd[s], nw), BF16);
             } else {  // x = round(round(silu(round(gate))) * round(up))  (gpt-fast/model.py:258-259)
                 float gv[8], uv[8];
                 slab_column<BF16, 8>(pr.gu, pr.gu_split, (size_t)2 * Z, (size_t)m, gv);
                 slab_column<BF16, 8>(pr.gu, pr.gu_split, (size_t)2 * Z, (size_t)Z + m, uv);
 #pragma unroll
-                for (int s = 0; s < 8; ++s) {
-                    const float sl = bits_to_float(float_to_bits<BF16>(gv[s] / (1.0f + expf(-gv[s]))), BF16);
-                    x[s] = bits_to_float(float_to_bits<BF16>(sl * uv[s]), BF16);
-                }
+                for (int s = 0; s < 8; ++s) x[s] = bits_to_float(silu_mul_bits<BF16>(gv[s], uv[s]), BF16);
             }
             uint32_t mk = 0;
 #pragma unroll

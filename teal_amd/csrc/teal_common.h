@@ -16,6 +16,7 @@ namespace teal {
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kMaxSeg = 3;
 constexpr int kMaxSplit = 32;
@@ -195,19 +196,6 @@ __device__ __forceinline__ uint16_t float_to_bits(float f) {
     // decode step — specified to be bit-identical — differed in one head every few layers (tests/test_soak.py).
     asm("" : "+v"(f));
     return __builtin_bit_cast(uint16_t, (_Float16)f);
-}
-
-// RoPE of one (even, odd) pair (gpt-fast/model.py:apply_rotary_emb: x0 * cos - x1 * sin, x1 * cos + x0 * sin), written with
-// explicit fused multiply-adds so that every translation unit — whatever its -ffp-contract setting — rounds the same way:
-// the qkv projection's epilogue (teal_gemv_fast.h, ROPE) and the attention launches must agree bit for bit.
-__device__ __forceinline__ float rope_even(float x0, float x1, float c, float s) { return fmaf(x0, c, -(x1 * s)); }
-__device__ __forceinline__ float rope_odd(float x0, float x1, float c, float s) { return fmaf(x1, c, x0 * s); }
-
-// round(silu(round(sum))): the gate projection's output with the activation applied where it is computed (model.py:258)
-template <bool BF16>
-__device__ __forceinline__ uint16_t silu_bits(const float sum) {
-    const float g16 = bits_to_float(float_to_bits<BF16>(sum), BF16);
-    return float_to_bits<BF16>(g16 / (1.0f + expf(-g16)));
 }
 
 // keep rule of the reference kernel: float32(|x|) > float32(tau)  (kernels/sparse_gemv.py:75)

@@ -1,7 +1,7 @@
 // teal_gemv_fast.h — the lean sparse GEMV kernel of the fused decode step (16-bit weights, whole 64-element chunks,
-// whole column tiles).  Same algorithm and the same arithmetic, in the same order, as sparse_gemv_kernel
-// (teal_gemv_kernel.h, which stays the general kernel: ragged shapes, int8 weights, planar slabs, long vectors), i.e.
-// it replaces the same reference code:
+// whole column tiles).  The algorithm of sparse_gemv_kernel (teal_gemv_kernel.h, which stays the general kernel: ragged
+// shapes, int8 weights, planar slabs, long vectors) with the producers and epilogue chains of teal_producers.h, i.e. it
+// replaces the same reference code:
 //   kernels/sparse_gemv.py:50-83    splitk_sparse_gemv_kernel   (mask + gathered GEMV)
 //   kernels/sparse_gemv.py:152-194  qkv_kernel                  (three thresholds over one fused weight)
 //   gpt-fast/model.py:158-161,258-259,289-291                   (residual adds, RMSNorm, silu(gate) * up: fused producers)
@@ -100,7 +100,6 @@ __global__ __launch_bounds__(1024) void gemv_fast_kernel(const void* in0, const 
         if (row_index) resid += (size_t)row_index[0] * (size_t)Z;  // embedding row of the current token
         const uint16_t* nw = reinterpret_cast<const uint16_t*>(in2);
         const float* slabs = reinterpret_cast<const float*>(in1);
-        typedef float f32x4 __attribute__((ext_vector_type(4)));
         uint32_t rb[KR];
         f32x4 v0[KR], v1[KR];
         // bit 8 of the (preloaded) slab count: ONE planar fp32 vector [Z] — the sum a TEAL_OUT_SLAB_SUM launch left (tensor
@@ -159,10 +158,7 @@ __global__ __launch_bounds__(1024) void gemv_fast_kernel(const void* in0, const 
 #pragma unroll
         for (int k = 0; k < KR; ++k) {
             float r = bits_to_float(rb[k], BF16);
-            if (ns > 0) {
-                const float yv = bits_to_float(float_to_bits<BF16>(ysum[k]), BF16);
-                r = bits_to_float(float_to_bits<BF16>(r + yv), BF16);
-            }
+            if (ns > 0) r = resid_add<BF16>(r, ysum[k]);
             if (!EXACT) r = (cidx[k] < nch) ? r : 0.0f;
             rv[k] = r;
             sumsq_part = fmaf(r, r, sumsq_part);  // explicit: see the contract(off) note at the top of teal_gemv_kernel.h
@@ -173,20 +169,17 @@ __global__ __launch_bounds__(1024) void gemv_fast_kernel(const void* in0, const 
         if (lane == 0) sumsq[wave] = ssw;
         __syncthreads();
         stamp(9);
-        float tot = (lane < WAVES) ? sumsq[lane] : 0.0f;
-        tot = wave_sum_f(tot);
-        const float rstd = rsqrtf(tot / (float)Z + eps);
+        const float rstd = rms_rstd<WAVES>(sumsq, lane, Z, eps);
         uint16_t* rout = reinterpret_cast<uint16_t*>(a.resid_out);
         const bool writer = rout && blockIdx.x == 0 && blockIdx.y == 0;  // (not via bid: gridDim.x is a scalar load)
 #pragma unroll
         for (int k = 0; k < KR; ++k) {
-            const float xn = bits_to_float(float_to_bits<BF16>(rv[k] * rstd), BF16);
-            xr[k] = float_to_bits<BF16>(xn * bits_to_float(wb[k], BF16));
+            xr[k] = norm_bits<BF16>(rv[k], rstd, wb[k]);
             if (writer && (EXACT || cidx[k] < nch)) rout[(uint32_t)cidx[k] * 64u + lane] = float_to_bits<BF16>(rv[k]);
         }
     } else if constexpr (MODE == 4) {
-        // attention output merged from the split-KV partials {max, sum, o[hd]} per (head, split): see the merge
-        // producer of sparse_gemv_kernel; one lane per (cached chunk, split) fetches {max, sum}
+        // attention output merged from the split-KV partials {max, sum, o[hd]} per (head, split) (merge_weight, merge_bits:
+        // teal_producers.h); one lane per (cached chunk, split) fetches {max, sum}
         // head_dim (64 / 128) and the partials per head arrive in the preloaded `nslabs` slot as att_ns | log2(head_dim) << 8:
         // nothing the merge's loads need waits for the argument batch, and head_dim divides by shifts
         const float* att = reinterpret_cast<const float*>(in0);
@@ -209,37 +202,10 @@ __global__ __launch_bounds__(1024) void gemv_fast_kernel(const void* in0, const 
             }
             TEAL_FAST_ARGS_BATCH(a);
             stamp(1);
-#define TEAL_DPPF(v, ctrl) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xf, 0xf, false))
-            float M = fmaxf(st.x, TEAL_DPPF(st.x, 0xB1));
-            M = fmaxf(M, TEAL_DPPF(M, 0x4E));
-            if constexpr (NS == 8) M = fmaxf(M, TEAL_DPPF(M, 0x141));
-            const float f = st.y > 0.0f ? expf(st.x - M) : 0.0f;
-            float Ls = st.y * f;
-            Ls += TEAL_DPPF(Ls, 0xB1);
-            Ls += TEAL_DPPF(Ls, 0x4E);
-            if constexpr (NS == 8) Ls += TEAL_DPPF(Ls, 0x141);
-#undef TEAL_DPPF
-            const int cw = __float_as_int(f / Ls);
-            // A split that contributes nothing (empty: sum 0; or e^(m - M) underflowed) is skipped, as merge_head does
-            // (teal_attention.hip: `if (ls > 0)`): whatever its o holds, NaN included, stays out of the sum.  Every lane holds
-            // the weight of a (chunk, split) the wave uses, so one ballot tells whether any split is skipped at all: the
-            // usual case, none, keeps the unguarded chain (wave-uniform branch)
-            const bool all_live = __ballot(__int_as_float(cw) > 0.0f) == ~0ull;
+            const int cw = merge_weight<NS>(st);
+            const bool all_live = merge_all_live(cw);
 #pragma unroll
-            for (int k = 0; k < KR; ++k) {
-                float Os = 0.0f;
-                if (all_live) {
-#pragma unroll
-                    for (int q = 0; q < NS; ++q) Os = fmaf(ov[k][q], __int_as_float(__builtin_amdgcn_readlane(cw, NS * k + q)), Os);
-                } else {
-#pragma unroll
-                    for (int q = 0; q < NS; ++q) {
-                        const float wq = __int_as_float(__builtin_amdgcn_readlane(cw, NS * k + q));
-                        if (wq > 0.0f) Os = fmaf(ov[k][q], wq, Os);
-                    }
-                }
-                xr[k] = float_to_bits<BF16>(Os);
-            }
+            for (int k = 0; k < KR; ++k) xr[k] = merge_bits<BF16, NS>(ov[k], cw, k, all_live);
         };
         if constexpr (KR * 8 <= 64) {
             if (att_ns == 8) merge(std::integral_constant<int, 8>{});
@@ -263,11 +229,7 @@ __global__ __launch_bounds__(1024) void gemv_fast_kernel(const void* in0, const 
             for (int k = 0; k < KR; ++k) xr[k] = float_to_bits<BF16>(bits_to_float(gb[k], BF16) * bits_to_float(ub[k], BF16));
         } else {
 #pragma unroll
-        for (int k = 0; k < KR; ++k) {
-            const float gt = bits_to_float(gb[k], BF16);
-            const float sl = bits_to_float(float_to_bits<BF16>(gt / (1.0f + expf(-gt))), BF16);
-            xr[k] = float_to_bits<BF16>(sl * bits_to_float(ub[k], BF16));
-        }
+            for (int k = 0; k < KR; ++k) xr[k] = silu_mul_bits<BF16>(bits_to_float(gb[k], BF16), ub[k]);
         }
     } else {
 #pragma unroll
@@ -528,10 +490,10 @@ __global__ __launch_bounds__(1024) void gemv_fast_kernel(const void* in0, const 
         if constexpr (PAIR) {
             // h = silu(gate) * up with the roundings of the unfused sequence (gpt-fast/model.py:258-259), and the keep
             // masks of h against the down projection's threshold for a MODE 3 consumer
-            const float g16 = bits_to_float(float_to_bits<BF16>(gs), BF16);
-            const float u16 = bits_to_float(float_to_bits<BF16>(us), BF16);
-            const float sl = bits_to_float(float_to_bits<BF16>(g16 / (1.0f + expf(-g16))), BF16);
-            const uint32_t hb = float_to_bits<BF16>(sl * u16);
+            const float g16 = round16<BF16>(gs);
+            const float u16 = round16<BF16>(us);
+            const float sl = silu16<BF16>(g16);
+            const uint32_t hb = mul_bits<BF16>(sl, u16);
             reinterpret_cast<uint16_t*>(a.y)[c] = (uint16_t)hb;
             const float hv = bits_to_float(hb, BF16);
             const unsigned long long mko = __ballot(keep_rule(hv, a.mask_tau) || (hv != hv));

@@ -37,11 +37,11 @@
 // explicit fmaf(), so the slab path and the rounded path, and this unit against the merge producers elsewhere, cannot drift
 // by an ulp when the compiler changes its mind.
 #pragma clang fp contract(off)
+#include "teal_producers.h"  // (below the pragma: the chains are compiled under this unit's rule)
 #include <stdio.h>
 
 namespace teal {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 constexpr int kPhaseRow = 32;  // uint64 stamps per workgroup (as in teal_gemv_kernel.h)
 
@@ -178,8 +178,7 @@ __global__ __launch_bounds__(1024) void sparse_gemv_int4_kernel(const I4Args a) 
 #pragma unroll
                             for (int q = 0; q < 4; ++q) sacc += (4 + q < nslabs) ? v1[j][q] : 0.0f;
                         }
-                        const float yv = bits_to_float(float_to_bits<BF16>(sacc), BF16);
-                        r = bits_to_float(float_to_bits<BF16>(r + yv), BF16);
+                        r = resid_add<BF16>(r, sacc);
                     }
                     if (m < Z) {
                         xs[m] = float_to_bits<BF16>(r);  // exact: r is a 16-bit value
@@ -190,16 +189,13 @@ __global__ __launch_bounds__(1024) void sparse_gemv_int4_kernel(const I4Args a) 
             ss = wave_sum_f(ss);
             if (lane == 0) wsum[wave] = ss;
             __syncthreads();
-            float tot = lane < WAVES ? wsum[lane] : 0.0f;
-            tot = wave_sum_f(tot);
-            const float rstd = rsqrtf(tot / (float)Z + a.eps);
+            const float rstd = rms_rstd<WAVES>(wsum, lane, Z, a.eps);
 #pragma unroll
             for (int k = 0; k < KM; ++k) {
                 const int m = tid + (k << 10);
                 if (m < Z) {
                     const uint32_t hb = xs[m];  // this thread's own element
-                    const float xn = bits_to_float(float_to_bits<BF16>(bits_to_float(hb, BF16) * rstd), BF16);
-                    xs[m] = float_to_bits<BF16>(xn * bits_to_float(wb[k], BF16));
+                    xs[m] = norm_bits<BF16>(bits_to_float(hb, BF16), rstd, wb[k]);
                     if (writer) a.resid_out[m] = (uint16_t)hb;
                 }
             }
@@ -305,14 +301,11 @@ __global__ __launch_bounds__(1024) void sparse_gemv_int4_kernel(const I4Args a) 
                 ub[i] = a.x[(uint32_t)Z + m_el[i]];
             }
 #pragma unroll
-            for (int i = 0; i < UP; ++i) {
-                const float gt = bits_to_float(gb[i], BF16);
-                const float sl = bits_to_float(float_to_bits<BF16>(gt / (1.0f + expf(-gt))), BF16);
-                xb[i] = float_to_bits<BF16>(sl * bits_to_float(ub[i], BF16));
-            }
+            for (int i = 0; i < UP; ++i) xb[i] = silu_mul_bits<BF16>(bits_to_float(gb[i], BF16), ub[i]);
         } else {
-            // attention output merged from the split-KV partials {max, sum, o[hd]} per (head, split); the arithmetic of the
-            // 16-bit kernel's merge producer: pairwise-tree sum of the rescaled denominators, fmaf chain over the splits
+            // attention output merged from the split-KV partials {max, sum, o[hd]} per (head, split), per element in registers with
+            // no cross-lane step; its result must equal merge_weight + merge_bits (teal_producers.h): the denominators' sum in the
+            // order of that butterfly (a pairwise tree), the same fmaf chain over the splits
             const int hd = a.att_hd, hs = hd + 2;
             auto merge = [&](auto ns_tag, auto i0_tag, auto n_tag) {
                 constexpr int NS = decltype(ns_tag)::value, I0 = decltype(i0_tag)::value, NU = decltype(n_tag)::value;

@@ -30,6 +30,7 @@
 // are specified to be bit-identical — were not (round 2's "wo slabs DIFF"; found by tests/test_soak.py).  With the
 // contraction explicit, what is written is what runs, in both.
 #pragma clang fp contract(off)
+#include "teal_producers.h"  // (below the pragma: the chains are compiled under this unit's rule)
 
 namespace teal {
 
@@ -160,12 +161,11 @@ __global__ __launch_bounds__(WAVES * 64) void sparse_gemv_kernel(const Params p)
     // activation of element m after the fused producer (modes 0 and 2 are element-wise)
     auto load_act = [&](const int m) -> uint32_t {
         if constexpr (MODE == 2) {
-            // silu(gate) * up with the roundings of the unfused fp16/bf16 sequence (model.py:258-259)
             const float gt = bits_to_float(x[m], BF16);
             const float up = bits_to_float(x[Z + m], BF16);
             if (p.in.gate_act) return float_to_bits<BF16>(gt * up);  // the producer applied silu (act_seg0)
-            const float sl = bits_to_float(float_to_bits<BF16>(gt / (1.0f + expf(-gt))), BF16);
-            return float_to_bits<BF16>(sl * up);
+            const float sl = silu16<BF16>(gt);  // (the halves of silu_mul_bits, as in the MODE 2 branch below)
+            return mul_bits<BF16>(sl, up);
         } else {
             return (uint32_t)x[m];
         }
@@ -190,7 +190,6 @@ __global__ __launch_bounds__(WAVES * 64) void sparse_gemv_kernel(const Params p)
             // producer wrote ws[col][slice]: all slabs of an element arrive in one (two) 16-byte loads,
             // issued together with the residual/weight loads above -> a single memory round trip
             const int stride = (p.in.nslabs + 3) & ~3;
-            typedef float f32x4 __attribute__((ext_vector_type(4)));
             f32x4 v0[KR], v1[KR];
 #pragma unroll
             for (int k = 0; k < KR; ++k) {
@@ -231,10 +230,7 @@ __global__ __launch_bounds__(WAVES * 64) void sparse_gemv_kernel(const Params p)
         for (int k = 0; k < KR; ++k) {
             const int m = (chunk_of(k) << 6) + lane;
             float r = bits_to_float(rb[k], BF16);
-            if (p.in.nslabs > 0) {
-                const float yv = bits_to_float(float_to_bits<BF16>(sacc[k]), BF16);
-                r = bits_to_float(float_to_bits<BF16>(r + yv), BF16);
-            }
+            if (p.in.nslabs > 0) r = resid_add<BF16>(r, sacc[k]);
             r = (m < Z) ? r : 0.0f;
             rv[k] = r;
             ss = fmaf(r, r, ss);  // explicit: see the contract(off) note at the top of this file
@@ -244,15 +240,15 @@ __global__ __launch_bounds__(WAVES * 64) void sparse_gemv_kernel(const Params p)
         if (lane == 0) sumsq[wave] = ss;
         __syncthreads();
         stamp(p, 9);   // past the producer barrier
-        float tot = (lane < WAVES) ? sumsq[lane] : 0.0f;
+        float tot = (lane < WAVES) ? sumsq[lane] : 0.0f;  // rms_rstd (teal_producers.h), inline: as a call it moved this kernel's code
         tot = wave_sum_f(tot);
         const float rstd = rsqrtf(tot / (float)Z + p.in.eps);
         uint16_t* rout = reinterpret_cast<uint16_t*>(p.in.resid_out);
 #pragma unroll
         for (int k = 0; k < KR; ++k) {
             const int m = (chunk_of(k) << 6) + lane;
-            const float xn = bits_to_float(float_to_bits<BF16>(rv[k] * rstd), BF16);
-            xr[k] = (m < Z) ? (uint32_t)float_to_bits<BF16>(xn * bits_to_float(wb[k], BF16)) : 0u;
+            const float xn = norm_scale<BF16>(rv[k], rstd);
+            xr[k] = (m < Z) ? (uint32_t)mul_bits<BF16>(xn, wb[k]) : 0u;
             if (rout && blockIdx.x == 0 && m < Z) rout[m] = float_to_bits<BF16>(rv[k]);
         }
     } else if constexpr (MODE == 4) {
@@ -277,37 +273,10 @@ __global__ __launch_bounds__(WAVES * 64) void sparse_gemv_kernel(const Params p)
 #pragma unroll
                 for (int q = 0; q < NS; ++q) ov[k][q] = b[q * hs];
             }
-#define TEAL_DPPF(v, ctrl) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xf, 0xf, false))
-            float M = fmaxf(st.x, TEAL_DPPF(st.x, 0xB1));  // quad_perm [1,0,3,2]
-            M = fmaxf(M, TEAL_DPPF(M, 0x4E));              // quad_perm [2,3,0,1]
-            if constexpr (NS == 8) M = fmaxf(M, TEAL_DPPF(M, 0x141));  // row_half_mirror: lane i <-> 7 - i
-            const float f = st.y > 0.0f ? expf(st.x - M) : 0.0f;
-            float Ls = st.y * f;
-            Ls += TEAL_DPPF(Ls, 0xB1);
-            Ls += TEAL_DPPF(Ls, 0x4E);
-            if constexpr (NS == 8) Ls += TEAL_DPPF(Ls, 0x141);
-#undef TEAL_DPPF
-            const int cw = __float_as_int(f / Ls);
-            // A split that contributes nothing (empty: sum 0; or e^(m - M) underflowed) is skipped, as merge_head does
-            // (teal_attention.hip: `if (ls > 0)`): whatever its o holds, NaN included, stays out of the sum.  Every lane holds
-            // the weight of a (chunk, split) the wave uses, so one ballot tells whether any split is skipped at all: the
-            // usual case, none, keeps the unguarded chain (wave-uniform branch)
-            const bool all_live = __ballot(__int_as_float(cw) > 0.0f) == ~0ull;
+            const int cw = merge_weight<NS>(st);
+            const bool all_live = merge_all_live(cw);
 #pragma unroll
-            for (int k = 0; k < KM; ++k) {
-                float Os = 0.0f;
-                if (all_live) {
-#pragma unroll
-                    for (int q = 0; q < NS; ++q) Os = fmaf(ov[k][q], __int_as_float(__builtin_amdgcn_readlane(cw, NS * k + q)), Os);
-                } else {
-#pragma unroll
-                    for (int q = 0; q < NS; ++q) {
-                        const float wq = __int_as_float(__builtin_amdgcn_readlane(cw, NS * k + q));
-                        if (wq > 0.0f) Os = fmaf(ov[k][q], wq, Os);
-                    }
-                }
-                xr[k] = float_to_bits<BF16>(Os);
-            }
+            for (int k = 0; k < KM; ++k) xr[k] = merge_bits<BF16, NS>(ov[k], cw, k, all_live);
 #pragma unroll
             for (int k = KM; k < KR; ++k) xr[k] = 0u;
         };
@@ -329,8 +298,8 @@ __global__ __launch_bounds__(WAVES * 64) void sparse_gemv_kernel(const Params p)
         for (int k = 0; k < KR; ++k) {
             const int m = (chunk_of(k) << 6) + lane;
             const float gt = bits_to_float(gb[k], BF16);
-            const float sl = p.in.gate_act ? gt : bits_to_float(float_to_bits<BF16>(gt / (1.0f + expf(-gt))), BF16);
-            xr[k] = (m < Z) ? (uint32_t)float_to_bits<BF16>(sl * bits_to_float(ub[k], BF16)) : 0u;
+            const float sl = p.in.gate_act ? gt : silu16<BF16>(gt);
+            xr[k] = (m < Z) ? (uint32_t)mul_bits<BF16>(sl, ub[k]) : 0u;
         }
     } else {
 #pragma unroll
@@ -675,10 +644,9 @@ __global__ __launch_bounds__(WAVES * 64) void sparse_gemv_kernel(const Params p)
                     gs = (gs - bias) * bits_to_float(scb, BF16);
                     us = (us - bias2) * bits_to_float(scb2, BF16);
                 }
-                const float g16 = bits_to_float(float_to_bits<BF16>(gs), BF16);
-                const float u16 = bits_to_float(float_to_bits<BF16>(us), BF16);
-                const float sl = bits_to_float(float_to_bits<BF16>(g16 / (1.0f + expf(-g16))), BF16);
-                hb = float_to_bits<BF16>(sl * u16);
+                const float g16 = round16<BF16>(gs);
+                const float u16 = round16<BF16>(us);
+                hb = silu_mul_bits<BF16>(g16, u16);
                 reinterpret_cast<uint16_t*>(sg.y)[c] = (uint16_t)hb;
                 const float hv = bits_to_float(hb, BF16);
                 kp = keep_rule(hv, p.mask_tau) || (hv != hv);

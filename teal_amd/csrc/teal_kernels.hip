@@ -12,7 +12,7 @@
 //   kernels/sparse_gemv.py:87-142   splitk_sparse_gemv (host wrapper, autotune, grid)  -> plan_gemv + run_gemv
 //   kernels/sparse_gemv.py:196-237  qkv_gemv                                           -> teal_sparse_qkv_gemv*
 //   kernels/sparse_gemv.py:8-12     init_to_zero("Y") pre-hook memset                  -> gone
-#include "teal_common.h"
+#include "teal_producers.h"
 #include "teal_gemv_plan.h"
 
 #include <stdlib.h>
@@ -93,11 +93,9 @@ __global__ __launch_bounds__(256) void gateup_silu_epilogue_kernel(const Params 
         g += p.ws[(size_t)k * p.ws_ld + n];
         u += p.ws[(size_t)k * p.ws_ld + N + n];
     }
-    const float g16 = bits_to_float(float_to_bits<BF16>(g), BF16);
-    const float u16 = bits_to_float(float_to_bits<BF16>(u), BF16);
-    const float sl = g16 / (1.0f + expf(-g16));
-    const float sl16 = bits_to_float(float_to_bits<BF16>(sl), BF16);
-    reinterpret_cast<uint16_t*>(h)[n] = float_to_bits<BF16>(sl16 * u16);
+    const float g16 = round16<BF16>(g);
+    const float u16 = round16<BF16>(u);
+    reinterpret_cast<uint16_t*>(h)[n] = silu_mul_bits<BF16>(g16, u16);
 }
 
 // Standalone compaction (one workgroup): ascending kept indices + count to global memory.

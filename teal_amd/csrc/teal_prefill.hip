@@ -26,18 +26,6 @@ namespace teal {
 
 constexpr int kRowsMax = 16;  // most tokens a pass takes; a feature's row holds rows_for(T) of them
 
-// 1 / rms per token from the per-workgroup sums of squares sumsq [nwg][KR] (lane = producing workgroup, nwg <= 64; the total in
-// workgroup order)
-template <int KR>
-__device__ __forceinline__ void rstd_rows(const float* __restrict__ sumsq, const int nwg, const int lane, const int Z, const float eps,
-                                          float (&rstd)[KR]) {
-    f32x4 pw[KR / 4];
-#pragma unroll
-    for (int w = 0; w < KR / 4; ++w) pw[w] = lane < nwg ? *reinterpret_cast<const f32x4*>(sumsq + (size_t)lane * KR + 4 * w) : (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < KR; ++s) rstd[s] = rsqrtf(wave_sum_f(pw[s >> 2][s & 3]) / (float)Z + eps);
-}
-
 // ------------------------------------------------------------------------------------------------
 // slabs[slice][n][8] (fp32) = sum over the slice's rows m of W^T[m][n] * x[token][m], for up to 2 NP tokens.
 //   xt     [Z][8] 16-bit: xt[m][s] = activation m of token s
@@ -119,8 +107,8 @@ __global__ __launch_bounds__(1024) void prefill_gemm_kernel(const SlabProd pr, c
                 load_row<BF16, KR>(xt + (size_t)m * KR, x);
 #pragma unroll
                 for (int s_ = 0; s_ < KR; ++s_) {
-                    const float xn = bits_to_float(float_to_bits<BF16>(x[s_] * rstd[s_]), BF16);
-                    x[s_] = s_ < pr.rows ? bits_to_float(float_to_bits<BF16>(xn * nw), BF16) : 0.0f;
+                    const float xn = norm_scale<BF16>(x[s_], rstd[s_]);
+                    x[s_] = s_ < pr.rows ? bits_to_float(mul_bits<BF16>(xn, nw), BF16) : 0.0f;
                 }
                 store_row<BF16, KR>(dst, x);
             } else {  // x = round(round(silu(round(gate))) * round(up))  (gpt-fast/model.py:258-259)
@@ -129,8 +117,8 @@ __global__ __launch_bounds__(1024) void prefill_gemm_kernel(const SlabProd pr, c
                 rounded_row<BF16, KR>(pr.gu, pr.gu_split, (size_t)2 * Z, (size_t)Z + m, uv);
 #pragma unroll
                 for (int s_ = 0; s_ < KR; ++s_) {
-                    const float sl = bits_to_float(float_to_bits<BF16>(gv[s_] / (1.0f + expf(-gv[s_]))), BF16);
-                    x[s_] = s_ < pr.rows ? bits_to_float(float_to_bits<BF16>(sl * uv[s_]), BF16) : 0.0f;
+                    const float sl = silu16<BF16>(gv[s_]);
+                    x[s_] = s_ < pr.rows ? bits_to_float(mul_bits<BF16>(sl, uv[s_]), BF16) : 0.0f;
                 }
                 store_row<BF16, KR>(dst, x);
             }
@@ -234,7 +222,7 @@ __global__ __launch_bounds__(256) void prefill_resid_kernel(const uint16_t* __re
             float y[KR];
             rounded_row<BF16, KR>(slabs, split, (size_t)dim, (size_t)col, y);
 #pragma unroll
-            for (int s = 0; s < KR; ++s) h[s] = bits_to_float(float_to_bits<BF16>(h[s] + y[s]), BF16);
+            for (int s = 0; s < KR; ++s) h[s] = round16<BF16>(h[s] + y[s]);  // (y is rounded: resid_add's second half)
         }
 #pragma unroll
         for (int s = 0; s < KR; ++s) h[s] = s < T ? h[s] : 0.0f;
@@ -263,8 +251,8 @@ __global__ __launch_bounds__(256) void prefill_norm_kernel(const uint16_t* __res
     load_row<BF16, KR>(ht + (size_t)col * KR, x);
 #pragma unroll
     for (int s = 0; s < KR; ++s) {
-        const float xn = bits_to_float(float_to_bits<BF16>(x[s] * rstd[s]), BF16);
-        x[s] = s < T ? bits_to_float(float_to_bits<BF16>(xn * nw), BF16) : 0.0f;
+        const float xn = norm_scale<BF16>(x[s], rstd[s]);
+        x[s] = s < T ? bits_to_float(mul_bits<BF16>(xn, nw), BF16) : 0.0f;
     }
     if (xt_out) store_row<BF16, KR>(xt_out + (size_t)col * KR, x);
     if (x_last) {

@@ -7,14 +7,13 @@
 // slabs in slice order and rounds once (slab_column / rounded_row): what a projection's 16-bit output tensor holds.  What a GEMM
 // builds its activations from while staging is a SlabProd, filled from the C ABI's teal_prefill_in_t by slab_prod_fill.
 #pragma once
-#include "teal_common.h"
+#include "teal_producers.h"
 
 #include <limits.h>
 
 namespace teal {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kSlabMaxSplit = 16;  // most slices (slabs) of a GEMM launch
 constexpr int rows_for(const int T) { return T <= 8 ? 8 : 16; }
 
@@ -71,6 +70,18 @@ inline int slab_gemm_split(const int num_cu, const int tiles, const int Z, const
         if (batches < best) { best = batches; split = c; }
     }
     return split;
+}
+
+// 1 / rms per token from the per-workgroup sums of squares sumsq [nwg][KR] (lane = producing workgroup, nwg <= 64; the total in
+// workgroup order)
+template <int KR>
+__device__ __forceinline__ void rstd_rows(const float* __restrict__ sumsq, const int nwg, const int lane, const int Z, const float eps,
+                                          float (&rstd)[KR]) {
+    f32x4 pw[KR / 4];
+#pragma unroll
+    for (int w = 0; w < KR / 4; ++w) pw[w] = lane < nwg ? *reinterpret_cast<const f32x4*>(sumsq + (size_t)lane * KR + 4 * w) : (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < KR; ++s) rstd[s] = rsqrtf(wave_sum_f(pw[s >> 2][s & 3]) / (float)Z + eps);
 }
 
 // sum of `split` slabs [slice][n_total][KR] of column `col` in slice order, rounded once to the activation dtype
