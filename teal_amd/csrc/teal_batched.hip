@@ -15,7 +15,7 @@
 //                             dimension), then batched_merge_kernel.
 //
 // Rounding points are the module path's (16-bit projection outputs, RoPE, attention output); sums are fp32.
-#include "teal_slab.h"
+#include "teal_chunked_attention.h"
 
 namespace teal {
 namespace {
@@ -25,9 +25,7 @@ constexpr int kBPhaseRows = 2048;      // rows a workgroup stages per phase (128
 constexpr int kBChunks = kBPhaseRows / 64;
 constexpr int kBCountStride = 9;       // counts[slice][segment][9]: kept per sequence (0 .. 7), union (8)
 constexpr int kBTauOff = (kBPhaseRows * 28 + (2 * kBChunks + 1 + 16 * 3 * kBCountStride) * 4 + 15) & ~15;  // LDS: the parked thresholds
-constexpr int kBAttnChunk = 32;        // context rows a workgroup stages per round
 constexpr int kBAttnMaxQ = 16;         // query heads of one KV head per workgroup
-constexpr int kBAttnMaxSplit = 64;
 
 struct BSegs {
     int nseg;
@@ -335,11 +333,10 @@ __global__ __launch_bounds__(256) void batched_round_rows_kernel(const float* __
 }
 
 // ------------------------------------------------------------------------------------------------
-// Attention of B single-token queries, sequence b at position p_b = clamp(pos[b], 0, max_seq - 1) against ITS cache rows 0 .. p_b.
-// Grid (nsplit, n_kv, groups * B): a workgroup serves hq query heads of one KV head of one sequence.  The new row (q of the hq
-// heads, k and v of the KV head) is rebuilt from the wqkv slabs (slot b, rounded) with RoPE at p_b (rounded) by every workgroup
-// that needs it and read from LDS; split 0 of group 0 stores it to the cache for LATER launches.  Context rows in chunks of 32,
-// chunk c to split c mod nsplit; each workgroup leaves {m, l, o[hd]} per (head, sequence), merged in split order.
+// Attention of B single-token queries, sequence b at position p_b = clamp(pos[b], 0, max_seq - 1) against ITS cache rows 0 .. p_b:
+// the chunked split-KV body (teal_chunked_attention.h) at T = 1 with the sequence as a grid dimension.  Grid (nsplit, n_kv,
+// groups * B): a workgroup serves hq query heads of one KV head of one sequence; its one new row is slot b of the wqkv slabs, its
+// caches are sequence b's [n_kv][max_seq][hd], its partials are row (h * B + b).
 // ------------------------------------------------------------------------------------------------
 // SLOTS: a workgroup of a slot whose `active` bit is clear exits before anything else (no cache row, no partials).
 template <bool BF16, int HD, bool SLOTS>
@@ -349,168 +346,20 @@ __global__ __launch_bounds__(256) void batched_attention_kernel(const float* __r
                                                                 float* __restrict__ partials, const int B, const int n_head,
                                                                 const int n_kv, const int hq, const int groups, const int max_seq,
                                                                 const float scale, const int* __restrict__ active) {
-    constexpr int C = kBAttnChunk, NT = 256, OJ = (kBAttnMaxQ * HD + NT - 1) / NT, QSTEP = NT / HD;
-    __shared__ float qs[kBAttnMaxQ][HD + 1];
-    __shared__ float kn[HD], vn[HD];
-    __shared__ float ks[C][HD + 1];
-    __shared__ float vs[C][HD];
-    __shared__ float sc[kBAttnMaxQ][C + 1];
-    __shared__ float mrow[kBAttnMaxQ], lrow[kBAttnMaxQ], alph[kBAttnMaxQ];
-    const int tid = threadIdx.x, sp = blockIdx.x, nsplit = gridDim.x, kvh = blockIdx.y;
     const int b = blockIdx.z / groups, grp = blockIdx.z % groups;
     if constexpr (SLOTS) {
         if (!((active[0] >> b) & 1)) return;  // workgroup-uniform
     }
-    const int rep = n_head / n_kv, h0 = kvh * rep + grp * hq, NQ = hq;
-    const int p = min(max(pos_ptr[b], 0), max_seq - 1);  // (a position past the cache is clamped into it)
-    const int ctx = p + 1;
-    const size_t nq = (size_t)n_head * HD, nkv = (size_t)n_kv * HD, ntot = nq + 2 * nkv;
     const size_t seq_off = (size_t)b * n_kv * max_seq * HD;
-
-    const int ncols = (hq + 2) * HD;
-    for (int c = tid; c < ncols; c += NT) {
-        const int part = c < hq * HD ? 0 : (c < (hq + 1) * HD ? 1 : 2);
-        const int d = part == 0 ? c % HD : c - (hq + part - 1) * HD;
-        const size_t col = part == 0 ? (size_t)h0 * HD + c : (part == 1 ? nq : nq + nkv) + (size_t)kvh * HD + d;
-        float a = 0.0f;
-        for (int s = 0; s < split; ++s) a += slabs[((size_t)s * ntot + col) * 8 + b];
-        const float r = bits_to_float(float_to_bits<BF16>(a), BF16);
-        if (part == 0) qs[c / HD][d] = r;
-        else if (part == 1) kn[d] = r;
-        else vn[d] = r;
-    }
-    if (tid < kBAttnMaxQ) { mrow[tid] = -INFINITY; lrow[tid] = 0.0f; }
-    __syncthreads();
-    for (int e = tid; e < (NQ + 1) * (HD / 2); e += NT) {  // one (even, odd) pair per thread
-        const int row = e / (HD / 2), i = e % (HD / 2);
-        float* x = row < NQ ? &qs[row][0] : &kn[0];
-        const uint32_t cs = *reinterpret_cast<const uint32_t*>(rope + ((size_t)p * (HD / 2) + i) * 2);
-        const float c = bits_to_float(cs & 0xFFFFu, BF16), sn = bits_to_float(cs >> 16, BF16);
-        const float x0 = x[2 * i], x1 = x[2 * i + 1];
-        x[2 * i] = bits_to_float(float_to_bits<BF16>(rope_even(x0, x1, c, sn)), BF16);
-        x[2 * i + 1] = bits_to_float(float_to_bits<BF16>(rope_odd(x0, x1, c, sn)), BF16);
-    }
-    __syncthreads();
-    uint16_t* kc_b = k_cache + seq_off + (size_t)kvh * max_seq * HD;
-    uint16_t* vc_b = v_cache + seq_off + (size_t)kvh * max_seq * HD;
-    if (sp == 0 && grp == 0) {  // one writer per (sequence, KV head): row p <= max_seq - 1
-        for (int d = tid; d < HD; d += NT) {
-            kc_b[(size_t)p * HD + d] = float_to_bits<BF16>(kn[d]);
-            vc_b[(size_t)p * HD + d] = float_to_bits<BF16>(vn[d]);
-        }
-    }
-
-    const int d_own = tid % HD;
-    float o[OJ];
-#pragma unroll
-    for (int j = 0; j < OJ; ++j) o[j] = 0.0f;
-    const int nchunks = (ctx + C - 1) / C;
-    for (int ch = sp; ch < nchunks; ch += nsplit) {
-        const int r0 = ch * C;
-        __syncthreads();  // the previous chunk's ks / vs / sc are consumed
-        for (int e = tid; e < C * (HD / 8); e += NT) {
-            const int rr = e / (HD / 8), seg = e % (HD / 8), r = r0 + rr;
-            float kf[8], vf[8];
-            if (r < p) {  // cached rows (never the row this launch writes)
-                const u32x4 kw = *reinterpret_cast<const u32x4*>(kc_b + (size_t)r * HD + seg * 8);
-                const u32x4 vw = *reinterpret_cast<const u32x4*>(vc_b + (size_t)r * HD + seg * 8);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    kf[2 * j] = bits_to_float(kw[j] & 0xFFFFu, BF16); kf[2 * j + 1] = bits_to_float(kw[j] >> 16, BF16);
-                    vf[2 * j] = bits_to_float(vw[j] & 0xFFFFu, BF16); vf[2 * j + 1] = bits_to_float(vw[j] >> 16, BF16);
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    kf[j] = r == p ? kn[seg * 8 + j] : 0.0f;
-                    vf[j] = r == p ? vn[seg * 8 + j] : 0.0f;
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { ks[rr][seg * 8 + j] = kf[j]; vs[rr][seg * 8 + j] = vf[j]; }
-        }
-        __syncthreads();
-        for (int pq = tid; pq < NQ * C; pq += NT) {
-            const int qi = pq / C, rr = pq % C, r = r0 + rr;
-            float s = -INFINITY;
-            if (r <= p) {
-                float a = 0.0f;
-#pragma unroll 16
-                for (int j = 0; j < HD; ++j) a = fmaf(qs[qi][j], ks[rr][j], a);
-                s = bits_to_float(float_to_bits<BF16>(a * scale), BF16);
-            }
-            sc[qi][rr] = s;
-        }
-        __syncthreads();
-        if (tid < NQ) {
-            const int qi = tid;
-            float mx = mrow[qi];
-            for (int rr = 0; rr < C; ++rr) mx = fmaxf(mx, sc[qi][rr]);
-            float a = 1.0f, l = lrow[qi];
-            if (mx != -INFINITY) {
-                a = mrow[qi] == -INFINITY ? 0.0f : expf(mrow[qi] - mx);
-                l *= a;
-                for (int rr = 0; rr < C; ++rr) {
-                    const float e = sc[qi][rr] == -INFINITY ? 0.0f : expf(sc[qi][rr] - mx);
-                    sc[qi][rr] = e;
-                    l += e;
-                }
-                mrow[qi] = mx;
-            } else {
-                for (int rr = 0; rr < C; ++rr) sc[qi][rr] = 0.0f;
-            }
-            lrow[qi] = l;
-            alph[qi] = a;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < OJ; ++j) {
-            const int qi = tid / HD + j * QSTEP;
-            if (qi < NQ) {
-                float acc = o[j] * alph[qi];
-#pragma unroll 8
-                for (int rr = 0; rr < C; ++rr) acc = fmaf(sc[qi][rr], vs[rr][d_own], acc);
-                o[j] = acc;
-            }
-        }
-    }
-    __syncthreads();
-    // partials[((h * B + b) * nsplit + sp) * (HD + 2)] = {m, l, o[HD]}
-#pragma unroll
-    for (int j = 0; j < OJ; ++j) {
-        const int qi = tid / HD + j * QSTEP;
-        if (qi < NQ) {
-            const int h = h0 + qi;
-            float* q = partials + (((size_t)h * B + b) * nsplit + sp) * (HD + 2);
-            q[2 + d_own] = o[j];
-            if (d_own == 0) { q[0] = mrow[qi]; q[1] = lrow[qi]; }
-        }
-    }
+    chunked_attention_body<BF16, HD, kBAttnMaxQ, kBatchMax, 1>(slabs, split, pos_ptr[b], rope, k_cache + seq_off, v_cache + seq_off, partials, 1,
+                                                               b, B, n_head, n_kv, hq, grp, max_seq, scale);
 }
 
-// yt[(h * hd + d) * 8 + b] = round(sum_s o_s e^(m_s - M) / sum_s l_s e^(m_s - M)), splits in order; slots b >= B are zero
-// (SLOTS: so are the slots whose `active` bit is clear)
+// slots b >= B are zero (SLOTS: so are the slots whose `active` bit is clear)
 template <bool BF16, bool SLOTS>
 __global__ __launch_bounds__(128) void batched_merge_kernel(const float* __restrict__ partials, uint16_t* __restrict__ yt, const int B,
                                                             const int hd, const int nsplit, const int* __restrict__ active) {
-    const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
-    if (d >= hd) return;
-    uint16_t* y = yt + ((size_t)h * hd + d) * 8 + b;
-    if (b >= B || (SLOTS && !((active[0] >> b) & 1))) { *y = 0; return; }
-    const float* p = partials + ((size_t)h * B + b) * nsplit * (hd + 2);
-    float M = -INFINITY;
-    for (int s = 0; s < nsplit; ++s) M = fmaxf(M, p[(size_t)s * (hd + 2)]);
-    float L = 0.0f, O = 0.0f;
-    for (int s = 0; s < nsplit; ++s) {
-        const float* q = p + (size_t)s * (hd + 2);
-        const float l = q[1];
-        if (l > 0.0f) {
-            const float f = expf(q[0] - M);
-            L = fmaf(l, f, L);
-            O = fmaf(q[2 + d], f, O);
-        }
-    }
-    *y = float_to_bits<BF16>(O / L);
+    chunked_merge_body<BF16, kBatchMax, SLOTS>(partials, yt, B, hd, nsplit, active);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -642,7 +491,7 @@ int teal_batched_round_rows(const float* slabs, int split, int N, int B, void* y
 }
 
 size_t teal_batched_decode_attention_ws_bytes(int B, int n_head, int head_dim) {
-    return (size_t)n_head * (B < 1 ? 1 : B) * kBAttnMaxSplit * (head_dim + 2) * sizeof(float);
+    return chunked_attention_ws_bytes(n_head, B < 1 ? 1 : B, kAttnMaxSplit, head_dim);
 }
 
 }  // extern "C"
@@ -652,25 +501,14 @@ namespace {
 int batched_attention_launch(const float* qkv_slabs, int split, const void* rope, const int32_t* pos, const int32_t* active, void* k_cache,
                              void* v_cache, void* yt, float* partials, size_t partials_bytes, int B, int n_head, int n_kv_head, int head_dim,
                              int max_seq, int dtype, void* stream) {
-    if (!qkv_slabs || !rope || !pos || !k_cache || !v_cache || !yt || !partials || split < 1 || split > kSlabMaxSplit) return TEAL_ERR_ARG;
-    if (dtype != TEAL_F16 && dtype != TEAL_BF16) return TEAL_ERR_DTYPE;
-    if ((head_dim != 64 && head_dim != 128) || n_head <= 0 || n_kv_head <= 0 || n_head % n_kv_head || B < 1 || B > kBatchMax || max_seq < 1)
-        return TEAL_ERR_SHAPE;
-    if (!aligned16(qkv_slabs) || !aligned16(k_cache) || !aligned16(v_cache)) return TEAL_ERR_ALIGN;
+    const int rc = chunked_attention_check(qkv_slabs, split, rope, pos, k_cache, v_cache, yt, partials, B, kBatchMax, n_head, n_kv_head,
+                                           head_dim, max_seq, 1, dtype);
+    if (rc != TEAL_OK) return rc;
     DeviceCtx* ctx = device_ctx();
     if (!ctx) return TEAL_ERR_NO_DEVICE;
-    const int rep = n_head / n_kv_head;
-    int hq = 1;  // the most query heads of a group that fit a workgroup and divide the group
-    for (int c = 1; c <= rep; ++c)
-        if (rep % c == 0 && c <= kBAttnMaxQ) hq = c;
-    const int groups = rep / hq;
-    // about two workgroups per CU at the longest context the cache holds; never more splits than chunks
-    const int chunks = (max_seq + kBAttnChunk - 1) / kBAttnChunk;
-    const int wg = n_kv_head * groups * B;
-    int nsplit = (2 * ctx->num_cu + wg - 1) / wg;
-    nsplit = nsplit < 1 ? 1 : (nsplit > kBAttnMaxSplit ? kBAttnMaxSplit : nsplit);
-    if (nsplit > chunks) nsplit = chunks;
-    if (partials_bytes < (size_t)n_head * B * nsplit * (head_dim + 2) * sizeof(float)) return TEAL_ERR_WORKSPACE;
+    const ChunkedAttnPlan pl = chunked_attention_plan(ctx->num_cu, n_head / n_kv_head, n_kv_head, 1, B, max_seq, kBAttnMaxQ);
+    const int hq = pl.hq, groups = pl.groups, nsplit = pl.nsplit;
+    if (partials_bytes < chunked_attention_ws_bytes(n_head, B, nsplit, head_dim)) return TEAL_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const float scale = 1.0f / sqrtf((float)head_dim);
     const dim3 grid(nsplit, n_kv_head, groups * B);

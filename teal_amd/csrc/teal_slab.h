@@ -6,6 +6,8 @@
 // GEMM deals its 16-row groups to `split` slices (slab_gemm_split) and leaves one slab per slice; every consumer sums a column's
 // slabs in slice order and rounds once (slab_column / rounded_row): what a projection's 16-bit output tensor holds.  What a GEMM
 // builds its activations from while staging is a SlabProd, filled from the C ABI's teal_prefill_in_t by slab_prod_fill.
+// The attention of the two passes that attend a cache (verify, batched) reads its new rows from the wqkv slabs in this layout:
+// teal_chunked_attention.h, which includes this header.
 #pragma once
 #include "teal_producers.h"
 

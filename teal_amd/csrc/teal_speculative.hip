@@ -2,204 +2,37 @@
 //
 // One round: k draft steps (the fused decode step, TEAL-sparse), then ONE dense pass over the k + 1 tokens [x0, d1 .. dk] at
 // positions p .. p+k through the prompt pass's GEMMs (teal_prefill.hip; the slab layout and its helpers: teal_slab.h), with
-//   verify_attention_kernel + verify_merge_kernel   attention of the k + 1 rows against the whole cache (split-KV)
+//   verify_attention_kernel + verify_merge_kernel   attention of the k + 1 rows against the whole cache (split-KV; the body the
+//                                                   batched step shares: teal_chunked_attention.h)
 //   spec_round_logits_kernel                        the lm_head slabs of every row, summed and rounded once (the module's logits)
 //   spec_row_stats_kernel                           per row: max, top-k pivot, softmax normaliser
 //   spec_decide_kernel                              the reference's accept / reject rule (gpt-fast/generate.py:123-146)
 // Everything that decides the round stays on the device: the accepted count, the emitted tokens, the next round's position
 // and input token.  The draw convention is in include/teal_hip.h (teal_spec_accept).
-#include "teal_slab.h"
+#include "teal_chunked_attention.h"
 
 namespace teal {
 
 constexpr int kVerifyMaxT = 16;     // the prompt pass's most tokens per pass
-constexpr int kVerifyChunk = 32;    // context rows a workgroup stages per round
 constexpr int kVerifyMaxQ = 64;     // query rows (heads of a group x tokens) per workgroup
-constexpr int kVerifyMaxSplit = 64;
 
-// ------------------------------------------------------------------------------------------------
-// Attention of T <= 16 new tokens at positions p0 .. p0+T-1 (p0 read from the device) against cache rows 0 .. p0+t.
-// Grid (nsplit, n_kv, rep / hq): a workgroup serves the hq query heads of one group of its KV head for ALL T tokens
-// (hq * T <= 64 query rows), so every K / V row it loads is used hq * T times.  Context rows are dealt in chunks of 32,
-// chunk c to split c mod nsplit.  The T new rows are rebuilt by every workgroup from the wqkv slabs (RoPE at p0 + t, the
-// module path's rounding points) and read from LDS: the cache stores of rows p0 .. p0+T-1 (split 0, group 0 only) are for
-// LATER launches — nothing written in this launch is read back by it.  Each workgroup leaves an un-normalised partial
-// {m, l, o[hd]} per (query head, token); verify_merge_kernel rescales and sums them in split order.
-// ------------------------------------------------------------------------------------------------
+// Attention of T <= 16 new tokens at positions p0 .. p0+T-1 (p0 read from the device) against cache rows 0 .. p0+t: the chunked
+// split-KV body (teal_chunked_attention.h) with the KR token slots of the slabs as its new rows.  Grid (nsplit, n_kv, rep / hq).
 template <bool BF16, int HD, int KR>
 __global__ __launch_bounds__(256) void verify_attention_kernel(const float* __restrict__ slabs, const int split,
                                                                const int* __restrict__ pos_ptr, const uint16_t* __restrict__ rope,
                                                                uint16_t* __restrict__ k_cache, uint16_t* __restrict__ v_cache,
                                                                float* __restrict__ partials, const int T, const int n_head,
                                                                const int n_kv, const int hq, const int max_seq, const float scale) {
-    constexpr int C = kVerifyChunk, NT = 256, OJ = kVerifyMaxQ * HD / NT, QSTEP = NT / HD;
-    __shared__ float qs[kVerifyMaxQ][HD + 1];
-    __shared__ float kn[KR][HD + 1];
-    __shared__ float vn[KR][HD];
-    __shared__ float ks[C][HD + 1];
-    __shared__ float vs[C][HD];
-    __shared__ float sc[kVerifyMaxQ][C + 1];
-    __shared__ float mrow[kVerifyMaxQ], lrow[kVerifyMaxQ], alph[kVerifyMaxQ];
-    const int tid = threadIdx.x, sp = blockIdx.x, nsplit = gridDim.x, kvh = blockIdx.y;
-    const int rep = n_head / n_kv, h0 = kvh * rep + blockIdx.z * hq, NQ = hq * T;
-    // (a caller past the cache is clamped into it: the output is then meaningless, the memory stays intact)
-    const int p0 = min(max(pos_ptr[0], 0), max_seq - T);
-    const int ctx = p0 + T;
-    const size_t nq = (size_t)n_head * HD, nkv = (size_t)n_kv * HD, ntot = nq + 2 * nkv;
-
-    // ---- the new rows: q of the group's heads, k and v of the KV head, from the slabs (rounded), then RoPE (rounded)
-    const int ncols = (hq + 2) * HD;
-    for (int c = tid; c < ncols; c += NT) {
-        const int part = c < hq * HD ? 0 : (c < (hq + 1) * HD ? 1 : 2);
-        const int d = part == 0 ? c % HD : c - (hq + part - 1) * HD;
-        const size_t col = part == 0 ? (size_t)h0 * HD + c : (part == 1 ? nq : nq + nkv) + (size_t)kvh * HD + d;
-        float r[KR];
-        slab_column<BF16, KR>(slabs, split, ntot, col, r);
-#pragma unroll
-        for (int t = 0; t < KR; ++t) {
-            if (t < T) {
-                if (part == 0) qs[(c / HD) * T + t][d] = r[t];
-                else if (part == 1) kn[t][d] = r[t];
-                else vn[t][d] = r[t];
-            }
-        }
-    }
-    if (tid < kVerifyMaxQ) { mrow[tid] = -INFINITY; lrow[tid] = 0.0f; }
-    __syncthreads();
-    for (int e = tid; e < (NQ + T) * (HD / 2); e += NT) {  // one (even, odd) pair per thread
-        const int row = e / (HD / 2), i = e % (HD / 2);
-        const int t = row < NQ ? row % T : row - NQ;
-        float* x = row < NQ ? &qs[row][0] : &kn[t][0];
-        const uint32_t cs = *reinterpret_cast<const uint32_t*>(rope + ((size_t)(p0 + t) * (HD / 2) + i) * 2);
-        const float c = bits_to_float(cs & 0xFFFFu, BF16), sn = bits_to_float(cs >> 16, BF16);
-        const float x0 = x[2 * i], x1 = x[2 * i + 1];
-        x[2 * i] = bits_to_float(float_to_bits<BF16>(rope_even(x0, x1, c, sn)), BF16);
-        x[2 * i + 1] = bits_to_float(float_to_bits<BF16>(rope_odd(x0, x1, c, sn)), BF16);
-    }
-    __syncthreads();
-    if (sp == 0 && blockIdx.z == 0) {  // one writer per KV head; rows p0 .. p0+T-1 <= max_seq - 1
-        for (int e = tid; e < T * HD; e += NT) {
-            const int t = e / HD, d = e % HD;
-            const size_t at = ((size_t)kvh * max_seq + p0 + t) * HD + d;
-            k_cache[at] = float_to_bits<BF16>(kn[t][d]);
-            v_cache[at] = float_to_bits<BF16>(vn[t][d]);
-        }
-    }
-
-    // ---- this split's chunks of the context: scores, online softmax, o += p V
-    const int d_own = tid % HD;
-    float o[OJ];
-#pragma unroll
-    for (int j = 0; j < OJ; ++j) o[j] = 0.0f;
-    const int nchunks = (ctx + C - 1) / C;
-    const uint16_t* kc = k_cache + (size_t)kvh * max_seq * HD;
-    const uint16_t* vc = v_cache + (size_t)kvh * max_seq * HD;
-    for (int ch = sp; ch < nchunks; ch += nsplit) {
-        const int r0 = ch * C;
-        __syncthreads();  // the previous chunk's ks / vs / sc are consumed
-        for (int e = tid; e < C * (HD / 8); e += NT) {
-            const int rr = e / (HD / 8), seg = e % (HD / 8), r = r0 + rr;
-            float kf[8], vf[8];
-            if (r < p0) {  // cached rows (never the rows this launch writes)
-                const u32x4 kw = *reinterpret_cast<const u32x4*>(kc + (size_t)r * HD + seg * 8);
-                const u32x4 vw = *reinterpret_cast<const u32x4*>(vc + (size_t)r * HD + seg * 8);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    kf[2 * j] = bits_to_float(kw[j] & 0xFFFFu, BF16); kf[2 * j + 1] = bits_to_float(kw[j] >> 16, BF16);
-                    vf[2 * j] = bits_to_float(vw[j] & 0xFFFFu, BF16); vf[2 * j + 1] = bits_to_float(vw[j] >> 16, BF16);
-                }
-            } else {
-                const int t = min(r - p0, T - 1);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    kf[j] = r < ctx ? kn[t][seg * 8 + j] : 0.0f;
-                    vf[j] = r < ctx ? vn[t][seg * 8 + j] : 0.0f;
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { ks[rr][seg * 8 + j] = kf[j]; vs[rr][seg * 8 + j] = vf[j]; }
-        }
-        __syncthreads();
-        for (int pq = tid; pq < NQ * C; pq += NT) {  // (query row, context row): causal — row r is visible to token t iff r <= p0 + t
-            const int qi = pq / C, rr = pq % C, r = r0 + rr, t = qi % T;
-            float s = -INFINITY;
-            if (r <= p0 + t) {
-                float a = 0.0f;
-#pragma unroll 16
-                for (int j = 0; j < HD; ++j) a = fmaf(qs[qi][j], ks[rr][j], a);
-                s = bits_to_float(float_to_bits<BF16>(a * scale), BF16);
-            }
-            sc[qi][rr] = s;
-        }
-        __syncthreads();
-        if (tid < NQ) {
-            const int qi = tid;
-            float mx = mrow[qi];
-            for (int rr = 0; rr < C; ++rr) mx = fmaxf(mx, sc[qi][rr]);
-            float a = 1.0f, l = lrow[qi];
-            if (mx != -INFINITY) {
-                a = mrow[qi] == -INFINITY ? 0.0f : expf(mrow[qi] - mx);
-                l *= a;
-                for (int rr = 0; rr < C; ++rr) {
-                    const float e = sc[qi][rr] == -INFINITY ? 0.0f : expf(sc[qi][rr] - mx);
-                    sc[qi][rr] = e;
-                    l += e;
-                }
-                mrow[qi] = mx;
-            } else {
-                for (int rr = 0; rr < C; ++rr) sc[qi][rr] = 0.0f;
-            }
-            lrow[qi] = l;
-            alph[qi] = a;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < OJ; ++j) {
-            const int qi = tid / HD + j * QSTEP;
-            if (qi < NQ) {
-                float acc = o[j] * alph[qi];
-#pragma unroll 8
-                for (int rr = 0; rr < C; ++rr) acc = fmaf(sc[qi][rr], vs[rr][d_own], acc);
-                o[j] = acc;
-            }
-        }
-    }
-    __syncthreads();
-    // partials[((h * T + t) * nsplit + sp) * (HD + 2)] = {m, l, o[HD]}
-#pragma unroll
-    for (int j = 0; j < OJ; ++j) {
-        const int qi = tid / HD + j * QSTEP;
-        if (qi < NQ) {
-            const int h = h0 + qi / T, t = qi % T;
-            float* p = partials + (((size_t)h * T + t) * nsplit + sp) * (HD + 2);
-            p[2 + d_own] = o[j];
-            if (d_own == 0) { p[0] = mrow[qi]; p[1] = lrow[qi]; }
-        }
-    }
+    chunked_attention_body<BF16, HD, kVerifyMaxQ, KR, KR>(slabs, split, pos_ptr[0], rope, k_cache, v_cache, partials, T, 0, T, n_head, n_kv,
+                                                          hq, blockIdx.z, max_seq, scale);
 }
 
-// yt[(h * HD + d) * KR + t] = round(sum_s o_s e^(m_s - M) / sum_s l_s e^(m_s - M)), splits in order; token slots >= T are zero
+// token slots >= T are zero
 template <bool BF16, int KR>
 __global__ __launch_bounds__(128) void verify_merge_kernel(const float* __restrict__ partials, uint16_t* __restrict__ yt, const int T,
                                                            const int hd, const int nsplit) {
-    const int h = blockIdx.x, t = blockIdx.y, d = threadIdx.x;
-    if (d >= hd) return;
-    uint16_t* y = yt + ((size_t)h * hd + d) * KR + t;
-    if (t >= T) { *y = 0; return; }
-    const float* p = partials + ((size_t)h * T + t) * nsplit * (hd + 2);
-    float M = -INFINITY;
-    for (int s = 0; s < nsplit; ++s) M = fmaxf(M, p[(size_t)s * (hd + 2)]);
-    float L = 0.0f, O = 0.0f;
-    for (int s = 0; s < nsplit; ++s) {
-        const float* q = p + (size_t)s * (hd + 2);
-        const float l = q[1];
-        if (l > 0.0f) {
-            const float f = expf(q[0] - M);
-            L = fmaf(l, f, L);
-            O = fmaf(q[2 + d], f, O);
-        }
-    }
-    *y = float_to_bits<BF16>(O / L);
+    chunked_merge_body<BF16, KR, false>(partials, yt, T, hd, nsplit, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -387,34 +220,23 @@ using namespace teal;
 extern "C" {
 
 size_t teal_verify_attention_ws_bytes(int T, int n_head, int head_dim) {
-    return (size_t)n_head * (T < 1 ? 1 : T) * kVerifyMaxSplit * (head_dim + 2) * sizeof(float);
+    return chunked_attention_ws_bytes(n_head, T < 1 ? 1 : T, kAttnMaxSplit, head_dim);
 }
 
 int teal_verify_attention(const float* qkv_slabs, int split, const void* rope, const int32_t* pos, void* k_cache, void* v_cache, void* yt,
                           float* partials, size_t partials_bytes, int T, int n_head, int n_kv_head, int head_dim, int max_seq, int dtype,
                           void* stream) {
-    if (!qkv_slabs || !rope || !pos || !k_cache || !v_cache || !yt || !partials || split < 1 || split > 16) return TEAL_ERR_ARG;
-    if (dtype != TEAL_F16 && dtype != TEAL_BF16) return TEAL_ERR_DTYPE;
-    if ((head_dim != 64 && head_dim != 128) || n_head <= 0 || n_kv_head <= 0 || n_head % n_kv_head || T < 1 || T > kVerifyMaxT ||
-        max_seq < T)
-        return TEAL_ERR_SHAPE;
-    if (!aligned16(qkv_slabs) || !aligned16(k_cache) || !aligned16(v_cache)) return TEAL_ERR_ALIGN;
+    const int rc = chunked_attention_check(qkv_slabs, split, rope, pos, k_cache, v_cache, yt, partials, T, kVerifyMaxT, n_head, n_kv_head,
+                                           head_dim, max_seq, T, dtype);
+    if (rc != TEAL_OK) return rc;
     DeviceCtx* ctx = device_ctx();
     if (!ctx) return TEAL_ERR_NO_DEVICE;
-    const int rep = n_head / n_kv_head;
-    int hq = 1;  // the most query heads of a group that fit 64 query rows and divide the group
-    for (int c = 1; c <= rep; ++c)
-        if (rep % c == 0 && c * T <= kVerifyMaxQ) hq = c;
-    const int groups = rep / hq;
-    // about two workgroups per CU at the longest context the cache holds; never more splits than chunks
-    const int chunks = (max_seq + kVerifyChunk - 1) / kVerifyChunk;
-    int nsplit = (2 * ctx->num_cu + n_kv_head * groups - 1) / (n_kv_head * groups);
-    nsplit = nsplit < 1 ? 1 : (nsplit > kVerifyMaxSplit ? kVerifyMaxSplit : nsplit);
-    if (nsplit > chunks) nsplit = chunks;
-    if (partials_bytes < (size_t)n_head * T * nsplit * (head_dim + 2) * sizeof(float)) return TEAL_ERR_WORKSPACE;
+    const ChunkedAttnPlan pl = chunked_attention_plan(ctx->num_cu, n_head / n_kv_head, n_kv_head, T, 1, max_seq, kVerifyMaxQ);
+    const int hq = pl.hq, nsplit = pl.nsplit;
+    if (partials_bytes < chunked_attention_ws_bytes(n_head, T, nsplit, head_dim)) return TEAL_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const float scale = 1.0f / sqrtf((float)head_dim);
-    const dim3 grid(nsplit, n_kv_head, groups);
+    const dim3 grid(nsplit, n_kv_head, pl.groups);
     auto* rp = reinterpret_cast<const uint16_t*>(rope);
     auto* kc = reinterpret_cast<uint16_t*>(k_cache);
     auto* vc = reinterpret_cast<uint16_t*>(v_cache);

@@ -289,8 +289,8 @@ def slabs_of(qkv, R, split=2):
     return s
 
 
-# ---- the shapes: the smallest that reach each code path (teal_attention.hip: STEP, PF, RD, kGqaMinSeq*; teal_speculative.hip:
-#      kVerifyChunk = 32) ----------------------------------------------------------------------------------------------------
+# ---- the shapes: the smallest that reach each code path (teal_attention.hip: STEP, PF, RD, kGqaMinSeq*; teal_chunked_attention.h:
+#      kAttnChunk = 32) ------------------------------------------------------------------------------------------------------
 #          (n_head, n_kv, hd, pos, S)
 SINGLE = ((4, 2, 64, 0, 64), (4, 2, 64, 255, 256),
           (8, 2, 128, 256, 512),                       # one row past the 256-row V prefetch
