@@ -731,6 +731,36 @@ int teal_constrain_logits(const void* logits, size_t logits_stride, int vocab, i
 int teal_kv_copy_rows(const void* src_table, const void* dst_table, int n_tensors, int n_heads, int rows, int row_bytes,
                       size_t src_head_stride, size_t dst_head_stride, void* stream);
 
+/* ---- fp8 KV cache of continuous batching, teal_amd/csrc/teal_kv8.hip ---------------------------------------------------
+ * A cached K or V row of one KV head is hd bytes of OCP e4m3fn codes and one fp32 scale word that holds an exact power of two; a
+ * cache is two tensors, codes [n_kv][max_seq][hd] uint8 and scales [n_kv][max_seq] fp32.  The rule, for a row x[0 .. hd) of 16-bit
+ * values widened exactly to fp32 (tests/kv8_rule.py restates it in integers):
+ *   a = max |x_d|;  e = 0 if a == 0, else the smallest integer with a * 2^-e <= 448, then clamped below at -100;  scale = 2^e;
+ *   code_d = RNE_e4m3fn(x_d * 2^-e): subnormals down to 2^-9, ties to even, the sign kept (-0 -> 0x80).  The product is exact in
+ *   fp32 wherever it does not underflow (and there the code is +-0 either way); |x_d * 2^-e| <= 448, so nothing saturates.
+ *   Dequantisation is float(code_d) * scale, exact in fp32.
+ * A row that holds NaN or Inf is outside the contract: its codes and scale are unspecified, and no byte outside the row is touched. */
+
+/* For every tensor t < n_tensors, head h < n_heads and row r < rows: the head_dim 16-bit values at src[t] + ((h * src_head_rows + r)
+ * * head_dim) elements become head_dim codes at code[t] + (h * dst_head_rows + r) * head_dim bytes and one scale word at scale[t] +
+ * (h * dst_head_rows + r) floats, by the rule above.  No other byte is written.  One launch covers all tensors (K and V of every
+ * layer: n_tensors = 2 L).  The three tables are DEVICE arrays of n_tensors 64-bit addresses (teal_kv_copy_rows' conventions: row 0 of
+ * head 0 of one tensor each, 16-byte aligned by the caller's contract, read on the device only — no host synchronisation).  rows == 0
+ * launches nothing.  TEAL_ERR_ARG: a null table, n_tensors / n_heads <= 0, rows < 0; TEAL_ERR_DTYPE; TEAL_ERR_SHAPE: head_dim not
+ * 64 / 128, rows above a head's rows on either side, n_tensors or n_heads above 65535; TEAL_ERR_ALIGN: a table off 8 bytes. */
+int teal_kv8_quantize_rows(const void* src_table, const void* code_table, const void* scale_table, int n_tensors, int n_heads, int head_dim,
+                           int rows, size_t src_head_rows, size_t dst_head_rows, int dtype, void* stream);
+/* teal_batched_decode_attention_slots on fp8 caches: k_codes / v_codes [B][n_kv][max_seq][hd] uint8 (16-byte aligned), k_scales /
+ * v_scales [B][n_kv][max_seq] fp32.  The same grid, plan, partials layout and merge launch; the kernel is the same chunked split-KV
+ * body with its cache format set.  Cached rows r < pos[b] enter as float(code) * scale; the new row is attended unquantised (the
+ * launch that makes a row sees it exactly, like the prompt pass) and its codes and scale are stored by the rule for later launches.
+ * So yt holds the words teal_batched_decode_attention_slots leaves on 16-bit caches that hold the dequantised values, whenever
+ * those are representable in the dtype.  An inactive slot writes nothing and its yt slot is zero.  TEAL_ERR_ARG also for null scales. */
+int teal_batched_decode_attention_slots_kv8(const float* qkv_slabs, int split, const void* rope, const int32_t* pos, const int32_t* active,
+                                            void* k_codes, void* v_codes, float* k_scales, float* v_scales, void* yt, float* partials,
+                                            size_t partials_bytes, int B, int n_head, int n_kv_head, int head_dim, int max_seq, int dtype,
+                                            void* stream);
+
 /* ---- benchmark comparator (scripts/benchmark_gemv.py only; not on the decode path) ----------- */
 
 /* The Deja Vu gather GEMV the reference's kernel benchmark plots next to TEAL's (scripts/benchmark_gemv.py:32-107,170-172),

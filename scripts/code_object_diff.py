@@ -117,8 +117,12 @@ def table(parent_lib: str, tree_lib: str, label: str, sources) -> list:
     rows = []
     with tempfile.TemporaryDirectory() as tmp:
         pa, tr = list(unit_texts(parent_lib, os.path.join(tmp, "parent"))), list(unit_texts(tree_lib, os.path.join(tmp, "tree")))
-    if not (len(pa) == len(tr) == len(sources)):
+    # (a tree may append translation units to SOURCES: the parent's units are compared, the new ones are listed as `new`)
+    if not (len(pa) <= len(tr) == len(sources)):
         raise SystemExit(f"{len(pa)} / {len(tr)} code objects for {len(sources)} translation units")
+    for src, t in zip(sources[len(pa):], tr[len(pa):]):
+        sha = hashlib.sha256("\n".join(_lines(t)).encode()).hexdigest()[:16]
+        rows.append(f"  {label:<12} {src:<30} {len(_lines(t)):>7} lines {len(_symbols(_lines(t))):>5} symbols  {'new':<9}  sha256 {sha}")
     for src, p, t in zip(sources, pa, tr):
         r = compare(p, t)
         sha = hashlib.sha256("\n".join(_lines(t)).encode()).hexdigest()[:16]

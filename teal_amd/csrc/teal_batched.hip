@@ -20,12 +20,10 @@
 namespace teal {
 namespace {
 
-constexpr int kBatchMax = 8;           // sequences per launch: one 16-byte word of 16-bit activations per feature
 constexpr int kBPhaseRows = 2048;      // rows a workgroup stages per phase (128 groups of 16)
 constexpr int kBChunks = kBPhaseRows / 64;
 constexpr int kBCountStride = 9;       // counts[slice][segment][9]: kept per sequence (0 .. 7), union (8)
 constexpr int kBTauOff = (kBPhaseRows * 28 + (2 * kBChunks + 1 + 16 * 3 * kBCountStride) * 4 + 15) & ~15;  // LDS: the parked thresholds
-constexpr int kBAttnMaxQ = 16;         // query heads of one KV head per workgroup
 
 struct BSegs {
     int nseg;

@@ -5,12 +5,15 @@
 // R = B: one kernel body, one merge body, one host-side plan and one argument check, each typed here once.  The two units keep
 // their __global__ wrappers (symbols, argument lists, launch bounds), the SLOTS early exit and their dispatch.
 #pragma once
+#include "teal_kv8.h"
 #include "teal_slab.h"
 
 namespace teal {
 
 constexpr int kAttnChunk = 32;     // context rows a workgroup stages per round
 constexpr int kAttnMaxSplit = 64;  // most splits of the context (partials per query row)
+constexpr int kBatchMax = 8;       // sequences per batched launch: one 16-byte word of 16-bit activations per feature
+constexpr int kBAttnMaxQ = 16;     // batched step: query heads of one KV head per workgroup
 
 // ------------------------------------------------------------------------------------------------
 // Attention of T new rows at positions p0 .. p0+T-1, p0 = clamp(pos, 0, max_seq - T), against the cache rows 0 .. p0+t of ONE
@@ -25,14 +28,20 @@ constexpr int kAttnMaxSplit = 64;  // most splits of the context (partials per q
 //   KR    token / sequence slots per slab column (teal_slab.h)
 //   NR    new K / V rows held in LDS.  NR = KR: the rows are slots 0 .. T-1 (slab_column).  NR = 1: T is 1 and the one row is
 //         slot `slot`; both forms add the slices in order from +0.
+//   KV8   the cache format (teal_kv8.h; NR = 1 only).  false: 16-bit rows.  true: k_cache / v_cache are [n_kv][max_seq][HD] e4m3fn
+//         codes and k_scales / v_scales the rows' [n_kv][max_seq] power-of-two scales.  Only the staging loop's load and the
+//         writer's store know: a cached row reaches ks / vs as float(code) * scale — exact — and the new row is attended from
+//         kn / vn unquantised, so everything after the staging loop is the 16-bit launch's on a cache of the dequantised values.
 // ------------------------------------------------------------------------------------------------
-template <bool BF16, int HD, int MAXQ, int KR, int NR>
+template <bool BF16, int HD, int MAXQ, int KR, int NR, bool KV8 = false>
 __device__ __forceinline__ void chunked_attention_body(const float* __restrict__ slabs, const int split, const int pos,
-                                                       const uint16_t* __restrict__ rope, uint16_t* __restrict__ k_cache,
-                                                       uint16_t* __restrict__ v_cache, float* __restrict__ partials, const int T_rows,
+                                                       const uint16_t* __restrict__ rope, kv_elem_t<KV8>* __restrict__ k_cache,
+                                                       kv_elem_t<KV8>* __restrict__ v_cache, float* __restrict__ partials, const int T_rows,
                                                        const int slot, const int R, const int n_head, const int n_kv, const int hq,
-                                                       const int grp, const int max_seq, const float scale) {
+                                                       const int grp, const int max_seq, const float scale,
+                                                       float* __restrict__ k_scales = nullptr, float* __restrict__ v_scales = nullptr) {
     constexpr bool ONE = NR == 1;
+    static_assert(ONE || !KV8, "the fp8 cache is the batched step's: one new row per launch");
     constexpr int C = kAttnChunk, NT = 256, OJ = (MAXQ * HD + NT - 1) / NT, QSTEP = NT / HD;
     __shared__ float qs[MAXQ][HD + 1];
     __shared__ float kn[NR][ONE ? HD : HD + 1];  // (a single row needs no padding against bank conflicts)
@@ -88,13 +97,27 @@ __device__ __forceinline__ void chunked_attention_body(const float* __restrict__
         x[2 * i + 1] = bits_to_float(float_to_bits<BF16>(rope_odd(x0, x1, c, sn)), BF16);
     }
     __syncthreads();
-    uint16_t* kc = k_cache + (size_t)kvh * max_seq * HD;
-    uint16_t* vc = v_cache + (size_t)kvh * max_seq * HD;
+    kv_elem_t<KV8>* kc = k_cache + (size_t)kvh * max_seq * HD;
+    kv_elem_t<KV8>* vc = v_cache + (size_t)kvh * max_seq * HD;
+    [[maybe_unused]] float* ksc = nullptr;
+    [[maybe_unused]] float* vsc = nullptr;
+    if constexpr (KV8) { ksc = k_scales + (size_t)kvh * max_seq; vsc = v_scales + (size_t)kvh * max_seq; }
     if (sp == 0 && grp == 0) {  // one writer per (sequence, KV head); rows p0 .. p0+T-1 <= max_seq - 1
-        for (int e = tid; e < T * HD; e += NT) {
-            const int t = e / HD, d = e % HD;
-            kc[(size_t)(p0 + t) * HD + d] = float_to_bits<BF16>(kn[t][d]);
-            vc[(size_t)(p0 + t) * HD + d] = float_to_bits<BF16>(vn[t][d]);
+        if constexpr (KV8) {  // wave 0 the K row, wave 1 the V row: HD / 8 lanes of 8 codes each
+            if (tid < 128 && (tid & 63) < HD / 8) {
+                const bool isv = tid >= 64;
+                const int d0 = (tid & 63) * 8;
+                float x[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) x[j] = isv ? vn[0][d0 + j] : kn[0][d0 + j];
+                kv8_store_row<HD / 8>(x, (isv ? vc : kc) + (size_t)p0 * HD + d0, (isv ? vsc : ksc) + p0, d0 == 0);
+            }
+        } else {
+            for (int e = tid; e < T * HD; e += NT) {
+                const int t = e / HD, d = e % HD;
+                kc[(size_t)(p0 + t) * HD + d] = float_to_bits<BF16>(kn[t][d]);
+                vc[(size_t)(p0 + t) * HD + d] = float_to_bits<BF16>(vn[t][d]);
+            }
         }
     }
 
@@ -107,27 +130,33 @@ __device__ __forceinline__ void chunked_attention_body(const float* __restrict__
     for (int ch = sp; ch < nchunks; ch += nsplit) {
         const int r0 = ch * C;
         __syncthreads();  // the previous chunk's ks / vs / sc are consumed
-        for (int e = tid; e < C * (HD / 8); e += NT) {
-            const int rr = e / (HD / 8), seg = e % (HD / 8), r = r0 + rr;
-            float kf[8], vf[8];
+        constexpr int W = KV8 ? 16 : 8;  // elements of a row per 16-byte load
+        for (int e = tid; e < C * (HD / W); e += NT) {
+            const int rr = e / (HD / W), seg = e % (HD / W), r = r0 + rr;
+            float kf[W], vf[W];
             if (r < p0) {  // cached rows (never the rows this launch writes)
-                const u32x4 kw = *reinterpret_cast<const u32x4*>(kc + (size_t)r * HD + seg * 8);
-                const u32x4 vw = *reinterpret_cast<const u32x4*>(vc + (size_t)r * HD + seg * 8);
+                const u32x4 kw = *reinterpret_cast<const u32x4*>(kc + (size_t)r * HD + seg * W);
+                const u32x4 vw = *reinterpret_cast<const u32x4*>(vc + (size_t)r * HD + seg * W);
+                if constexpr (KV8) {
+                    kv8_dequant16(kw, ksc[r], kf);
+                    kv8_dequant16(vw, vsc[r], vf);
+                } else {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    kf[2 * j] = bits_to_float(kw[j] & 0xFFFFu, BF16); kf[2 * j + 1] = bits_to_float(kw[j] >> 16, BF16);
-                    vf[2 * j] = bits_to_float(vw[j] & 0xFFFFu, BF16); vf[2 * j + 1] = bits_to_float(vw[j] >> 16, BF16);
+                    for (int j = 0; j < 4; ++j) {
+                        kf[2 * j] = bits_to_float(kw[j] & 0xFFFFu, BF16); kf[2 * j + 1] = bits_to_float(kw[j] >> 16, BF16);
+                        vf[2 * j] = bits_to_float(vw[j] & 0xFFFFu, BF16); vf[2 * j + 1] = bits_to_float(vw[j] >> 16, BF16);
+                    }
                 }
             } else {
                 const int t = min(r - p0, T - 1);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    kf[j] = r < ctx ? kn[t][seg * 8 + j] : 0.0f;
-                    vf[j] = r < ctx ? vn[t][seg * 8 + j] : 0.0f;
+                for (int j = 0; j < W; ++j) {
+                    kf[j] = r < ctx ? kn[t][seg * W + j] : 0.0f;
+                    vf[j] = r < ctx ? vn[t][seg * W + j] : 0.0f;
                 }
             }
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { ks[rr][seg * 8 + j] = kf[j]; vs[rr][seg * 8 + j] = vf[j]; }
+            for (int j = 0; j < W; ++j) { ks[rr][seg * W + j] = kf[j]; vs[rr][seg * W + j] = vf[j]; }
         }
         __syncthreads();
         for (int pq = tid; pq < NQ * C; pq += NT) {  // (query row, context row): causal — row r is visible to token t iff r <= p0 + t

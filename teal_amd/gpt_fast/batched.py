@@ -29,7 +29,7 @@ from . import constraints as CN
 from . import logit_processors as PR
 from . import sampling as SM
 from . import stopping as ST
-from .engine_features import SamplerFeatures, _SlotCaches, dense_16bit_refusal, slab_chain_refusal
+from .engine_features import SamplerFeatures, _SlotCaches, dense_16bit_refusal, kv_cache_refusal, slab_chain_refusal
 from .model import Transformer
 from .prefill import MAX_T, PrefillEngine, PrefillIn, SlabChain
 from .speculative import VerifyPass
@@ -40,9 +40,14 @@ NINF = float("-inf")
 
 
 class BatchedDecodeEngine(SlabChain, SamplerFeatures):
+    _kv_kind = "batched"  # kv_cache_refusal's name of this engine
+
     @staticmethod
-    def supports(model: Transformer) -> Optional[str]:
+    def supports(model: Transformer, kv_cache: Optional[str] = None) -> Optional[str]:
         """None if the batched step can run `model` as it stands (batch = the caches' max_batch_size), else the reason."""
+        why = kv_cache_refusal("batched", kv_cache)
+        if why is not None:
+            return why
         cfg = model.config
         if int(getattr(model, "tp_world", 1)) > 1:
             return "tensor-parallel models are not batched (decode them one sequence at a time)"
@@ -74,13 +79,19 @@ class BatchedDecodeEngine(SlabChain, SamplerFeatures):
             return f"batch size {B} outside 1..{BATCH_MAX} (setup_caches(max_batch_size=B))"
         return None
 
-    def __init__(self, model: Transformer, thresholds: List[Dict[str, float]], batch: int):
+    def __init__(self, model: Transformer, thresholds: List[Dict[str, float]], batch: int, kv_cache: Optional[str] = None):
+        why = kv_cache_refusal(self._kv_kind, kv_cache)
+        if why is not None:
+            raise ValueError(f"{type(self).__name__}: {why}")
+        self.kv_cache = kv_cache
         why = BatchedDecodeEngine.supports(model)
         if why is not None:
             raise ValueError(f"BatchedDecodeEngine cannot run this model: {why}")
         B = int(batch)
         cache_b = model.layers[0].attention.kv_cache.k_cache.shape[0]
-        if not 1 <= B <= BATCH_MAX or B != cache_b:
+        if kv_cache is not None and not 1 <= B <= BATCH_MAX:  # (fp8: the slots are the engine's own, not the model's caches)
+            raise ValueError(f"{type(self).__name__}: batch {B} outside 1..{BATCH_MAX}")
+        if kv_cache is None and (not 1 <= B <= BATCH_MAX or B != cache_b):
             raise ValueError(f"BatchedDecodeEngine: batch {B} must equal the caches' max_batch_size ({cache_b}) and be <= {BATCH_MAX}")
         if len(thresholds) != len(model.layers):
             raise ValueError("one thresholds dict per layer")
@@ -376,9 +387,31 @@ class SlotDecodeEngine(BatchedDecodeEngine):
 
     _stops: Optional[ST.StopConditions] = None   # set_stop_conditions
     tau_table: Optional[torch.Tensor] = None     # set_slot_sparsity: fp32 [n_layer][4 launches][3][8] (None while it is off)
+    _kv_kind = "slot"
+    kv8 = None                                   # kv_cache="fp8": per layer (k codes, v codes, k scales, v scales)
 
-    def __init__(self, model: Transformer, thresholds: List[Dict[str, float]], batch: int):
-        super().__init__(model, thresholds, batch)
+    @staticmethod
+    def supports(model: Transformer, kv_cache: Optional[str] = None) -> Optional[str]:
+        """None if the slot step can run `model` as it stands, else the reason.  kv_cache None: batch = the caches' max_batch_size.
+        "fp8": the model's caches are the staging cache, setup_caches(max_batch_size=1); the batch is the constructor's."""
+        why = kv_cache_refusal("slot", kv_cache) or BatchedDecodeEngine.supports(model)
+        cache_b = model.layers[0].attention.kv_cache.k_cache.shape[0] if why is None else 1
+        if kv_cache is not None and cache_b != 1:
+            why = (f"kv_cache={kv_cache!r} keeps the model's own caches as the staging cache of the prompt passes, the only 16-bit K / V "
+                   f"left: setup_caches(max_batch_size=1), not {cache_b} (the engine owns the slots' fp8 rows)")
+        return why
+
+    def __init__(self, model: Transformer, thresholds: List[Dict[str, float]], batch: int, kv_cache: Optional[str] = None):
+        """kv_cache None: the B slots are the model's own [B, n_kv, max_seq, hd] caches — every launch and allocation as without the
+        keyword.  "fp8": the engine owns the slots' K / V as e4m3fn codes [B, n_kv, max_seq, hd] and power-of-two scales
+        [B, n_kv, max_seq] per layer (include/teal_hip.h, "fp8 KV cache"); the model's caches, batch 1, are the staging cache every
+        prompt pass writes, and one teal_kv8_quantize_rows launch per admission moves the prompt's rows into the slot.  A row is
+        attended exactly by the pass that makes it (the prompt pass, a step's own new row) and as fp8 by every later step."""
+        if kv_cache is not None:  # (the format, then the staging cache: checked here, before the batched engine's own checks)
+            why = SlotDecodeEngine.supports(model, kv_cache=kv_cache)
+            if why is not None:
+                raise ValueError(f"SlotDecodeEngine cannot run this model: {why}")
+        super().__init__(model, thresholds, batch, kv_cache)
         dev = self.logits.device
         self.slot_state = torch.zeros(SLOT_WORDS, dtype=torch.int32, device=dev)
         self.slot_state[SLOT_EOS:SLOT_EOS + 8] = -1
@@ -389,7 +422,21 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         self.admit_paths = {"hip": 0, "module": 0}
         # shared prefixes: per slot the device table of its 2 L cache tensors' addresses (K, V of layer 0, K, V of layer 1, ...)
         caches = [c for layer in model.layers for c in (layer.attention.kv_cache.k_cache, layer.attention.kv_cache.v_cache)]
-        self._slot_tables = [torch.tensor([c[s].data_ptr() for c in caches], dtype=torch.int64).to(dev) for s in range(self.B)]
+        table = lambda ts, s: torch.tensor([t[s].data_ptr() for t in ts], dtype=torch.int64).to(dev)  # noqa: E731
+        # (fp8: the one 16-bit "slot" is the staging cache; the slots proper are the code and scale tensors below)
+        self._slot_tables = [table(caches, s) for s in range(caches[0].shape[0])]
+        if kv_cache is not None:
+            cfg = self.cfg
+            shape = (self.B, cfg.n_local_heads, self.max_seq)
+            # per layer (k codes, v codes, k scales, v scales); a scale of 1 under rows nobody wrote yet
+            self.kv8 = [(torch.zeros(*shape, self.hd, dtype=torch.uint8, device=dev), torch.zeros(*shape, self.hd, dtype=torch.uint8, device=dev),
+                         torch.ones(*shape, dtype=torch.float32, device=dev), torch.ones(*shape, dtype=torch.float32, device=dev))
+                        for _ in model.layers]
+            self._kv8_of = {id(layer.attention): i for i, layer in enumerate(model.layers)}
+            codes = [c for kc, vc, _, _ in self.kv8 for c in (kc, vc)]
+            scales = [c for _, _, ks, vs in self.kv8 for c in (ks, vs)]
+            self._code_tables = [table(codes, s) for s in range(self.B)]
+            self._scale_tables = [table(scales, s) for s in range(self.B)]
         self._prefixes: Dict[str, _Prefix] = {}
         self._verify: Optional[SlotVerifyPass] = None
         self._verify_why: Optional[str] = None
@@ -399,6 +446,38 @@ class SlotDecodeEngine(BatchedDecodeEngine):
     @property
     def _active(self) -> int:
         return self.slot_state.data_ptr()
+
+    def _attention(self, at, A: torch.Tensor, ns: int, st):
+        if self.kv8 is None:
+            return super()._attention(at, A, ns, st)
+        cfg = self.cfg
+        kc, vc, ks, vs = self.kv8[self._kv8_of[id(at)]]
+        rc = self.L.teal_batched_decode_attention_slots_kv8(
+            A.data_ptr(), ns, self.rope.data_ptr(), self.pos_buf.data_ptr(), self._active, kc.data_ptr(), vc.data_ptr(), ks.data_ptr(),
+            vs.data_ptr(), self.yt.data_ptr(), self.partials.data_ptr(), self.partials.numel() * 4, self.B, cfg.n_head, cfg.n_local_heads,
+            cfg.head_dim, self.max_seq, self.code, st)
+        if rc != 0:
+            _lib.check(rc, "teal_batched_decode_attention_slots_kv8")
+
+    def _quantize_rows(self, s: int, rows: int):
+        """rows 0 .. rows-1 of the staging cache (every layer's K and V) into slot s's codes and scales: one launch"""
+        rc = self.L.teal_kv8_quantize_rows(self._slot_tables[0].data_ptr(), self._code_tables[s].data_ptr(), self._scale_tables[s].data_ptr(),
+                                           2 * len(self.model.layers), self.cfg.n_local_heads, self.hd, rows, self.max_seq, self.max_seq,
+                                           self.code, runtime.stream_ptr())
+        if rc != 0:
+            _lib.check(rc, "teal_kv8_quantize_rows")
+
+    def _cache_slot(self, s: int) -> int:
+        """the slot of the model's caches a prompt pass for slot s writes: s itself, or the staging cache's only one"""
+        return s if self.kv8 is None else 0
+
+    def kv_cache_bytes(self) -> Dict[str, int]:
+        """bytes of K / V the engine's slots hold, by kind.  staging: the model's own 16-bit caches (kv_cache None: they ARE the B
+        slots; "fp8": the one sequence the prompt passes write).  codes / scales: the slots' fp8 rows (0 without them)."""
+        nbytes = lambda ts: sum(t.numel() * t.element_size() for t in ts)  # noqa: E731
+        staging = nbytes(c for layer in self.model.layers for c in (layer.attention.kv_cache.k_cache, layer.attention.kv_cache.v_cache))
+        kv8 = self.kv8 or []
+        return {"staging": staging, "codes": nbytes(c for t in kv8 for c in t[:2]), "scales": nbytes(c for t in kv8 for c in t[2:])}
 
     def _retire(self, mask: int, count_step: bool, st):
         if self._stops is not None:  # the same place in the step, one launch for one
@@ -419,7 +498,7 @@ class SlotDecodeEngine(BatchedDecodeEngine):
 
     def _feature_key(self):
         return super()._feature_key() + (("stops",) if self._stops is not None else ()) + \
-               (("slot sparsity",) if self.tau_table is not None else ())
+               (("slot sparsity",) if self.tau_table is not None else ()) + ((f"kv {self.kv_cache}",) if self.kv_cache is not None else ())
 
     # ---- stop conditions ---------------------------------------------------------------------------------------------------
     def set_stop_conditions(self, on: bool):
@@ -548,13 +627,14 @@ class SlotDecodeEngine(BatchedDecodeEngine):
     # ---- admission ---------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def _prompt_pass(self, s: int, prompt: torch.Tensor) -> torch.Tensor:
-        """the dense prompt pass of one request into slot s's caches only -> logits [vocab] of its last token"""
+        """the dense prompt pass of one request into slot s's caches only (fp8: into the staging cache) -> logits [vocab] of its last
+        token"""
         T = int(prompt.numel())
         m = self.model
         if 2 <= T <= MAX_T:  # the HIP prompt pass at the slot's cache base pointers
             if self._prefill is None:
                 self._prefill = SlotPrefillEngine(m)
-            self._prefill.slot = s
+            self._prefill.slot = self._cache_slot(s)
             self.admit_paths["hip"] += 1
             return self._prefill(prompt.to(torch.int32)).view(-1)
         # the module path on a batch-1 view of slot s (the op-by-op ops: a one-token prompt takes the sparse kernels, a longer
@@ -570,7 +650,7 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         fused = m.fused_decode
         try:
             for layer, kc in zip(m.layers, saved):
-                layer.attention.kv_cache = _SlotCacheView(kc, s)
+                layer.attention.kv_cache = _SlotCacheView(kc, self._cache_slot(s))
             m.fused_decode = False
             logits = m(prompt.view(1, -1), torch.arange(start, start + T, device=prompt.device))
         finally:
@@ -635,13 +715,13 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         """the prefix's rows into slot s (one launch), then the dense pass over the suffix at positions P .. P+T-1 into slot s's
         caches only -> logits [vocab] of its last token"""
         T = int(suffix.numel())
-        self._copy_rows(pf.table, self._slot_tables[s], pf.rows, pf.rows, self.max_seq)
+        self._copy_rows(pf.table, self._slot_tables[self._cache_slot(s)], pf.rows, pf.rows, self.max_seq)
         if T <= MAX_T and self._verify is None and self._verify_why is None:
             self._verify_why = SlotVerifyPass.supports(self.model)
             if self._verify_why is None:
                 self._verify = SlotVerifyPass(self.model)
         if T <= MAX_T and self._verify is not None:  # the HIP verify pass at the slot's cache base pointers
-            self._verify.slot = s
+            self._verify.slot = self._cache_slot(s)
             self.prefix_paths["hip"] += 1
             return self._verify.last_logits(self._verify.run(suffix, pf.pos, T), T)
         self.prefix_paths["module"] += 1
@@ -722,6 +802,8 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         if self._proc is not None:  # (every admission: the slot's last request left its counts and its parameters)
             self._proc.set_row(s, (pf.tokens if pf is not None else []) + prompt.tolist(), **controls)
         logits = self._prompt_pass(s, prompt) if pf is None else self._suffix_pass(s, pf, prompt)
+        if self.kv8 is not None:  # the staging cache's rows 0 .. P+T-1 into the slot (outside the captured step)
+            self._quantize_rows(s, P + T)
         self.admit_logits = logits  # (the last admission's, for tests and reports: valid until the next one)
         self.rng_state[s].copy_(torch.tensor([int(seed), 0], dtype=torch.int64), non_blocking=False)
         self.pos_buf[s] = P + T - 1  # the sampler moves it to P + T: the row the first decode step writes

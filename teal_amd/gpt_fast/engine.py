@@ -27,7 +27,7 @@ from typing import Dict, List, Optional
 import torch
 
 from .. import _lib, runtime
-from .engine_features import SamplerFeatures, model_linears, relayout
+from .engine_features import SamplerFeatures, kv_cache_refusal, model_linears, relayout
 from .model import Transformer
 
 TEAL_IN_PLAIN, TEAL_IN_RESID_NORM, TEAL_IN_SILU_MUL, TEAL_IN_MASKED, TEAL_IN_ATTN_MERGE = 0, 1, 2, 3, 4
@@ -177,7 +177,10 @@ class DecodeEngine(SamplerFeatures):
         return ns, fused_merge, not quantised and not grouped
 
     def __init__(self, model: Transformer, thresholds: List[Dict[str, float]], pair: Optional[bool] = None,
-                 att_split: int = 0, reduce_presummed: Optional[bool] = None):
+                 att_split: int = 0, reduce_presummed: Optional[bool] = None, kv_cache: Optional[str] = None):
+        why = kv_cache_refusal("tensor-parallel" if int(getattr(model, "tp_world", 1)) > 1 else "decode", kv_cache)
+        if why is not None:
+            raise ValueError(f"DecodeEngine: {why}")
         why = DecodeEngine.supports(model)
         if why is not None:
             raise ValueError(f"DecodeEngine cannot run this model: {why}")

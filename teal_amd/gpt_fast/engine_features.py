@@ -92,6 +92,23 @@ def slab_chain_refusal(model, shape_why: str, caches_why: str, own_shape: bool =
     return None
 
 
+KV_CACHE_FORMATS = (None, "fp8")  # SlotDecodeEngine(kv_cache=): the model's 16-bit caches, or e4m3 rows with power-of-two scales
+
+
+def kv_cache_refusal(kind: str, kv_cache: Optional[str]) -> Optional[str]:
+    """why the `kind` engine ("slot", "batched", "decode", "speculative", "tensor-parallel") cannot take kv_cache=, or None.  The fp8
+    cache is filled where a request is admitted: rows leave the 16-bit prompt pass through teal_kv8_quantize_rows, so only the
+    engine that admits can hold one."""
+    if kv_cache is None:
+        return None
+    if kv_cache not in KV_CACHE_FORMATS:
+        return f"unknown kv_cache {kv_cache!r} (None: the model's 16-bit caches; 'fp8': e4m3 rows with power-of-two scales)"
+    if kind != "slot":
+        return (f"kv_cache={kv_cache!r} is SlotDecodeEngine's (continuous batching): the {kind} path has no admission to quantise "
+                "a prompt's rows at")
+    return None
+
+
 class _SlotCaches:
     """the K / V base pointers of slot `slot` of batch-B caches: slot s of a contiguous [B, n_kv, max_seq, hd] cache is itself a
     contiguous [1, n_kv, max_seq, hd] cache"""

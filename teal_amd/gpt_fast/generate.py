@@ -734,6 +734,16 @@ def check_stop_args(args) -> Dict:
     return out
 
 
+def check_kv_cache_args(args) -> Optional[str]:
+    """--kv_cache: the engine's keyword (None: the model's 16-bit caches; "fp8"); refused here, before anything is loaded, anywhere
+    but under --requests: the fp8 cache is filled at an admission, and only continuous batching admits"""
+    fmt = getattr(args, "kv_cache", "model") or "model"
+    if fmt != "model" and getattr(args, "requests", None) is None:
+        raise SystemExit(f"--kv_cache {fmt} needs --requests: the fp8 KV cache is filled where a request is admitted (its prompt's rows "
+                         "are quantised there), and no other decode path admits")
+    return None if fmt == "model" else fmt
+
+
 def _mean_logprob_line(lps) -> str:
     return f"    mean logprob {sum(lps) / max(1, len(lps)):.4f} over {len(lps)} tokens (model distribution, temperature 1)"
 
@@ -948,11 +958,16 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer, request_line
                 raise ValueError(f"request {i}: {e}") from None
     except ValueError as e:
         raise SystemExit(f"--requests: {e}")
-    model.setup_caches(max_batch_size=B, max_seq_length=max_seq)
-    why = SlotDecodeEngine.supports(model)
+    kv_cache = check_kv_cache_args(args)
+    # (fp8: the model's caches are the staging cache of the prompt passes, one sequence; the engine owns the slots' rows)
+    model.setup_caches(max_batch_size=B if kv_cache is None else 1, max_seq_length=max_seq)
+    why = SlotDecodeEngine.supports(model, kv_cache=kv_cache)
     if why is not None:
         raise SystemExit(f"--requests: the batched engine cannot run this model: {why}")
-    eng = SlotDecodeEngine(model, thresholds, B)
+    eng = SlotDecodeEngine(model, thresholds, B, kv_cache=kv_cache)
+    kvb = eng.kv_cache_bytes()
+    print(f"KV cache ({'model' if kv_cache is None else kv_cache}): {kvb['staging'] / 1e6:.2f} MB 16-bit "
+          f"({'the slots' if kv_cache is None else 'the staging cache'}), {kvb['codes'] / 1e6:.2f} MB codes, {kvb['scales'] / 1e6:.2f} MB scales")
     batcher = ContinuousBatcher(eng, sync_every=args.sync_every, temperature=args.temperature, top_k=args.top_k, seed=1234,
                                 use_graph=bool(args.compile), prefixes=prefixes, logprobs=getattr(args, "logprobs", None),
                                 **check_processor_args(args), **check_sampling_args(args), **stop_kw,
@@ -995,7 +1010,7 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer, request_line
             "decoder": type(batcher).__name__, "sequences": res["tokens"], "steps": res["steps"], "admissions": res["admissions"],
             "admission_share": res["admission_share"], "mean_active_slots": res["mean_active_slots"], "union_kept": res["union_kept"],
             "sync_every": res["sync_every"], "prefix_admissions": res["prefix_admissions"],
-            "prefix_rows_reused": res["prefix_rows_reused"], "prefix_paths": res["prefix_paths"],
+            "prefix_rows_reused": res["prefix_rows_reused"], "prefix_paths": res["prefix_paths"], "kv_cache_bytes": kvb,
             **{k: res[k] for k in ("logprobs", "top_logprobs", "finish_reason", "stop_match", "kept_by_request") if k in res}}
 
 
@@ -1013,6 +1028,7 @@ def main(args) -> Dict:
     proc = check_processor_args(args)
     samp = check_sampling_args(args)
     check_stop_args(args)
+    check_kv_cache_args(args)
     if getattr(args, "prefixes", None) is not None and getattr(args, "requests", None) is None:
         raise SystemExit("--prefixes names shared prefixes of continuous batching: it needs --requests")
     if getattr(args, "constraints", None) is not None and getattr(args, "requests", None) is None:
@@ -1247,6 +1263,9 @@ def build_parser() -> argparse.ArgumentParser:
                    "--requests: the default of requests that set none")
     p.add_argument("--min_p", type=float, default=None, help="min-p sampling: after top_p, keep the tokens at least this likely "
                    "relative to the most likely one (in [0, 1); 0: off)")
+    p.add_argument("--kv_cache", type=str, default="model", choices=("model", "fp8"), help="with --requests: the slots' KV cache. "
+                   "model: the model's 16-bit dtype.  fp8: e4m3 rows with one power-of-two scale per row and KV head, about half the "
+                   "bytes per slot and per step; the prompt pass and a row's own step see exact K / V, later steps see fp8")
     p.add_argument("--stop_token_ids", type=str, default=None, help="with --requests: token ids a,b,c (at most 16) — a request also "
                    "ends right after any of them, like --eos_id.  The default of requests that set no \"stop_token_ids\"; a request "
                    "line may also carry \"stop_sequences\" (token id lists) and, with a tokenizer, \"stop\" strings (matched as the "

@@ -23,6 +23,7 @@ import torch
 
 from .. import _lib, runtime
 from .engine import DecodeEngine
+from .engine_features import kv_cache_refusal
 from .model import Transformer
 from .prefill import MAX_T, PrefillEngine
 
@@ -91,7 +92,10 @@ class SpeculativeDecoder:
     the round's); `verify`: the target's VerifyPass.  `fill_in`: the draft has KV caches of its own (a separate draft model)."""
 
     def __init__(self, draft: DecodeEngine, verify: VerifyPass, k: int, temperature: float, top_k: Optional[int], fill_in: bool,
-                 capacity: int, graph: bool = True):
+                 capacity: int, graph: bool = True, kv_cache: Optional[str] = None):
+        why = kv_cache_refusal("speculative", kv_cache)
+        if why is not None:
+            raise ValueError(f"speculative decoding: {why}")
         if not 1 <= int(k) <= MAX_K:
             raise ValueError(f"speculative decoding: speculate_k must be in 1..{MAX_K}, got {k}")
         V = verify.model.config.vocab_size
