@@ -717,6 +717,29 @@ int teal_constrain_logits(const void* logits, size_t logits_stride, int vocab, i
                           const void* rng_state, const int32_t* eos, const int32_t* table, const int32_t* arena, size_t arena_words,
                           int32_t* trace, int trace_len, void* out, size_t out_stride, const int32_t* active, int slot0, void* stream);
 
+/* ---- teacher-forced tokens of continuous batching, teal_amd/csrc/teal_force.hip -------------------------------------------------
+ * One launch after a draw's sampler launch or launches, before the logprob launch (teal_token_logprobs) and before retire.  Row
+ * r < B serves slot slot0 + r.
+ *   c = rng_state[r][1]          (uint64: the draw counter the sampler has just bumped)
+ *   i = c - 1
+ *   n = min(forced_len[r], forced_stride)
+ *   if (active == NULL or bit slot0 + r of active[0] is set) and 0 <= i < n:
+ *       t = forced[r * forced_stride + i]
+ *       tokens[r] = t
+ *       if history != NULL and i < history_len:  history[r * history_len + i] = t
+ *   otherwise nothing is written
+ * The sampler has already moved pos, the counter and the history entry, so the launch leaves exactly the words a sampler that had
+ * drawn t would have left, and everything behind it sees t as the drawn token: teal_token_logprobs reports lp(t) of the model's
+ * raw row, the retire launch (plain or with stop conditions) counts t and matches it, the next step is fed t, and the next
+ * step's logit processors count it.  The ids are not checked against a vocabulary here: that is the admission's.
+ * forced: int32 [B][forced_stride]; forced_len: int32 [B]; rng_state: uint64 [B][2]; tokens: int32 [B]; history: int32
+ * [B][history_len] or NULL.  A null required pointer, B outside 1..8, slot0 < 0 or slot0 + B > 32, forced_stride <= 0 or
+ * history_len < 0 with a history: TEAL_ERR_ARG, every check before any HIP call.  One wave, lane r serving row r; two dependent
+ * load rounds at most ({active word, counter, length}, then the table entry); no atomics, no workspace: replays are
+ * bit-identical. */
+int teal_force_tokens(const int32_t* forced, int forced_stride, const int32_t* forced_len, const void* rng_state, int32_t* tokens,
+                      int32_t* history, int history_len, int B, const int32_t* active, int slot0, void* stream);
+
 /* ---- shared prompt prefixes of continuous batching, teal_amd/csrc/teal_prefix.hip ------------------------------------
  * A prefix is a token sequence whose K / V rows (every layer) are computed once and kept in a device store; a request that names
  * it is admitted by copying those rows into its slot's caches and running a prompt pass over its own tokens only. */

@@ -23,7 +23,7 @@ SOURCES = ("teal_kernels.hip", "teal_attention.hip", "teal_sampler.hip", "teal_g
            "teal_gemv_w8_f16.hip", "teal_gemv_w8_bf16.hip", "teal_gemv_fast_f16.hip", "teal_gemv_fast_bf16.hip", "teal_gemv_int4.hip",
            "teal_gemv_fast_w8_f16.hip", "teal_gemv_fast_w8_bf16.hip", "teal_comparators.hip", "teal_prefill.hip",
            "teal_speculative.hip", "teal_batched.hip", "teal_prefix.hip", "teal_logprob.hip", "teal_logit_adjust.hip",
-           "teal_sample_rows.hip", "teal_stop.hip", "teal_constrain.hip", "teal_kv8.hip")
+           "teal_sample_rows.hip", "teal_stop.hip", "teal_constrain.hip", "teal_kv8.hip", "teal_force.hip")
 # translation units whose kernels take their hot arguments as scalar parameters: the command processor preloads the
 # first 11 dwords into SGPRs at wave launch (no scalar-cache miss before the first activation load)
 PRELOAD = {"teal_gemv_fast_f16.hip": 12, "teal_gemv_fast_bf16.hip": 12, "teal_gemv_fast_w8_f16.hip": 12,
@@ -65,7 +65,8 @@ OPTIONAL_WITH_OVERRIDE = ("teal_decode_attention_split_roped", "teal_prefill_gem
                           "teal_batched_retire", "teal_sample_topk_slot", "teal_kv_copy_rows", "teal_decode_attention_split_plan",
                           "teal_token_logprobs", "teal_score_step", "teal_logit_adjust", "teal_sample_rows",
                           "teal_batched_retire_stops", "teal_constrain_logits", "teal_fused_gemv_plan",
-                          "teal_batched_sparse_gemm_slot_taus", "teal_kv8_quantize_rows", "teal_batched_decode_attention_slots_kv8")
+                          "teal_batched_sparse_gemm_slot_taus", "teal_kv8_quantize_rows", "teal_batched_decode_attention_slots_kv8",
+                          "teal_force_tokens")
 
 # every symbol include/teal_hip.h declares
 EXPORTS = (
@@ -80,7 +81,7 @@ EXPORTS = (
     "teal_batched_sparse_gemm_slots", "teal_batched_decode_attention_slots", "teal_batched_retire", "teal_sample_topk_slot",
     "teal_kv_copy_rows", "teal_decode_attention_split_plan", "teal_token_logprobs", "teal_score_step",
     "teal_logit_adjust", "teal_sample_rows", "teal_batched_retire_stops", "teal_constrain_logits", "teal_fused_gemv_plan",
-    "teal_batched_sparse_gemm_slot_taus", "teal_kv8_quantize_rows", "teal_batched_decode_attention_slots_kv8",
+    "teal_batched_sparse_gemm_slot_taus", "teal_kv8_quantize_rows", "teal_batched_decode_attention_slots_kv8", "teal_force_tokens",
 )
 
 # what libteal_hip_diag.so exports on top (include/teal_hip.h, #ifdef TEAL_DIAGNOSTICS); libteal_hip.so must export NONE of them
@@ -236,6 +237,8 @@ def _open(path: str, diag: bool) -> ctypes.CDLL:
     if hasattr(L, "teal_kv8_quantize_rows"):
         L.teal_kv8_quantize_rows.argtypes = [vp, vp, vp, ci, ci, ci, ci, sz, sz, ci, vp]
         L.teal_batched_decode_attention_slots_kv8.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, ci, ci, ci, vp]
+    if hasattr(L, "teal_force_tokens"):
+        L.teal_force_tokens.argtypes = [vp, ci, vp, vp, vp, vp, ci, ci, vp, ci, vp]
     if hasattr(L, "teal_token_logprobs"):
         L.teal_token_logprobs.argtypes = [vp, sz, ci, ci, ci, vp, vp, vp, ci, ci, vp, vp, vp, ci, vp]
         L.teal_score_step.argtypes = [vp, ci, ci, vp, ci, vp, vp, vp, vp]

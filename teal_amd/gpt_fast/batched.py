@@ -26,6 +26,7 @@ import torch
 from .. import _lib, runtime
 from ..kernels.sparse_gemv import BATCH_MAX, batched_segs
 from . import constraints as CN
+from . import forcing as FT
 from . import logit_processors as PR
 from . import sampling as SM
 from . import stopping as ST
@@ -383,7 +384,8 @@ class SlotDecodeEngine(BatchedDecodeEngine):
     id, its budget or the cache end.  `admit` puts one request into a free slot between replays.  With stop conditions on
     (set_stop_conditions) teal_batched_retire_stops takes the retire launch's place: stop ids, stop sequences, a minimum length
     and a finish reason per request (stopping.py).  With constraints on (set_constraints) one more launch in front of the samplers
-    steps each slot's token automaton and masks the row it draws from (constraints.py)."""
+    steps each slot's token automaton and masks the row it draws from (constraints.py).  With forced tokens on (set_forced_tokens)
+    one more launch behind the samplers puts a request's given tokens in the drawn ones' place (forcing.py)."""
 
     _stops: Optional[ST.StopConditions] = None   # set_stop_conditions
     tau_table: Optional[torch.Tensor] = None     # set_slot_sparsity: fp32 [n_layer][4 launches][3][8] (None while it is off)
@@ -594,6 +596,27 @@ class SlotDecodeEngine(BatchedDecodeEngine):
     def _eos_words(self, row0: int) -> int:
         return self.slot_state.data_ptr() + 4 * (SLOT_EOS + row0)
 
+    # ---- forced tokens -----------------------------------------------------------------------------------------------------
+    def set_forced_tokens(self, on: bool, capacity: Optional[int] = None):
+        """off (the default): every step and every admission issues exactly the launches it issues without this feature.  on: one
+        launch between the samplers and the logprob launch puts, for draws 0 .. n-1 of a request admitted with n forced tokens
+        (admit(..., forced_tokens=)), the given token in the drawn one's place — in the token word and the history entry, the only
+        two words that name it: the logprob, the retire rule, the next step and its logit processors see the forced token as the
+        drawn one.  capacity: the forced tokens a request may carry (default: max_seq); the table is int32 [8][capacity] with a
+        length word per slot, all 0, written by admissions only — nothing of it joins the loop state.  Allowed on an idle engine
+        only (a running slot's row would be empty); drops the captured graphs."""
+        if int(self.slot_state[SLOT_ACTIVE].item()) != 0:
+            raise RuntimeError("set_forced_tokens needs an idle engine: a slot is active")
+        self._frc = FT.ForcedTokens(self.B, self.max_seq if capacity is None else capacity, self.cfg.vocab_size,
+                                    self.history.device) if on else None
+        self._graph = None
+
+    def read_forced(self, slot: int) -> int:
+        """the length word of `slot`: how many tokens its last admission forced (0: none)"""
+        if not 0 <= int(slot) < self.B:
+            raise ValueError(f"slot {slot} outside 0..{self.B - 1}")
+        return self._forced().read(int(slot))
+
     def register_constraint(self, name: str, automaton: CN.Automaton):
         """the automaton's image into the arena under `name`, for admit(..., constraint=name).  It is checked at this engine's
         vocabulary here (ValueError with the reason) and against each request's own EOS id at its admission.  Allowed while slots
@@ -732,7 +755,7 @@ class SlotDecodeEngine(BatchedDecodeEngine):
               top_k: Optional[int] = 200, prefix: Optional[str] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
               frequency_penalty: float = 0.0, logit_bias: Optional[Dict] = None, top_p: float = 1.0, min_p: float = 0.0,
               stop_token_ids=(), stop_sequences=(), min_new_tokens: int = 0, constraint: Optional[str] = None,
-              thresholds: Optional[List[Dict[str, float]]] = None):
+              thresholds: Optional[List[Dict[str, float]]] = None, forced_tokens=()):
         """Request -> slot `slot` (free): the dense prompt pass into that slot's caches, the first token drawn from the last row's
         logits (draw 0 of the stream `seed`), the slot's token, position, history, rng state, budget and EOS set on the device and
         its bit set.  A request whose first token ends it (budget 1, EOS) is switched off again by the same retire rule.
@@ -751,7 +774,12 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         included, is drawn from the tokens its automaton allows, and `eos_id` only in an accepting state.  The automaton is checked
         against this request's `eos_id` here; a temperature above 100 is refused (a banned token's weight must be exactly 0).
         thresholds: the request's own sparsity level, one dict per layer with the constructor's keys (it needs
-        set_slot_sparsity(True)); None: the engine's own.  With the feature on every admission writes the slot's whole column."""
+        set_slot_sparsity(True)); None: the engine's own.  With the feature on every admission writes the slot's whole column.
+        forced_tokens: token ids the request's draws 0 .. n-1 yield in place of what its sampler drew (they need
+        set_forced_tokens(True)): at most the table's capacity and at most `budget`, never together with `constraint` (a forced
+        token may be one the automaton bans).  A forced token is a drawn token for every rule that follows — EOS, stop conditions,
+        budget, processors — and its logprob is the model's for that token.  A larger budget goes on sampling after the last one,
+        from the stream where the draw counter stands.  With the feature on every admission writes the slot's length word."""
         s, B = int(slot), self.B
         prompt = torch.as_tensor(tokens, dtype=torch.int32).view(-1).to(self.logits.device)
         T = int(prompt.numel())
@@ -783,6 +811,16 @@ class SlotDecodeEngine(BatchedDecodeEngine):
             if self.tau_table is None:
                 raise RuntimeError("per-request sparsity is off (set_slot_sparsity)")
             thresholds = self._check_thresholds(thresholds)
+        forced = FT.check_forced(self.cfg.vocab_size, forced_tokens)
+        if forced:
+            if self._frc is None:
+                raise RuntimeError("forced tokens are off (set_forced_tokens)")
+            if len(forced) > self._frc.capacity:
+                raise ValueError(f"{len(forced)} forced tokens: the table holds {self._frc.capacity} per request (set_forced_tokens(capacity=))")
+            if len(forced) > int(budget):
+                raise ValueError(f"{len(forced)} forced tokens exceed the request's budget of {int(budget)}")
+            if constraint is not None:
+                raise ValueError("forced tokens do not combine with a constraint: a forced token may be one the automaton bans")
         if self._samp is not None:
             SM.check_sampling(temperature, top_k, top_p, min_p)
         elif SM.check_sampling(top_p=top_p, min_p=min_p)["top_p"] < 1.0 or min_p > 0.0:
@@ -793,6 +831,8 @@ class SlotDecodeEngine(BatchedDecodeEngine):
         if self.tau_table is not None:  # (every admission: the slot's next occupant never inherits a level)
             col = torch.tensor(self._tau_column(self.ths if thresholds is None else thresholds), dtype=torch.float32)
             self.tau_table[..., s].copy_(col.to(self.tau_table.device))
+        if self._frc is not None:  # (every admission: the slot's next occupant never inherits a row)
+            self._frc.set_row(s, forced)
         if self._con is not None:  # (every admission: the slot's next occupant never inherits a constraint)
             self._con.set_row(s, constraint)
         if self._samp is not None:  # (every admission: the slot's last request left its settings)

@@ -12,7 +12,7 @@ so its tokens do not depend on its slot, on the requests beside it or on sync_ev
 row kept).
 
 What a request may carry beyond that — a shared prefix, logprobs, logit processors, its own sampling, stop conditions, a constraint,
-its own sparsity — is one object each (Prefixes ... Sparsity below; ContinuousBatcher.features): the batcher's defaults, what
+its own sparsity, forced tokens — is one object each (Prefixes ... Forced below; ContinuousBatcher.features): the batcher's defaults, what
 is refused before anything runs, whether the engine feature is switched on, the keywords of the request's admission, and what the
 result gains.  A new per-request feature is one more such object; the scheduling loop names none of them.
 """
@@ -68,10 +68,22 @@ class Request:
     allowed_token_ids: Optional[List[int]] = None
     # its own sparsity level in [0, 1) (None: the run's): the thresholds its slot keeps rows under
     sparsity: Optional[float] = None
+    # teacher forcing: token ids its draws 0 .. n-1 yield in place of what the sampler drew (n <= max_new_tokens; with n ==
+    # max_new_tokens the request only scores them, with a larger budget it goes on sampling behind them: an answer prefix).  A
+    # forced token is a drawn token for every rule that follows — EOS, stop conditions, budget, processors
+    forced_tokens: Optional[List[int]] = None
 
     def __post_init__(self):
         if sum(v is not None for v in (self.constraint, self.choices, self.allowed_token_ids)) > 1:
             raise ValueError("a request takes at most one of constraint, choices and allowed_token_ids")
+        if self.forced_tokens is not None:
+            if not _token_ids(self.forced_tokens):
+                raise ValueError("forced_tokens must be a non-empty list of token ids")
+            if any(v is not None for v in (self.constraint, self.choices, self.allowed_token_ids)):
+                raise ValueError("forced_tokens do not combine with constraint, choices or allowed_token_ids: a forced token may be one "
+                                 "the automaton bans")
+            if len(self.forced_tokens) > self.max_new_tokens:
+                raise ValueError(f"{len(self.forced_tokens)} forced_tokens exceed max_new_tokens {self.max_new_tokens}")
 
     def constraint_spec(self):
         """None, or (name, automaton): the automaton built from `choices` / `allowed_token_ids` under a name made of its content
@@ -301,6 +313,62 @@ def parse_constraint_fields(d: dict, where: str, tokenizer=None, constraints: Op
     return {}
 
 
+FORCED_FIELDS = ("forced_tokens", "forced_text")
+
+
+def parse_forced(d: dict, where: str, tokenizer=None) -> Dict:
+    """the forced-token field of one request object, validated; {} if absent.  "forced_text" is encoded alone, WITHOUT a BOS (needs
+    a tokenizer) — the tokens are what the tokenizer gives for the string by itself, with the caveat of "stop" strings: a
+    continuation the model would spell with other tokens after this prompt is scored as THESE tokens.  Without a tokenizer
+    everything that needs none is still refused (check_forced_fields, before anything is loaded), and {} is returned for a
+    well-formed "forced_text"."""
+    kinds = [k for k in FORCED_FIELDS if k in d]
+    if not kinds:
+        return {}
+    if len(kinds) > 1:
+        raise ValueError(f"{where}: at most one of \"forced_tokens\" and \"forced_text\", got both")
+    both = [k for k in ("constraint", "choices", "allowed_token_ids") if k in d]
+    if both:
+        raise ValueError(f"{where}: \"{kinds[0]}\" does not combine with \"{both[0]}\": a forced token may be one the automaton bans")
+    n = d.get("max_new_tokens")
+    budget = n if isinstance(n, int) and not isinstance(n, bool) else None
+    if "forced_tokens" in d:
+        toks = d["forced_tokens"]
+        if not _token_ids(toks):
+            raise ValueError(f"{where}: \"forced_tokens\" must be a non-empty list of token ids")
+    else:
+        x = d["forced_text"]
+        if not isinstance(x, str) or not x:
+            raise ValueError(f"{where}: \"forced_text\" must be a non-empty string")
+        if tokenizer is None:
+            return {}
+        toks = [int(t) for t in tokenizer.encode(x)]
+        if not toks:
+            raise ValueError(f"{where}: the \"forced_text\" {x!r} encodes to no tokens")
+    if budget is not None and budget < len(toks):
+        raise ValueError(f"{where}: \"max_new_tokens\" {budget} is below the {len(toks)} forced tokens (leave it out to score them only)")
+    return {"forced_tokens": [int(t) for t in toks]}
+
+
+def check_forced_fields(request_lines: Sequence[str], prefix_lines: Sequence[str] = (), tokenizer_expected: bool = True) -> bool:
+    """whether some request line carries forced tokens — needs no tokenizer, so it runs before anything is loaded: an empty list,
+    non-integers, both fields on one line, either field next to a constraint field, a budget below the number of forced tokens,
+    "forced_text" where no tokenizer will be there (tokenizer_expected False) and either field on a prefix line are refused"""
+    for i, d in _json_objects(prefix_lines):
+        for k in FORCED_FIELDS:
+            if k in d:
+                raise ValueError(f"prefix line {i + 1}: \"{k}\" belongs to a request line: a prefix's rows come from the prompt pass, "
+                                 "which draws nothing")
+    found = False
+    for i, d in _json_objects(request_lines):
+        parse_forced(d, f"request line {i + 1}")
+        if "forced_text" in d and not tokenizer_expected:
+            raise ValueError(f"request line {i + 1}: \"forced_text\" needs a tokenizer (a checkpoint), not --synthetic: give "
+                             "\"forced_tokens\"")
+        found = found or any(k in d for k in FORCED_FIELDS)
+    return found
+
+
 def parse_constraints(lines: Sequence[str]) -> Dict[str, Automaton]:
     """JSON Lines, one token automaton per line: {"id": "yes-no", "states": [{"edges": [[token, next], ...], "default": -1,
     "accept": true}, ...]} (state 0 is the start).  Blank lines are skipped; an empty file is an empty mapping."""
@@ -346,6 +414,10 @@ def parse_prefixes(lines: Sequence[str], tokenizer=None) -> Dict[str, List[int]]
         if "sparsity" in d:
             raise ValueError(f"prefix line {i + 1}: \"sparsity\" belongs to a request line: a prefix's rows are computed once, by the "
                              "dense prompt pass")
+        for k in FORCED_FIELDS:
+            if k in d:
+                raise ValueError(f"prefix line {i + 1}: \"{k}\" belongs to a request line: a prefix's rows come from the prompt pass, "
+                                 "which draws nothing")
         if ("tokens" in d) == ("prompt" in d):
             raise ValueError(f"prefix line {i + 1}: needs exactly one of \"tokens\" and \"prompt\"")
         if d["id"] in out:
@@ -385,7 +457,10 @@ def parse_requests(lines: Sequence[str], default_max_new_tokens: int, tokenizer=
     model spells with other tokens (another split, a leading-space variant) is not caught.  A line may carry ONE constraint:
     "constraint" (an id of `constraints`), "choices" (token id lists, or strings — each encoded alone WITHOUT a BOS, with the same
     caveat; the request produces exactly one of them and then the EOS id, so it needs `eos_id`) or "allowed_token_ids".  A line may
-    carry its own "sparsity" (in [0, 1); at most 8 distinct levels in one file)."""
+    carry its own "sparsity" (in [0, 1); at most 8 distinct levels in one file).  A line may carry "forced_tokens" (token ids) or,
+    with a tokenizer, "forced_text" (encoded alone WITHOUT a BOS, with the caveat of "stop" strings): the request's first draws
+    yield these tokens, and the result reports their log-likelihood.  Such a line without "max_new_tokens" gets a budget of their
+    number (it only scores them); a larger budget goes on sampling behind them.  Neither combines with a constraint field."""
     out = []
     for i, line in enumerate(lines):
         if not line.strip():
@@ -409,8 +484,11 @@ def parse_requests(lines: Sequence[str], default_max_new_tokens: int, tokenizer=
             toks = ([] if pid is not None else [tokenizer.bos_id()]) + tokenizer.encode(d["prompt"])
             if not toks:
                 raise ValueError(f"request line {i + 1}: the \"prompt\" under prefix {pid!r} encodes to no tokens (an empty suffix)")
-        n = d.get("max_new_tokens", default_max_new_tokens)
-        if not isinstance(n, int) or n < 1:
+        if "forced_text" in d and tokenizer is None:
+            raise ValueError(f"request line {i + 1}: \"forced_text\" needs a tokenizer (a checkpoint), not --synthetic: give \"forced_tokens\"")
+        frc = parse_forced(d, f"request line {i + 1}", tokenizer)
+        n = d.get("max_new_tokens", len(frc["forced_tokens"]) if frc else default_max_new_tokens)
+        if not isinstance(n, int) or isinstance(n, bool) or n < 1:
             raise ValueError(f"request line {i + 1}: \"max_new_tokens\" must be a positive integer")
         con = parse_constraint_fields(d, f"request line {i + 1}", tokenizer, constraints)
         if "choices" in con and eos_id is None:
@@ -418,7 +496,7 @@ def parse_requests(lines: Sequence[str], default_max_new_tokens: int, tokenizer=
                              "one its last state is a dead end")
         out.append(Request([int(t) for t in toks], n, eos_id, prefix=pid, **parse_controls(d, f"request line {i + 1}"),
                            **parse_sampling(d, f"request line {i + 1}"), **parse_stops(d, f"request line {i + 1}", tokenizer), **con,
-                           **parse_sparsity(d, f"request line {i + 1}")))
+                           **parse_sparsity(d, f"request line {i + 1}"), **frc))
     if not out:
         raise ValueError("no requests")
     sparsity_levels_of(out)
@@ -678,11 +756,63 @@ class Sparsity(_Feature):
         return {"kept_by_request": [t / n if n else None for t, n in zip(self.kept_sum, self.kept_n)]} if self.on else {}
 
 
+class Forced(_Feature):
+    """Teacher forcing: a request may carry tokens its first draws yield in place of what its sampler drew (forcing.py).  The
+    swap happens on the device inside the step, behind the samplers and in front of the logprob and retire launches, so the
+    logprob filed under a forced draw is the model's log p(that token | everything before it) and the request ends on a forced EOS
+    or stop like on a drawn one, whatever sync_every is.
+    Exactly when some request carries forced tokens the engine also offers set_forced_tokens(True) and admit(..., forced_tokens=);
+    only those requests are admitted with the keyword.  `logprobs`: the batcher's Logprobs, whose level is raised to at least 1
+    when this feature switches on (the top-1 alternate decides "is_greedy"), so the result then holds "logprobs" and "top_logprobs"
+    as well.  The result gains, per request in input order (None for a request without forced tokens): "forced" — how many forced
+    draws it made, below the number given if an EOS id, a stop condition or the cache ended it first —, "loglikelihood" — the sum
+    of those draws' fp32 logprobs, added in draw order in Python floats — and "is_greedy" — whether every one of those tokens was
+    its row's top-1 id."""
+
+    def __init__(self, logprobs: Logprobs):
+        self.logprobs = logprobs
+
+    def plan(self, eng, requests):
+        self.given = [list(r.forced_tokens) if r.forced_tokens else None for r in requests]
+        self.kw = [{"forced_tokens": g} if g else {} for g in self.given]
+        for i, (r, g) in enumerate(zip(requests, self.given)):
+            if g and len(g) > r.max_new_tokens:
+                raise ValueError(f"request {i}: {len(g)} forced tokens exceed its budget of {r.max_new_tokens}")
+            if g and r.constraint_spec() is not None:
+                raise ValueError(f"request {i}: forced tokens do not combine with a constraint")
+            if g and not all(0 <= t < eng.cfg.vocab_size for t in g):
+                raise ValueError(f"request {i}: a forced token id is outside the vocabulary 0..{eng.cfg.vocab_size - 1}")
+        if any(self.kw):
+            lp = self.logprobs
+            if not lp.on or lp.n < 1:  # the level the verdicts below need
+                lp.n, lp.on = max(1, lp.n or 0), False
+                lp.switch_on(eng.set_logprobs, lp.n)
+            self.switch_on(eng.set_forced_tokens, True)
+        self.counts: List[Optional[int]] = [None] * len(requests)
+        self.sums: List[Optional[float]] = [None] * len(requests)
+        self.greedy: List[Optional[bool]] = [None] * len(requests)
+
+    def harvest(self, eng, s, r, n):
+        g = self.given[r]
+        if not self.on or not g:
+            return
+        k = min(len(g), n)  # draws 0 .. k-1 were forced: the request's first k tokens ARE g[:k]
+        lps, tops = self.logprobs.lps[r], self.logprobs.tops[r]
+        total = 0.0
+        for v in lps[:k]:
+            total += float(v)
+        self.counts[r], self.sums[r] = k, total
+        self.greedy[r] = all(tops[i][0][0] == g[i] for i in range(k))
+
+    def result(self, eng):
+        return {"forced": self.counts, "loglikelihood": self.sums, "is_greedy": self.greedy} if self.on else {}
+
+
 class ContinuousBatcher:
     """Runs requests through an engine with B slots.  The engine offers B, max_seq, admit(slot, tokens, budget, eos_id, seed,
     temperature, top_k), run_steps(k, temperature, top_k, use_graph), read_state() (the slot state words, one copy),
     read_history(slot, n) and union_kept().  Every other keyword belongs to one of `features` — Prefixes, Logprobs, Processors,
-    Sampling, Stops, Constraints and Sparsity above, which say what they add to this protocol: while none is asked for, an engine
+    Sampling, Stops, Constraints, Sparsity and Forced above, which say what they add to this protocol: while none is asked for, an engine
     needs none of their methods and every call is the one above.  run() may be called again: what a feature switched on stays on."""
 
     def __init__(self, engine, sync_every: int = 8, refill: str = "free", temperature: float = 0.8, top_k: Optional[int] = 200,
@@ -698,9 +828,10 @@ class ContinuousBatcher:
         self.eng, self.K, self.refill = engine, int(sync_every), refill
         self.temperature, self.top_k, self.seed, self.use_graph = temperature, top_k, int(seed), use_graph
         sampling = Sampling(temperature, top_k, top_p, min_p)
-        self.features = [Prefixes(prefixes), Logprobs(logprobs), Processors(repetition_penalty, presence_penalty, frequency_penalty),
+        lps = Logprobs(logprobs)
+        self.features = [Prefixes(prefixes), lps, Processors(repetition_penalty, presence_penalty, frequency_penalty),
                          sampling, Stops(stop_token_ids, min_new_tokens, finish_reason), Constraints(constraints, sampling),
-                         Sparsity(sparsity, sparsity_levels)]
+                         Sparsity(sparsity, sparsity_levels), Forced(lps)]
         self.prefixes = self.features[0].prefixes  # (the fit check counts a prefix's rows)
 
     def _clock(self):

@@ -1,6 +1,6 @@
 """What the fused engines share on the host side: the model's linears and the pointers a captured pass holds, the checks
 every dense-chain engine starts `supports` with, and the sampler-side features (token logprobs, logit processors, constraints,
-per-request sampling) of the decode engines with the one launch sequence that draws a token under them.  A new per-request feature of the
+per-request sampling, forced tokens) of the decode engines with the one launch sequence that draws a token under them.  A new per-request feature of the
 sampler goes into `SamplerFeatures` only.
 """
 from __future__ import annotations
@@ -11,6 +11,7 @@ import torch
 
 from ..monkeypatch import UP_SHIFT_BYTES, to_column_major
 from . import constraints as CN
+from . import forcing as FT
 from . import logit_processors as PR
 from . import logprobs as LP
 from . import sampling as SM
@@ -124,7 +125,8 @@ class _SlotCaches:
 class SamplerFeatures:
     """Token logprobs (logprobs.py: one launch behind the sampler), per-request logit processors (logit_processors.py: one
     launch in front of it), constraints (constraints.py: one launch between the two, on a slot engine) and per-request sampling
-    (sampling.py: one launch in the samplers' place), all off until switched on,
+    (sampling.py: one launch in the samplers' place) and forced tokens (forcing.py: one launch behind the samplers, on a slot
+    engine), all off until switched on,
     and `_draw`, the launches of a draw under them.  The host class provides `_feature_rows` (its sequences), `history` (int32
     [..., length]: a logprob row is as long), `cfg.vocab_size`, `dtype`, `code`, a `_graph` the setters drop and `_sample_row`."""
 
@@ -132,6 +134,7 @@ class SamplerFeatures:
     _proc: Optional[PR.LogitProcessors] = None   # set_logit_processors
     _samp: Optional[SM.SamplingParams] = None    # set_sampling_params
     _con: Optional[CN.Constraints] = None        # set_constraints (a slot engine's)
+    _frc: Optional[FT.ForcedTokens] = None       # set_forced_tokens (a slot engine's)
     _active: Optional[int] = None                # the address of a slot engine's active word: its launches are predicated on it
 
     def _feature_refusal(self, what: str) -> None:
@@ -214,6 +217,18 @@ class SamplerFeatures:
             raise NotImplementedError(f"{type(self).__name__} has no per-request sparsity: a request's thresholds are written at its "
                                       "admission, which only SlotDecodeEngine has")
 
+    def set_forced_tokens(self, on: bool, capacity: Optional[int] = None):
+        """forced tokens belong to the slot engine: a request's tokens are written at its admission, and this engine has none —
+        switching them on is refused with that reason (off is what it is)"""
+        if on:
+            raise NotImplementedError(f"{type(self).__name__} has no forced tokens: a request's tokens are written at its admission, and "
+                                      "this engine has no admission (only SlotDecodeEngine has)")
+
+    def _forced(self) -> FT.ForcedTokens:
+        if self._frc is None:
+            raise RuntimeError("forced tokens are off (set_forced_tokens)")
+        return self._frc
+
     def _constraints(self) -> CN.Constraints:
         if self._con is None:
             raise RuntimeError("constraints are off (set_constraints)")
@@ -244,7 +259,8 @@ class SamplerFeatures:
               fed: Optional[torch.Tensor] = None, st=None):
         """Sequences row0 .. row0+rows-1 draw their next token from `logits` (rows `stride` elements apart; 0: the one row as it
         stands): the processors' launch (if on), the constrain launch (if on) over what they left, then ONE sampling launch over the rows or the fused top-k sampler row by row,
-        then the logprob launch (if on) over the logits as the model gave them.  rng_state / tokens / pos / history are the first
+        then the forcing launch (if on), which puts a row's forced token in the drawn one's place, then the logprob launch (if on)
+        over the logits as the model gave them.  rng_state / tokens / pos / history are the first
         row's; pos and history None: the draw feeds no loop state.  count_token: the processors first count each row's token in
         `fed` (default `tokens`: the buffer the step was fed from) as generated."""
         active, src = self._active, logits
@@ -260,6 +276,8 @@ class SamplerFeatures:
         else:
             for r in range(rows):
                 self._sample_row(row0 + r, src[r] if stride else src, temperature, top_k, pos is not None, st)
+        if self._frc is not None:  # behind the samplers, in front of everything that reads the drawn token
+            self._frc.launch(rows, rng_state, tokens, history, self.history.shape[-1], row0=row0, active=active, st=st)
         if self._lp is not None:  # (a slot engine: predicated on the active word the samplers saw — retire clears bits behind it)
             self._lp.launch(logits, stride, self.cfg.vocab_size, self.code, rows, tokens, rng_state, row0=row0, active=active, st=st)
 
@@ -271,6 +289,7 @@ class SamplerFeatures:
                (list(self._con.loop_tensors()) if self._con is not None else [])
 
     def _feature_key(self):
-        """the features' share of a captured step's key (per-request sampling and constraints add their word only while on)"""
+        """the features' share of a captured step's key (per-request sampling, constraints and forced tokens add their word only
+        while on)"""
         return (None if self._lp is None else self._lp.top_n, self._proc is not None) + (("sampling",) if self._samp is not None else ()) + \
-               (("constraints",) if self._con is not None else ())
+               (("constraints",) if self._con is not None else ()) + (("forced",) if self._frc is not None else ())

@@ -864,9 +864,10 @@ def _read_lines(path) -> List[str]:
 def check_request_files(args):
     """--requests, --prefixes and --constraints, each read once -> (request lines, prefix lines, the constraints parsed, the
     requests' sparsity levels).  What needs neither the model nor a tokenizer is refused here, before anything is loaded, in this
-    order: a malformed automaton or a request on a constraint nobody defined, a request on a prefix nobody defined, and
+    order: a malformed automaton or a request on a constraint nobody defined, a request on a prefix nobody defined, a malformed
+    "forced_tokens" / "forced_text" field (or one on a prefix line, or a "forced_text" under --synthetic), and
     check_request_sparsity's refusals"""
-    from teal_amd.gpt_fast.continuous import check_constraint_ids, check_prefix_ids, parse_constraints
+    from teal_amd.gpt_fast.continuous import check_constraint_ids, check_forced_fields, check_prefix_ids, parse_constraints
     cf, pf = getattr(args, "constraints", None), getattr(args, "prefixes", None)
     try:
         request_lines = _read_lines(args.requests)
@@ -877,6 +878,7 @@ def check_request_files(args):
     try:
         prefix_lines = _read_lines(pf) if pf is not None else []
         check_prefix_ids(request_lines, prefix_lines)
+        check_forced_fields(request_lines, prefix_lines, tokenizer_expected=not getattr(args, "synthetic", None))
     except (OSError, ValueError) as e:
         raise SystemExit(f"--requests: {e}")
     return request_lines, prefix_lines, constraints, check_request_sparsity(args, request_lines)
@@ -933,6 +935,7 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer, request_line
     --compile, with one warm-up run first).  request_lines / prefix_lines / constraints: what check_request_files read"""
     from teal_amd.gpt_fast.batched import SlotDecodeEngine
     from teal_amd.gpt_fast.continuous import ContinuousBatcher, cache_rows, parse_prefixes, parse_requests
+    from teal_amd.gpt_fast.forcing import check_forced
     from teal_amd.gpt_fast.stopping import check_stops
     B = int(args.batch_size)
     constraints = constraints or {}
@@ -953,6 +956,7 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer, request_line
             max_seq = max(max_seq, min(max(len(t) for t in prefixes.values()) + 2, model.config.block_size))
         for i, r in enumerate(reqs):  # an id outside this model's vocabulary: refused before anything runs
             try:
+                check_forced(model.config.vocab_size, r.forced_tokens)
                 check_stops(model.config.vocab_size, **r.stops(stop_kw))
             except ValueError as e:
                 raise ValueError(f"request {i}: {e}") from None
@@ -991,6 +995,9 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer, request_line
         print(f"[request {i}, slot {res['slots'][i]}] {text}")
         if "logprobs" in res and tokenizer is not None:
             print(_mean_logprob_line(res["logprobs"][i]))
+        if res.get("forced", [None] * len(reqs))[i] is not None:
+            print(f"    {res['forced'][i]} forced tokens: loglikelihood {res['loglikelihood'][i]:.4f}, "
+                  f"{'all' if res['is_greedy'][i] else 'not all'} of them the model's top-1")
         if "finish_reason" in res and tokenizer is not None:
             what = {"stop_token": f" (token {res['stop_match'][i]})", "stop_sequence": f" (stop sequence {res['stop_match'][i]})"}
             print(f"    finish reason: {res['finish_reason'][i]}{what.get(res['finish_reason'][i], '')}")
@@ -1011,7 +1018,8 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer, request_line
             "admission_share": res["admission_share"], "mean_active_slots": res["mean_active_slots"], "union_kept": res["union_kept"],
             "sync_every": res["sync_every"], "prefix_admissions": res["prefix_admissions"],
             "prefix_rows_reused": res["prefix_rows_reused"], "prefix_paths": res["prefix_paths"], "kv_cache_bytes": kvb,
-            **{k: res[k] for k in ("logprobs", "top_logprobs", "finish_reason", "stop_match", "kept_by_request") if k in res}}
+            **{k: res[k] for k in ("logprobs", "top_logprobs", "finish_reason", "stop_match", "kept_by_request", "forced", "loglikelihood",
+                                    "is_greedy") if k in res}}
 
 
 def sample_batch(logits: torch.Tensor, temperature: float, top_k: Optional[int]) -> torch.Tensor:
@@ -1238,7 +1246,8 @@ def build_parser() -> argparse.ArgumentParser:
                    "single-token calls: A/B against the fused decode step")
     p.add_argument("--requests", type=Path, default=None, help="continuous batching: a JSON Lines file, one request per line "
                    "({\"tokens\": [...]} or {\"prompt\": \"...\"}, optional \"max_new_tokens\"); --batch_size slots, refilled as "
-                   "requests finish")
+                   "requests finish.  A line may carry \"forced_tokens\": [ids] (or \"forced_text\"): its first draws yield these "
+                   "tokens and their log-likelihood is reported")
     p.add_argument("--prefixes", type=Path, default=None, help="with --requests: a JSON Lines file of shared prefixes, one per line "
                    "({\"id\": \"sys\", \"tokens\": [...]} or {\"id\": \"sys\", \"prompt\": \"...\"}); a request line that carries "
                    "\"prefix\": \"sys\" gives only its own suffix and reuses the prefix's K / V rows, computed once")

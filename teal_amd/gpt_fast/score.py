@@ -1,7 +1,7 @@
 """Perplexity of the fused decode path under TEAL sparsity, on the caller's own token ids.
 
     python -m teal_amd.gpt_fast.score (--synthetic NAME | --checkpoint_path P)
-        [--hist_path H --sparsity S | --greedy_lookup ...] --tokens FILE [--window W]
+        [--hist_path H --sparsity S | --greedy_lookup ...] --tokens FILE [--window W] [--batch_size B]
 
 FILE is JSON Lines of {"tokens": [...]} (with a tokenizer — a checkpoint — {"text": "..."} too).  Each sequence is cut into
 windows of at most W tokens (default: the cache length, the model's block_size) and each window is scored by teacher forcing
@@ -18,7 +18,15 @@ the decode steps sparse; here the context's K / V rows come from sparsified step
 an upper bound on the damage sparsity does to generation after a dense prompt pass.  The logprobs are the model's own
 distribution (temperature 1, no top-k filter).  A window's first token is conditioned on nothing and is not scored (a window of
 T tokens gives T - 1 logprobs), so windows are not comparable with a sliding-context evaluation; a trailing window of one token
-scores nothing.  No dataset ships with this repository and none is downloaded: the tool scores the token ids it is given.
+scores nothing.
+
+--batch_size B (2..8) scores the same windows through continuous batching instead: each window w becomes a request with the prompt
+[w[0]], forced_tokens w[1:] and no EOS id, B of them share the batched step (SlotDecodeEngine, ContinuousBatcher), and a window's
+logprobs are those of its forced draws.  The two perplexities are printed as before, the second from a second engine at thresholds
+-1.  What differs from the single-stream numbers: position 0 of a window goes through the admission's prompt pass (a one-token
+prompt: the module path's op-by-op kernels, at the leg's thresholds) and not through the fused decode step, and the batched chain's
+sums are grouped differently from the lean GEMV's (slabs summed in slice order, rounded once) — so the numbers are close to
+DecodeEngine.score's, not identical.  Without the flag the tool is as it was.  No dataset ships with this repository and none is downloaded: the tool scores the token ids it is given.
 """
 from __future__ import annotations
 
@@ -86,6 +94,26 @@ def score_windows(eng, windows: Sequence[Sequence[int]], use_graph: bool = True)
     return [eng.score(torch.tensor(w, dtype=torch.int32), use_graph=use_graph).tolist() for w in windows]
 
 
+def score_windows_batched(eng, windows: Sequence[Sequence[int]], use_graph: bool = True, sync_every: int = 8) -> List[List[float]]:
+    """the windows as teacher-forced requests through ContinuousBatcher on a SlotDecodeEngine: window w is the prompt [w[0]] with
+    forced_tokens w[1:] and no EOS id; -> per window the logprobs of its forced draws (len(w) - 1 of them)"""
+    from teal_amd.gpt_fast.continuous import ContinuousBatcher, Request
+    reqs = [Request([int(w[0])], len(w) - 1, None, forced_tokens=[int(t) for t in w[1:]]) for w in windows]
+    res = ContinuousBatcher(eng, sync_every=sync_every, use_graph=use_graph, logprobs=1).run(reqs)
+    short = [i for i, (k, w) in enumerate(zip(res["forced"], windows)) if k != len(w) - 1]
+    if short:
+        raise RuntimeError(f"window {short[0]} made {res['forced'][short[0]]} of its {len(windows[short[0]]) - 1} forced draws")
+    return [lp[:len(w) - 1] for lp, w in zip(res["logprobs"], windows)]
+
+
+def set_module_thresholds(model, ths: List[Dict[str, float]]) -> None:
+    """the thresholds the patched modules' own forward (the admission pass of a one-token prompt) masks under"""
+    for layer, th in zip(model.layers, ths):
+        at, ff = layer.attention, layer.feed_forward
+        at.thresh_q, at.thresh_k, at.thresh_v, at.thresh_o = (th[k] for k in ("q", "k", "v", "o"))
+        ff.thresh_up, ff.thresh_gate, ff.thresh_down = th["up"], th["gate"], th["down"]
+
+
 def dense_thresholds(ths: List[Dict[str, float]]) -> List[Dict[str, float]]:
     """every row kept: |x| > -1"""
     return [{p: -1.0 for p in th} for th in ths]
@@ -105,6 +133,8 @@ def main(args) -> Dict:
         raise SystemExit("score: --sparsity must be in [0, 1)")
     if args.window is not None and args.window < 2:
         raise SystemExit("score: --window must be at least 2 tokens")
+    if args.batch_size is not None and not 2 <= args.batch_size <= 8:
+        raise SystemExit("score: --batch_size must be in 2..8 (without it the windows are scored one at a time)")
     device = args.device
     dtype = {"fp16": torch.float16, "bf16": torch.bfloat16}[args.precision]
     runtime.init()
@@ -131,6 +161,23 @@ def main(args) -> Dict:
     ths = G.apply_sparsity(model, sparsity=args.sparsity, hist_path=args.hist_path, greedy_lookup=args.greedy_lookup,
                            synthetic=bool(args.synthetic))
     model.max_seq_length, model.max_batch_size = -1, -1
+    n = sum(len(w) - 1 for w in windows)
+    if args.batch_size is not None:
+        from teal_amd.gpt_fast.batched import SlotDecodeEngine
+        B = int(args.batch_size)
+        model.setup_caches(max_batch_size=B, max_seq_length=max(len(w) for w in windows))
+        G.relayout_for_engine(model)
+        why = SlotDecodeEngine.supports(model)
+        if why is not None:
+            raise SystemExit(f"score: --batch_size: the batched engine cannot run this model: {why}")
+        sparse = perplexity(score_windows_batched(SlotDecodeEngine(model, ths, B), windows))
+        set_module_thresholds(model, dense_thresholds(ths))
+        dense = perplexity(score_windows_batched(SlotDecodeEngine(model, dense_thresholds(ths), B), windows))
+        print(f"{len(windows)} windows of at most {W} tokens, {n} scored tokens (model distribution, temperature 1; {B} windows per "
+              "batched step, position 0 of each through the prompt pass)")
+        print(f"perplexity at sparsity {args.sparsity:g}: {sparse:.4f}")
+        print(f"perplexity with every row kept (thresholds -1), same windows: {dense:.4f}")
+        return {"perplexity": sparse, "perplexity_dense": dense, "windows": len(windows), "scored_tokens": n, "window": W, "batch_size": B}
     model.setup_caches(max_batch_size=1, max_seq_length=max(len(w) for w in windows))
     G.relayout_for_engine(model)
     cls, why = pick_engine(model)
@@ -140,7 +187,6 @@ def main(args) -> Dict:
     sparse = perplexity(score_windows(eng, windows))
     eng.set_thresholds(dense_thresholds(ths))
     dense = perplexity(score_windows(eng, windows))
-    n = sum(len(w) - 1 for w in windows)
     print(f"{len(windows)} windows of at most {W} tokens, {n} scored tokens (model distribution, temperature 1; every position "
           "through the sparse decode step)")
     print(f"perplexity at sparsity {args.sparsity:g}: {sparse:.4f}")
@@ -158,6 +204,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--greedy_lookup", type=str, default=None, help="models/<name>/lookup directory (block-wise greedy sparsities)")
     p.add_argument("--tokens", type=Path, required=True, help="JSON Lines: {\"tokens\": [...]} or, with a tokenizer, {\"text\": \"...\"}")
     p.add_argument("--window", type=int, default=None, help="tokens per window (default: the model's block_size)")
+    p.add_argument("--batch_size", type=int, default=None, help="2..8: score that many windows per batched step, as teacher-forced "
+                   "requests of continuous batching (default: one window at a time on the single-stream engine)")
     p.add_argument("--precision", choices=["fp16", "bf16"], default="fp16")
     p.add_argument("--device", type=str, default="cuda")
     return p
