@@ -346,7 +346,7 @@ __global__ __launch_bounds__(256) void batched_attention_kernel(const float* __r
                                                                 const float scale, const int* __restrict__ active) {
     const int b = blockIdx.z / groups, grp = blockIdx.z % groups;
     if constexpr (SLOTS) {
-        if (!((active[0] >> b) & 1)) return;  // workgroup-uniform
+        if (slot_off(active, b)) return;  // workgroup-uniform
     }
     const size_t seq_off = (size_t)b * n_kv * max_seq * HD;
     chunked_attention_body<BF16, HD, kBAttnMaxQ, kBatchMax, 1>(slabs, split, pos_ptr[b], rope, k_cache + seq_off, v_cache + seq_off, partials, 1,

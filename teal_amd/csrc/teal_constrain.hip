@@ -60,7 +60,7 @@ __global__ __launch_bounds__(1024) void constrain_logits_kernel(const uint16_t* 
                                                                  const uint32_t neg_maxf) {
     __shared__ uint32_t bitmap[kConstrainPerWg / 32];
     const int r = blockIdx.y;
-    if (active && !((active[0] >> (slot0 + r)) & 1)) return;  // (workgroup-uniform: before any barrier)
+    if (active && slot_off(active, slot0 + r)) return;  // (workgroup-uniform: before any barrier)
     const int tid = threadIdx.x;
     const int wg0 = blockIdx.x * kConstrainPerWg;
     const int e0 = wg0 + tid * 8;

@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) void batched_attention_kv8_kernel(const float*
                                                                     const int n_kv, const int hq, const int groups, const int max_seq,
                                                                     const float scale, const int* __restrict__ active) {
     const int b = blockIdx.z / groups, grp = blockIdx.z % groups;
-    if (!((active[0] >> b) & 1)) return;  // workgroup-uniform
+    if (slot_off(active, b)) return;  // workgroup-uniform
     const size_t row_off = (size_t)b * n_kv * max_seq;
     chunked_attention_body<BF16, HD, kBAttnMaxQ, kBatchMax, 1, true>(slabs, split, pos_ptr[b], rope, k_codes + row_off * HD,
                                                                      v_codes + row_off * HD, partials, 1, b, B, n_head, n_kv, hq, grp,

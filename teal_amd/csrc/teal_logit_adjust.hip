@@ -50,7 +50,7 @@ __global__ __launch_bounds__(1024) void logit_adjust_kernel(const uint16_t* __re
                                                              const uint16_t* __restrict__ bias, uint16_t* __restrict__ out,
                                                              const size_t out_stride, const int* __restrict__ active, const int slot0) {
     const int r = blockIdx.y;
-    if (active && !((active[0] >> (slot0 + r)) & 1)) return;
+    if (active && slot_off(active, slot0 + r)) return;
     const int e0 = (blockIdx.x * 1024 + threadIdx.x) * 8;
     if (e0 >= V) return;  // (V % 8 == 0: a thread's 8 elements are inside the row or all outside)
     const u32x4 lv = *reinterpret_cast<const u32x4*>(logits + (size_t)r * stride + e0);

@@ -18,7 +18,7 @@
 // the first is its maximum, which the max pass leaves behind; a round reduces the 1024 candidates to the winner, the thread that
 // owned it writes the entry and rescans its own vectors for its next one — one thread rescans per round, the other 1023
 // candidates stay valid (they lost to a larger one).
-#include "teal_common.h"
+#include "teal_draw.h"
 
 namespace teal {
 
@@ -156,7 +156,7 @@ __global__ __launch_bounds__(1024) void token_logprobs_kernel(const uint16_t* __
                                                                int* __restrict__ top_ids, float* __restrict__ top_lp,
                                                                const int* __restrict__ active, const int slot0) {
     const int r = blockIdx.x;
-    if (active && !((active[0] >> (slot0 + r)) & 1)) return;
+    if (active && slot_off(active, slot0 + r)) return;
     const unsigned long long c = rng_state[2 * r + 1];
     if (c == 0ull || c > (unsigned long long)lp_len) return;
     const size_t o = (size_t)r * lp_len + (size_t)(c - 1ull);

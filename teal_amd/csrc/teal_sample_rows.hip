@@ -9,7 +9,7 @@
 //   top_k   0 < k < V: every logit not below the k-th largest value (ties kept) -> the set K1
 //   top_p   < 1: over K1, w_i = expf(t_i), Z = sum w, A(v) = mass of the values above v: v stays iff A(v) < top_p * Z
 //   min_p   > 0: v stays iff expf(t) >= min_p
-//   race    argmax expf(t_i) / -logf(u_i) over what stayed — consider()'s fp32 expression of teal_sampler.hip, the same hash3
+//   race    argmax expf(t_i) / -logf(u_i) over what stayed — race_score's fp32 expression (teal_draw.h), the same hash3
 //           stream, the smallest index winning exact ties, and the same epilogue
 //
 // How: one workgroup of 1024 threads per row.  A thread loads its NV 16-byte vectors once and keeps the order-preserving 16-bit
@@ -29,7 +29,7 @@
 // to a guess.
 //
 // min_p needs no pivot: it is one comparison on the race's own expf(t_i).
-#include "teal_common.h"
+#include "teal_draw.h"
 
 namespace teal {
 
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const uint16_t* __res
                                                             const int history_len, int* __restrict__ kept_out,
                                                             const int* __restrict__ active, const int slot0) {
     const int r = blockIdx.x;
-    if (active && !((active[0] >> (slot0 + r)) & 1)) return;  // (workgroup-uniform: before any barrier, load or store)
+    if (active && slot_off(active, slot0 + r)) return;  // (workgroup-uniform: before any barrier, load or store)
     __shared__ u64 hist[256];
     __shared__ u64 whist[16][256];  // per-wave sub-histograms (sample_full's reason: the keys cluster in a few bins)
     __shared__ u64 sel[2];
@@ -111,8 +111,7 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const uint16_t* __res
     kmax = (uint32_t)ired[0];
 #pragma unroll
     for (int w = 1; w < 16; ++w) kmax = max(kmax, (uint32_t)ired[w]);
-    auto key_bits = [](const uint32_t k) -> uint32_t { return (k & 0x8000u) ? (k ^ 0x8000u) : (~k & 0xFFFFu); };  // order_key16^-1
-    const float mx = bits_to_float(key_bits(kmax), BF16);
+    const float mx = bits_to_float(key_bits16(kmax), BF16);
     // f(key, vocabulary index) for every key this thread holds
     auto for_keys = [&](auto f) {
 #pragma unroll
@@ -134,12 +133,7 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const uint16_t* __res
     };
     auto merge_hist = [&]() {  // whist[16][256] -> hist[256]; barriers on both sides
         __syncthreads();
-        if (tid < 256) {
-            u64 a = 0ull;
-#pragma unroll
-            for (int w = 0; w < 16; ++w) a += whist[w][tid];
-            hist[tid] = a;
-        }
+        merge_whist(whist, hist, tid);
         __syncthreads();
     };
     // the smallest d = kmax - key at which the cumulative weight reaches the need; weight(key, d) == 0: the key takes no part
@@ -172,36 +166,34 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const uint16_t* __res
         const uint32_t dk = dmax;
         const uint32_t dp = select_d([&](const uint32_t key, const uint32_t d) -> u64 {
             if (d > dk) return 0ull;
-            return (u64)(expf((bits_to_float(key_bits(key), BF16) - mx) * inv_temp) * kMassScale);
+            return (u64)(expf((bits_to_float(key_bits16(key), BF16) - mx) * inv_temp) * kMassScale);
         }, 0ull, (double)top_p);
         dmax = min(dk, dp);
     }
-    // exponential race over what stayed: consider() of teal_sampler.hip, term for term
+    // exponential race over what stayed: race_score and race_take (teal_draw.h), as in every sampler
     const uint32_t seed = (uint32_t)seed64, ctr = (uint32_t)ctr64;
     float best = -1.0f;
     int besti = 0x7FFFFFFF, kept = 0;
     for_keys([&](const uint32_t key, const int i) {
         if (kmax - key > dmax) return;
-        const float pnum = expf((bits_to_float(key_bits(key), BF16) - mx) * inv_temp);
+        const float pnum = expf((bits_to_float(key_bits16(key), BF16) - mx) * inv_temp);
         if (!(pnum >= min_p)) return;
         ++kept;
-        const float u = ((float)(hash3(seed, ctr, (uint32_t)i) >> 8) + 0.5f) * (1.0f / 16777216.0f);
-        const float scv = pnum / (-logf(u));
-        if (scv > best || (scv == best && i < besti)) { best = scv; besti = i; }
+        race_take(best, besti, race_score(pnum, seed, ctr, i), i);
     });
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
         const float ob = __shfl_xor(best, d);
         const int oi = __shfl_xor(besti, d);
         kept += __shfl_xor(kept, d);
-        if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
+        race_take(best, besti, ob, oi);
     }
     __syncthreads();
     if (lane == 0) { fred[wave] = best; ired[wave] = besti; kred[wave] = kept; }
     __syncthreads();
     if (tid == 0) {
         for (int w = 1; w < 16; ++w) {
-            if (fred[w] > best || (fred[w] == best && ired[w] < besti)) { best = fred[w]; besti = ired[w]; }
+            if (fred[w] > best || (fred[w] == best && ired[w] < besti)) { best = fred[w]; besti = ired[w]; }  // race_take, written out
             kept += kred[w];
         }
         tokens[r] = besti;

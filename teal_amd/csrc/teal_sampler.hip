@@ -1,6 +1,6 @@
 // teal_sampler.hip — the fused top-k sampler and its C-ABI entry points (include/teal_hip.h).
 //   gpt-fast/generate.py:49-66  logits_to_probs + multinomial_sample_one -> sample_topk*_kernel
-#include "teal_common.h"
+#include "teal_draw.h"
 
 namespace teal {
 
@@ -12,7 +12,7 @@ namespace teal {
 // index); the draw counter lives on the device and is bumped by the kernel, so hipGraph replays
 // draw fresh numbers.  Token streams are not pinned by the reference (they depend on torch's RNG).
 // ------------------------------------------------------------------------------------------------
-// (order_key16, hash3 and select_bin live in teal_common.h: the speculative accept kernel draws from the same stream)
+// (the random stream, the selection helpers and the race's score and comparison live in teal_draw.h: every sampling kernel shares them)
 
 template <bool BF16>
 __device__ __forceinline__ void sample_full(const uint16_t* __restrict__ logits, const int V, const int top_k,
@@ -25,7 +25,6 @@ __device__ __forceinline__ void sample_full(const uint16_t* __restrict__ logits,
     __shared__ float fred[16];
     __shared__ int ired[16];
     __shared__ unsigned int sel[2];
-    __shared__ unsigned int suf[256];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool filter = top_k > 0 && top_k < V;
     const int V8 = V >> 3;  // 16-byte vectors (vocab sizes are multiples of 8; the tail is handled scalar)
@@ -55,19 +54,14 @@ __device__ __forceinline__ void sample_full(const uint16_t* __restrict__ logits,
     for (int d = 32; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
     if (lane == 0) fred[wave] = mx;
     __syncthreads();
-    if (tid < 256) {
-        unsigned int a = 0;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) a += whist[w][tid];
-        hist[tid] = a;
-    }
+    merge_whist(whist, hist, tid);
     __syncthreads();
     mx = fred[0];
 #pragma unroll
     for (int w = 1; w < 16; ++w) mx = fmaxf(mx, fred[w]);
     if (filter) {
         // suffix counts over the 256 bins (parallel scan), then the bin holding the top_k-th key
-        select_bin(hist, suf, sel, (unsigned int)top_k, tid);
+        select_bin(hist, sel, (unsigned int)top_k, tid);
         __syncthreads();
         const unsigned int hb = sel[0], need2 = sel[1];
         __syncthreads();
@@ -88,14 +82,9 @@ __device__ __forceinline__ void sample_full(const uint16_t* __restrict__ logits,
             if ((k >> 8) == hb) atomicAdd(&whist[wave][k & 0xFFu], 1u);
         }
         __syncthreads();
-        if (tid < 256) {
-            unsigned int a = 0;
-#pragma unroll
-            for (int w = 0; w < 16; ++w) a += whist[w][tid];
-            hist[tid] = a;
-        }
+        merge_whist(whist, hist, tid);
         __syncthreads();
-        select_bin(hist, suf, sel, need2, tid);
+        select_bin(hist, sel, need2, tid);
         if (tid == 0) sel[0] = (hb << 8) | sel[0];
         __syncthreads();
         pivot_key = sel[0];
@@ -108,9 +97,7 @@ __device__ __forceinline__ void sample_full(const uint16_t* __restrict__ logits,
     auto consider = [&](const uint32_t b, const int i) {
         if (filter && order_key16(b, BF16) < pivot_key) return;
         const float pnum = expf((bits_to_float(b, BF16) - mx) * inv_temp);
-        const float u = ((float)(hash3(seed, ctr, (uint32_t)i) >> 8) + 0.5f) * (1.0f / 16777216.0f);
-        const float scv = pnum / (-logf(u));
-        if (scv > best || (scv == best && i < besti)) { best = scv; besti = i; }
+        race_take(best, besti, race_score(pnum, seed, ctr, i), i);
     };
     for (int i = tid; i < V8; i += 1024) {
         const u32x4 w = lv[i];
@@ -125,14 +112,14 @@ __device__ __forceinline__ void sample_full(const uint16_t* __restrict__ logits,
     for (int d = 32; d >= 1; d >>= 1) {
         const float ob = __shfl_xor(best, d);
         const int oi = __shfl_xor(besti, d);
-        if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
+        race_take(best, besti, ob, oi);
     }
     __syncthreads();
     if (lane == 0) { fred[wave] = best; ired[wave] = besti; }
     __syncthreads();
     if (tid == 0) {
         for (int w = 1; w < 16; ++w)
-            if (fred[w] > best || (fred[w] == best && ired[w] < besti)) { best = fred[w]; besti = ired[w]; }
+            if (fred[w] > best || (fred[w] == best && ired[w] < besti)) { best = fred[w]; besti = ired[w]; }  // race_take, written out
         token_out[0] = besti;
         const unsigned long long c = rng_state[1];
         if (history && (long long)c < (long long)history_len) history[c] = besti;
@@ -150,9 +137,7 @@ __global__ __launch_bounds__(1024) void sample_topk_kernel(const uint16_t* __res
     sample_full<BF16>(logits, V, top_k, inv_temp, rng_state, token_out, pos_inout, history, history_len);
 }
 
-// the slot-predicated forms (teal_sample_topk_slot): bit `slot` of active[0] clear -> the whole launch exits before it reads or
-// writes anything else
-__device__ __forceinline__ bool slot_off(const int* __restrict__ active, const int slot) { return !((active[0] >> slot) & 1); }
+// the slot-predicated forms (teal_sample_topk_slot): slot_off -> the whole launch exits before it reads or writes anything else
 
 template <bool BF16>
 __global__ __launch_bounds__(1024) void sample_topk_slot_kernel(const uint16_t* __restrict__ logits, const int V,
@@ -222,17 +207,11 @@ __device__ __forceinline__ void sample_window_body(const uint16_t* __restrict__ 
     kmax = (uint32_t)ired[0];
 #pragma unroll
     for (int w = 1; w < 16; ++w) kmax = max(kmax, (uint32_t)ired[w]);
-    auto key_bits = [](const uint32_t k) -> uint32_t { return (k & 0x8000u) ? (k ^ 0x8000u) : (~k & 0xFFFFu); };  // order_key16^-1
-    const float mx = bits_to_float(key_bits(kmax), BF16);
+    const float mx = bits_to_float(key_bits16(kmax), BF16);
     stamp_s(1);
     auto merge_hist = [&]() {  // whist[16][256] -> hist[256]; barriers on both sides
         __syncthreads();
-        if (tid < 256) {
-            unsigned int a = 0;
-#pragma unroll
-            for (int w = 0; w < 16; ++w) a += whist[w][tid];
-            hist[tid] = a;
-        }
+        merge_whist(whist, hist, tid);
         __syncthreads();
     };
     uint32_t pivot_key = 0u;  // keep keys >= pivot_key
@@ -261,7 +240,7 @@ __device__ __forceinline__ void sample_window_body(const uint16_t* __restrict__ 
                 inwin = (unsigned int)(fred[0] + fred[1] + fred[2] + fred[3]);
             }
             if (inwin >= (unsigned int)top_k || sh == 8) {
-                select_bin(hist, nullptr, sel, (unsigned int)top_k, tid);
+                select_bin(hist, sel, (unsigned int)top_k, tid);
                 const unsigned int d = 255u - sel[0], need2 = sel[1];
                 __syncthreads();
                 if (sh == 0) {
@@ -283,7 +262,7 @@ __device__ __forceinline__ void sample_window_body(const uint16_t* __restrict__ 
                         }
                     }
                     merge_hist();
-                    select_bin(hist, nullptr, sel, need2, tid);
+                    select_bin(hist, sel, need2, tid);
                     pivot_key = kmax - ((d << sh) | (255u - sel[0]));
                     __syncthreads();
                 }
@@ -294,16 +273,14 @@ __device__ __forceinline__ void sample_window_body(const uint16_t* __restrict__ 
         }
     }
     stamp_s(2);
-    // exponential race over the kept set (see sample_topk_kernel)
+    // exponential race over the kept set (teal_draw.h)
     const uint32_t seed = (uint32_t)seed64, ctr = (uint32_t)ctr64;
     float best = -1.0f;
     int besti = 0x7FFFFFFF;
     auto consider = [&](const uint32_t key, const int i) {
         if (key < pivot_key) return;
-        const float pnum = expf((bits_to_float(key_bits(key), BF16) - mx) * inv_temp);
-        const float u = ((float)(hash3(seed, ctr, (uint32_t)i) >> 8) + 0.5f) * (1.0f / 16777216.0f);
-        const float scv = pnum / (-logf(u));
-        if (scv > best || (scv == best && i < besti)) { best = scv; besti = i; }
+        const float pnum = expf((bits_to_float(key_bits16(key), BF16) - mx) * inv_temp);
+        race_take(best, besti, race_score(pnum, seed, ctr, i), i);
     };
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
@@ -321,14 +298,14 @@ __device__ __forceinline__ void sample_window_body(const uint16_t* __restrict__ 
     for (int d = 32; d >= 1; d >>= 1) {
         const float ob = __shfl_xor(best, d);
         const int oi = __shfl_xor(besti, d);
-        if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
+        race_take(best, besti, ob, oi);
     }
     __syncthreads();
     if (lane == 0) { fred[wave] = best; ired[wave] = besti; }
     __syncthreads();
     if (tid == 0) {
         for (int w = 1; w < 16; ++w)
-            if (fred[w] > best || (fred[w] == best && ired[w] < besti)) { best = fred[w]; besti = ired[w]; }
+            if (fred[w] > best || (fred[w] == best && ired[w] < besti)) { best = fred[w]; besti = ired[w]; }  // race_take, written out
         token_out[0] = besti;
         if (history && (long long)ctr64 < (long long)history_len) history[ctr64] = besti;
         rng_state[1] = ctr64 + 1ull;
@@ -386,12 +363,7 @@ __device__ __forceinline__ uint32_t window_pivot(const uint32_t (&keys)[NK], con
     const int lane = tid & 63, wave = tid >> 6;
     auto merge_hist = [&]() {
         __syncthreads();
-        if (tid < 256) {
-            unsigned int a = 0;
-#pragma unroll
-            for (int w = 0; w < 16; ++w) a += whist[w][tid];
-            hist[tid] = a;
-        }
+        merge_whist(whist, hist, tid);
         __syncthreads();
     };
     uint32_t pivot_key = 0u;
@@ -414,7 +386,7 @@ __device__ __forceinline__ uint32_t window_pivot(const uint32_t (&keys)[NK], con
             inwin = (unsigned int)(fred[0] + fred[1] + fred[2] + fred[3]);
         }
         if (inwin >= top_k || sh == 8) {
-            select_bin(hist, nullptr, sel, top_k, tid);
+            select_bin(hist, sel, top_k, tid);
             const unsigned int d = 255u - sel[0], need2 = sel[1];
             __syncthreads();
             if (sh == 0) {
@@ -432,7 +404,7 @@ __device__ __forceinline__ uint32_t window_pivot(const uint32_t (&keys)[NK], con
                     if (((valid >> j) & 1u) && (e >> sh) == d) atomicAdd(&whist[wave][255u - (e & lowmask)], 1u);
                 }
                 merge_hist();
-                select_bin(hist, nullptr, sel, need2, tid);
+                select_bin(hist, sel, need2, tid);
                 pivot_key = kmax - ((d << sh) | (255u - sel[0]));
                 __syncthreads();
             }
@@ -552,8 +524,7 @@ __device__ __forceinline__ void sample_multi_body(const uint16_t* __restrict__ l
     }
     gmax = block_max_u32(gmax, ired, tid);
     const uint32_t pivot = window_pivot<BF16, NC>(ck, cvalid, gmax, (unsigned int)top_k, hist, whist, fred, sel, tid);
-    auto key_bits = [](const uint32_t k) -> uint32_t { return (k & 0x8000u) ? (k ^ 0x8000u) : (~k & 0xFFFFu); };  // order_key16^-1
-    const float mx = bits_to_float(key_bits(gmax), BF16);
+    const float mx = bits_to_float(key_bits16(gmax), BF16);
     const uint32_t seed = (uint32_t)seed64, ctr = (uint32_t)ctr64;
     float best = -1.0f;
     int besti = 0x7FFFFFFF;
@@ -561,24 +532,22 @@ __device__ __forceinline__ void sample_multi_body(const uint16_t* __restrict__ l
     for (int j = 0; j < NC; ++j) {
         if (((cvalid >> j) & 1u) && ck[j] >= pivot) {
             const int i = (int)ci[j];
-            const float pnum = expf((bits_to_float(key_bits(ck[j]), BF16) - mx) * inv_temp);
-            const float u = ((float)(hash3(seed, ctr, (uint32_t)i) >> 8) + 0.5f) * (1.0f / 16777216.0f);
-            const float scv = pnum / (-logf(u));
-            if (scv > best || (scv == best && i < besti)) { best = scv; besti = i; }
+            const float pnum = expf((bits_to_float(key_bits16(ck[j]), BF16) - mx) * inv_temp);
+            race_take(best, besti, race_score(pnum, seed, ctr, i), i);
         }
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
         const float ob = __shfl_xor(best, d);
         const int oi = __shfl_xor(besti, d);
-        if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
+        race_take(best, besti, ob, oi);
     }
     __syncthreads();
     if (lane == 0) { fred[wave] = best; ired[wave] = besti; }
     __syncthreads();
     if (tid == 0) {
         for (int w = 1; w < 16; ++w)
-            if (fred[w] > best || (fred[w] == best && ired[w] < besti)) { best = fred[w]; besti = ired[w]; }
+            if (fred[w] > best || (fred[w] == best && ired[w] < besti)) { best = fred[w]; besti = ired[w]; }  // race_take, written out
         token_out[0] = besti;
         if (history && (long long)ctr64 < (long long)history_len) history[ctr64] = besti;
         rng_state[1] = ctr64 + 1ull;

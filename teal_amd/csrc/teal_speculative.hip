@@ -10,6 +10,7 @@
 // Everything that decides the round stays on the device: the accepted count, the emitted tokens, the next round's position
 // and input token.  The draw convention is in include/teal_hip.h (teal_spec_accept).
 #include "teal_chunked_attention.h"
+#include "teal_draw.h"
 
 namespace teal {
 
@@ -46,8 +47,6 @@ struct RowStats {
     float pad;
 };
 
-__device__ __forceinline__ float uniform01(const uint32_t h) { return ((float)(h >> 8) + 0.5f) * (1.0f / 16777216.0f); }
-
 template <bool BF16>
 __device__ __forceinline__ float row_prob(const uint16_t* __restrict__ row, const RowStats& st, const float inv_temp, const int v) {
     const uint32_t b = row[v];
@@ -68,8 +67,8 @@ __global__ __launch_bounds__(256) void spec_round_logits_kernel(const float* __r
         if (t < T) tl[(size_t)t * V + col] = float_to_bits<BF16>(r[t]);
 }
 
-// one workgroup per row: rows 0 .. k are the target's (tl), rows k+1 .. 2k the draft's (dl).  The top-k pivot is the fused
-// sampler's exact two-pass radix select on the 16-bit keys.
+// one workgroup per row: rows 0 .. k are the target's (tl), rows k+1 .. 2k the draft's (dl).  The top-k pivot is sample_full's
+// exact two-pass radix select on the 16-bit keys (select_bin and merge_whist of teal_draw.h), restated over a scalar walk.
 template <bool BF16>
 __global__ __launch_bounds__(1024) void spec_row_stats_kernel(const uint16_t* __restrict__ tl, const uint16_t* __restrict__ dl, const int V,
                                                               const int k, const int top_k, const float inv_temp, RowStats* __restrict__ stats) {
@@ -91,19 +90,14 @@ __global__ __launch_bounds__(1024) void spec_row_stats_kernel(const uint16_t* __
     mx = wave_max_f(mx);
     if (lane == 0) fred[wave] = mx;
     __syncthreads();
-    if (tid < 256) {
-        unsigned int a = 0;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) a += whist[w][tid];
-        hist[tid] = a;
-    }
+    merge_whist(whist, hist, tid);
     __syncthreads();
     mx = fred[0];
 #pragma unroll
     for (int w = 1; w < 16; ++w) mx = fmaxf(mx, fred[w]);
     uint32_t pivot = 0;
     if (filter) {
-        select_bin(hist, nullptr, sel, (unsigned int)top_k, tid);
+        select_bin(hist, sel, (unsigned int)top_k, tid);
         const unsigned int hb = sel[0], need2 = sel[1];
         __syncthreads();
         for (int i = tid; i < 16 * 256; i += 1024) (&whist[0][0])[i] = 0;
@@ -113,14 +107,9 @@ __global__ __launch_bounds__(1024) void spec_row_stats_kernel(const uint16_t* __
             if ((kk >> 8) == hb) atomicAdd(&whist[wave][kk & 0xFFu], 1u);
         }
         __syncthreads();
-        if (tid < 256) {
-            unsigned int a = 0;
-#pragma unroll
-            for (int w = 0; w < 16; ++w) a += whist[w][tid];
-            hist[tid] = a;
-        }
+        merge_whist(whist, hist, tid);
         __syncthreads();
-        select_bin(hist, nullptr, sel, need2, tid);
+        select_bin(hist, sel, need2, tid);
         pivot = (hb << 8) | sel[0];
         __syncthreads();
     }
@@ -186,6 +175,7 @@ __global__ __launch_bounds__(1024) void spec_decide_kernel(const uint16_t* __res
     for (int o = 32; o >= 1; o >>= 1) {
         const float ob = __shfl_xor(best, o), obq = __shfl_xor(bestq, o);
         const int oi = __shfl_xor(besti, o), oiq = __shfl_xor(bestqi, o);
+        // race_take (teal_draw.h) for each of the two pairs, spelled out: as calls they reorder this kernel's compares
         if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
         if (obq > bestq || (obq == bestq && oiq < bestqi)) { bestq = obq; bestqi = oiq; }
     }
@@ -193,6 +183,7 @@ __global__ __launch_bounds__(1024) void spec_decide_kernel(const uint16_t* __res
     __syncthreads();
     if (tid == 0) {
         for (int w = 1; w < 16; ++w) {
+            // (race_take, written out for both pairs)
             if (fb[0][w] > best || (fb[0][w] == best && ib[0][w] < besti)) { best = fb[0][w]; besti = ib[0][w]; }
             if (fb[1][w] > bestq || (fb[1][w] == bestq && ib[1][w] < bestqi)) { bestq = fb[1][w]; bestqi = ib[1][w]; }
         }
