@@ -784,6 +784,33 @@ int teal_batched_decode_attention_slots_kv8(const float* qkv_slabs, int split, c
                                             size_t partials_bytes, int B, int n_head, int n_kv_head, int head_dim, int max_seq, int dtype,
                                             void* stream);
 
+/* ---- stream attention of the batched / slot step, teal_amd/csrc/teal_stream_attention.hip -----------------------------------
+ * A second split-KV body for one new token per sequence against a long cache (teal_stream_attention.h has the design): a lane
+ * owns 8 features of a cache row, hd / 8 adjacent lanes are one online-softmax stream held in registers, and the loop over the
+ * cached rows has no LDS staging and no barrier.  Opt-in (BatchedDecodeEngine(attention="stream")): the chunked entries above
+ * stay the default and are unchanged.
+ *
+ * teal_batched_decode_attention's contract on 16-bit caches when active == NULL (every slot b < B), and
+ * teal_batched_decode_attention_slots' otherwise (an inactive slot writes nothing and its yt slot is zero): sequence b at
+ * p_b = clamp(pos[b], 0, max_seq - 1) attends its cache rows 0 .. p_b - 1 and its new row, built from slot b of the wqkv slabs
+ * (slices summed in order from +0, rounded; RoPE at p_b, rounded) and stored as row p_b — the very words the chunked launch
+ * stores.  Scores are round16(q . k / sqrt(hd)) as there; sums are fp32 in another order, so yt agrees with the chunked launch
+ * to rounding, not bit for bit.  For a given B and geometry a sequence's yt words depend on its own inputs alone: not on its
+ * slot, its neighbours or the active word, and a replay repeats them.  partials: teal_batched_decode_attention_ws_bytes sizes
+ * them; the layout and the merge launch are the chunked launch's.  At most 8 query heads of a KV head share a workgroup (the
+ * largest divisor of n_head / n_kv_head that is <= 8).  Errors: the chunked entries' (TEAL_ERR_ARG, _DTYPE, _SHAPE, _ALIGN,
+ * _NO_DEVICE, _WORKSPACE), every one before any launch. */
+int teal_batched_decode_attention_stream(const float* qkv_slabs, int split, const void* rope, const int32_t* pos, const int32_t* active,
+                                         void* k_cache, void* v_cache, void* yt, float* partials, size_t partials_bytes, int B, int n_head,
+                                         int n_kv_head, int head_dim, int max_seq, int dtype, void* stream);
+/* The same on the fp8 caches of teal_batched_decode_attention_slots_kv8 (active may be NULL here too).  Cached rows enter as
+ * float(code) * scale, the new row is attended unquantised and stored by the rule: yt holds the words
+ * teal_batched_decode_attention_stream leaves on 16-bit caches that hold the dequantised values.  TEAL_ERR_ARG also for null scales. */
+int teal_batched_decode_attention_stream_kv8(const float* qkv_slabs, int split, const void* rope, const int32_t* pos, const int32_t* active,
+                                             void* k_codes, void* v_codes, float* k_scales, float* v_scales, void* yt, float* partials,
+                                             size_t partials_bytes, int B, int n_head, int n_kv_head, int head_dim, int max_seq, int dtype,
+                                             void* stream);
+
 /* ---- benchmark comparator (scripts/benchmark_gemv.py only; not on the decode path) ----------- */
 
 /* The Deja Vu gather GEMV the reference's kernel benchmark plots next to TEAL's (scripts/benchmark_gemv.py:32-107,170-172),

@@ -1,6 +1,6 @@
 // teal_kv8.h — the fp8 KV-cache row format of continuous batching (include/teal_hip.h, "fp8 KV cache"): the device side of
 // the rule, typed once for the two places that write a row (teal_kv8_quantize_rows and the batched attention's single writer) and
-// the one that reads it (the staging loop of teal_chunked_attention.h).
+// the two that read it (the staging loop of teal_chunked_attention.h, the lane load of teal_stream_attention.h).
 //
 // A row x[0 .. hd) of one KV head, 16-bit values widened exactly to fp32, is hd OCP e4m3fn codes and one fp32 scale 2^e:
 //   a = max |x_d|;  e = 0 if a == 0, else the smallest integer with a * 2^-e <= 448, clamped below at -100;
@@ -55,6 +55,17 @@ __device__ __forceinline__ void kv8_store_row(const float (&x)[8], uint8_t* __re
 __device__ __forceinline__ void kv8_dequant16(const u32x4 w, const float scale, float (&out)[16]) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
+        const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[j], false);
+        const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[j], true);
+        out[4 * j] = lo[0] * scale; out[4 * j + 1] = lo[1] * scale;
+        out[4 * j + 2] = hi[0] * scale; out[4 * j + 3] = hi[1] * scale;
+    }
+}
+
+// 8 codes (one 8-byte load, in memory order) times their row's scale: the stream body's lane (teal_stream_attention.h)
+__device__ __forceinline__ void kv8_dequant8(const u32x2 w, const float scale, float (&out)[8]) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
         const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[j], false);
         const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[j], true);
         out[4 * j] = lo[0] * scale; out[4 * j + 1] = lo[1] * scale;

@@ -30,7 +30,7 @@ from . import forcing as FT
 from . import logit_processors as PR
 from . import sampling as SM
 from . import stopping as ST
-from .engine_features import SamplerFeatures, _SlotCaches, dense_16bit_refusal, kv_cache_refusal, slab_chain_refusal
+from .engine_features import SamplerFeatures, _SlotCaches, attention_refusal, dense_16bit_refusal, kv_cache_refusal, slab_chain_refusal
 from .model import Transformer
 from .prefill import MAX_T, PrefillEngine, PrefillIn, SlabChain
 from .speculative import VerifyPass
@@ -80,11 +80,16 @@ class BatchedDecodeEngine(SlabChain, SamplerFeatures):
             return f"batch size {B} outside 1..{BATCH_MAX} (setup_caches(max_batch_size=B))"
         return None
 
-    def __init__(self, model: Transformer, thresholds: List[Dict[str, float]], batch: int, kv_cache: Optional[str] = None):
-        why = kv_cache_refusal(self._kv_kind, kv_cache)
+    def __init__(self, model: Transformer, thresholds: List[Dict[str, float]], batch: int, kv_cache: Optional[str] = None,
+                 attention: str = "chunked"):
+        """attention: the split-KV body of the step's attention launch, for the engine's life.  "chunked" (the default): every
+        launch as without the keyword.  "stream": teal_batched_decode_attention_stream[_kv8], the barrier-free body for one new
+        token against a long cache (same caches, partials and merge; yt agrees with the chunked body to rounding)."""
+        why = kv_cache_refusal(self._kv_kind, kv_cache) or attention_refusal(self._kv_kind, attention)
         if why is not None:
             raise ValueError(f"{type(self).__name__}: {why}")
         self.kv_cache = kv_cache
+        self.attention = attention or "chunked"
         why = BatchedDecodeEngine.supports(model)
         if why is not None:
             raise ValueError(f"BatchedDecodeEngine cannot run this model: {why}")
@@ -153,7 +158,9 @@ class BatchedDecodeEngine(SlabChain, SamplerFeatures):
         head = (A.data_ptr(), ns, self.rope.data_ptr(), self.pos_buf.data_ptr())
         tail = (at.kv_cache.k_cache.data_ptr(), at.kv_cache.v_cache.data_ptr(), self.yt.data_ptr(), self.partials.data_ptr(),
                 self.partials.numel() * 4, self.B, cfg.n_head, cfg.n_local_heads, cfg.head_dim, self.max_seq, self.code, st)
-        if self._active is None:
+        if self.attention == "stream":
+            rc, what = self.L.teal_batched_decode_attention_stream(*head, self._active, *tail), "teal_batched_decode_attention_stream"
+        elif self._active is None:
             rc, what = self.L.teal_batched_decode_attention(*head, *tail), "teal_batched_decode_attention"
         else:
             rc, what = self.L.teal_batched_decode_attention_slots(*head, self._active, *tail), "teal_batched_decode_attention_slots"
@@ -403,8 +410,10 @@ class SlotDecodeEngine(BatchedDecodeEngine):
                    f"left: setup_caches(max_batch_size=1), not {cache_b} (the engine owns the slots' fp8 rows)")
         return why
 
-    def __init__(self, model: Transformer, thresholds: List[Dict[str, float]], batch: int, kv_cache: Optional[str] = None):
-        """kv_cache None: the B slots are the model's own [B, n_kv, max_seq, hd] caches — every launch and allocation as without the
+    def __init__(self, model: Transformer, thresholds: List[Dict[str, float]], batch: int, kv_cache: Optional[str] = None,
+                 attention: str = "chunked"):
+        """attention: BatchedDecodeEngine's keyword, for both cache formats.
+        kv_cache None: the B slots are the model's own [B, n_kv, max_seq, hd] caches — every launch and allocation as without the
         keyword.  "fp8": the engine owns the slots' K / V as e4m3fn codes [B, n_kv, max_seq, hd] and power-of-two scales
         [B, n_kv, max_seq] per layer (include/teal_hip.h, "fp8 KV cache"); the model's caches, batch 1, are the staging cache every
         prompt pass writes, and one teal_kv8_quantize_rows launch per admission moves the prompt's rows into the slot.  A row is
@@ -413,7 +422,7 @@ class SlotDecodeEngine(BatchedDecodeEngine):
             why = SlotDecodeEngine.supports(model, kv_cache=kv_cache)
             if why is not None:
                 raise ValueError(f"SlotDecodeEngine cannot run this model: {why}")
-        super().__init__(model, thresholds, batch, kv_cache)
+        super().__init__(model, thresholds, batch, kv_cache, attention)
         dev = self.logits.device
         self.slot_state = torch.zeros(SLOT_WORDS, dtype=torch.int32, device=dev)
         self.slot_state[SLOT_EOS:SLOT_EOS + 8] = -1
@@ -454,12 +463,14 @@ class SlotDecodeEngine(BatchedDecodeEngine):
             return super()._attention(at, A, ns, st)
         cfg = self.cfg
         kc, vc, ks, vs = self.kv8[self._kv8_of[id(at)]]
-        rc = self.L.teal_batched_decode_attention_slots_kv8(
+        stream = self.attention == "stream"
+        entry = self.L.teal_batched_decode_attention_stream_kv8 if stream else self.L.teal_batched_decode_attention_slots_kv8
+        rc = entry(
             A.data_ptr(), ns, self.rope.data_ptr(), self.pos_buf.data_ptr(), self._active, kc.data_ptr(), vc.data_ptr(), ks.data_ptr(),
             vs.data_ptr(), self.yt.data_ptr(), self.partials.data_ptr(), self.partials.numel() * 4, self.B, cfg.n_head, cfg.n_local_heads,
             cfg.head_dim, self.max_seq, self.code, st)
         if rc != 0:
-            _lib.check(rc, "teal_batched_decode_attention_slots_kv8")
+            _lib.check(rc, "teal_batched_decode_attention_stream_kv8" if stream else "teal_batched_decode_attention_slots_kv8")
 
     def _quantize_rows(self, s: int, rows: int):
         """rows 0 .. rows-1 of the staging cache (every layer's K and V) into slot s's codes and scales: one launch"""

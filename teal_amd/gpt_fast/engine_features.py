@@ -110,6 +110,25 @@ def kv_cache_refusal(kind: str, kv_cache: Optional[str]) -> Optional[str]:
     return None
 
 
+# BatchedDecodeEngine(attention=): the split-KV body of the step's attention launch.  "chunked": teal_chunked_attention.h, the
+# default; "stream": teal_stream_attention.h, the barrier-free body for one new token against a long cache (opt-in)
+ATTENTION_BODIES = ("chunked", "stream")
+
+
+def attention_refusal(kind: str, attention: Optional[str]) -> Optional[str]:
+    """why the `kind` engine ("slot", "batched", "decode", "speculative", "tensor-parallel") cannot take attention=, or None.  The
+    stream body replaces the chunked body of the batched / slot step only: every other path attends through teal_attention.hip or
+    the verify pass, which have one body each."""
+    if attention in (None, "chunked"):
+        return None
+    if attention not in ATTENTION_BODIES:
+        return f"unknown attention {attention!r} (one of {', '.join(map(repr, ATTENTION_BODIES))})"
+    if kind not in ("slot", "batched"):
+        return (f"attention={attention!r} is the batched step's (BatchedDecodeEngine, SlotDecodeEngine): the {kind} path attends "
+                "through teal_attention.hip or the verify pass, which have no second body")
+    return None
+
+
 class _SlotCaches:
     """the K / V base pointers of slot `slot` of batch-B caches: slot s of a contiguous [B, n_kv, max_seq, hd] cache is itself a
     contiguous [1, n_kv, max_seq, hd] cache"""

@@ -744,6 +744,24 @@ def check_kv_cache_args(args) -> Optional[str]:
     return None if fmt == "model" else fmt
 
 
+def check_attention_args(args) -> str:
+    """--attention: the engines' keyword ("chunked", the default, or "stream"); refused here, before anything is loaded, anywhere but
+    under --batch_size > 1 or --requests: the stream body is the batched step's, and the other decode paths have one body each"""
+    from teal_amd.gpt_fast.engine_features import attention_refusal
+    body = getattr(args, "attention", "chunked") or "chunked"
+    batched = int(getattr(args, "batch_size", 1) or 1) > 1 or getattr(args, "requests", None) is not None
+    if getattr(args, "draft_checkpoint_path", None) is not None or getattr(args, "self_speculate", False):
+        kind = "speculative"
+    elif int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1"))) > 1:
+        kind = "tensor-parallel"
+    else:
+        kind = "batched" if batched else "decode"
+    why = attention_refusal(kind, body)
+    if why is not None:
+        raise SystemExit(f"--attention {body}: {why} (it needs --batch_size > 1 or --requests)")
+    return body
+
+
 def _mean_logprob_line(lps) -> str:
     return f"    mean logprob {sum(lps) / max(1, len(lps)):.4f} over {len(lps)} tokens (model distribution, temperature 1)"
 
@@ -763,7 +781,7 @@ def run_batched(args, model: Transformer, thresholds, prompts: torch.Tensor, tok
         from teal_amd.gpt_fast.batched import BatchedDecodeEngine
         why = BatchedDecodeEngine.supports(model)
         if why is None:
-            eng = BatchedDecodeEngine(model, thresholds, B)
+            eng = BatchedDecodeEngine(model, thresholds, B, attention=check_attention_args(args))
         else:
             print(f"batched engine not used: {why}")
     n_lp = getattr(args, "logprobs", None)
@@ -968,7 +986,7 @@ def run_continuous(args, model: Transformer, thresholds, tokenizer, request_line
     why = SlotDecodeEngine.supports(model, kv_cache=kv_cache)
     if why is not None:
         raise SystemExit(f"--requests: the batched engine cannot run this model: {why}")
-    eng = SlotDecodeEngine(model, thresholds, B, kv_cache=kv_cache)
+    eng = SlotDecodeEngine(model, thresholds, B, kv_cache=kv_cache, attention=check_attention_args(args))
     kvb = eng.kv_cache_bytes()
     print(f"KV cache ({'model' if kv_cache is None else kv_cache}): {kvb['staging'] / 1e6:.2f} MB 16-bit "
           f"({'the slots' if kv_cache is None else 'the staging cache'}), {kvb['codes'] / 1e6:.2f} MB codes, {kvb['scales'] / 1e6:.2f} MB scales")
@@ -1037,6 +1055,7 @@ def main(args) -> Dict:
     samp = check_sampling_args(args)
     check_stop_args(args)
     check_kv_cache_args(args)
+    check_attention_args(args)
     if getattr(args, "prefixes", None) is not None and getattr(args, "requests", None) is None:
         raise SystemExit("--prefixes names shared prefixes of continuous batching: it needs --requests")
     if getattr(args, "constraints", None) is not None and getattr(args, "requests", None) is None:
@@ -1275,6 +1294,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--kv_cache", type=str, default="model", choices=("model", "fp8"), help="with --requests: the slots' KV cache. "
                    "model: the model's 16-bit dtype.  fp8: e4m3 rows with one power-of-two scale per row and KV head, about half the "
                    "bytes per slot and per step; the prompt pass and a row's own step see exact K / V, later steps see fp8")
+    p.add_argument("--attention", type=str, default="chunked", choices=("chunked", "stream"), help="with --batch_size > 1 or "
+                   "--requests: the split-KV body of the step's attention launch.  chunked: the default.  stream: the barrier-free "
+                   "body for one new token against a long cache (opt-in; same caches, outputs equal to rounding)")
     p.add_argument("--stop_token_ids", type=str, default=None, help="with --requests: token ids a,b,c (at most 16) — a request also "
                    "ends right after any of them, like --eos_id.  The default of requests that set no \"stop_token_ids\"; a request "
                    "line may also carry \"stop_sequences\" (token id lists) and, with a tokenizer, \"stop\" strings (matched as the "
